@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W            # the driver's line
     python bench.py --gpus N --config 3 [--cov full] [--frames 10000000]   # config 3 alone
+    python bench.py ... --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
 
 The default line is BASELINE config 2 (`configs[1]`, the configuration the metric is
 quoted on): GMM, K = 256 full-covariance Gaussians, D = 40, 1,000,000 fp32 frames PER
@@ -97,6 +98,25 @@ def fence(world):
     torch.cuda.synchronize()
 
 
+def dump_outputs(path, elbo, model):
+    '''--dump-outputs: what the last timed step handed its caller -- the ELBO and the posterior
+    the M-step left in every Bayesian parameter (its standard parameters, mean-field order) --
+    as `path`/<name>.npy in float64.  Inputs are seeded, so two builds compare array by array.'''
+    os.makedirs(path, exist_ok=True)
+    arrays = {'elbo': np.array(float(elbo), dtype=np.float64)}
+    for i, param in enumerate(model.bayesian_parameters()):
+        post = param.posterior
+        for name in post._std_params_def:
+            arrays[f'posterior{i:02d}_{name}'] = \
+                getattr(post.params, name).detach().to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise ValueError(f'--dump-outputs: {total} bytes, more than 64 MB')
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    print(f'dumped {len(arrays)} arrays ({total} bytes) to {path}', file=sys.stderr, flush=True)
+
+
 def max_over_ranks(elapsed, world, device, backend):
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == 'nccl' else 'cpu')
@@ -143,7 +163,7 @@ def make_gmm(device):
     return beer.Mixture.create(ns, prior_strength=1.).to(device)
 
 
-def run_gmm(args, rank, world, device, backend):
+def run_gmm(args, rank, world, device, backend, dump_dir=None):
     frames = args.frames
     if args.scaling == 'strong':              # a fixed corpus of args.frames, sharded
         frames = args.frames // world + (1 if rank < args.frames % world else 0)
@@ -209,6 +229,8 @@ def run_gmm(args, rank, world, device, backend):
         return kern
 
     elapsed, kt, elbo = timed_loop(args.steps, args.warmup)
+    if dump_dir and rank == 0:           # before the clock probe / f32_exact leg step the model again
+        dump_outputs(dump_dir, elbo, model)
     kern = kernel_table(kt, args.steps)
     # the shader clock the iteration's kernels run at on THIS box (a sleeping wave on a side stream)
     # (every rank: the step holds a collective)
@@ -372,7 +394,7 @@ def hmm_corpus(total_frames):
 
 
 def run_hmm(args, rank, world, device, backend, cov=None, total_frames=None, steps=None,
-            warmup=None, with_cpu_baseline=True, shard_of=None):
+            warmup=None, with_cpu_baseline=True, shard_of=None, dump_dir=None):
     '''`shard_of` = N (one process): this GPU takes the part of the corpus that rank 0 of an
     N-way split would take (`shard_utterances`: balanced by frame count) -- the per-rank work
     of an N-GPU run measured on one GPU; no collective runs.'''
@@ -431,6 +453,8 @@ def run_hmm(args, rank, world, device, backend, cov=None, total_frames=None, ste
         fence(world)
         elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed, world, device, backend)
+    if dump_dir and rank == 0:           # before the clock probe steps the model again
+        dump_outputs(dump_dir, elbo, ploop)
     # (every rank: a collective)
     clock = None if args.no_extras else ClockProbe(device).measure(step, 1e3 * elapsed / steps)
     if os.environ.get('BEER_BENCH_NO_KT'):
@@ -982,7 +1006,7 @@ def worker(args):
         print(json.dumps(run_config5(args, device)), flush=True)
         return
     run = run_gmm if args.config == 2 else run_hmm
-    out = run(args, rank, world, device, backend)
+    out = run(args, rank, world, device, backend, dump_dir=args.dump_outputs)
     if args.config == 2 and not args.no_config3:
         # BASELINE config 3 inside the same line: diagonal emissions on the 10 M-frame
         # corpus, full covariances on 2 M frames (every rank takes part: the corpus is
@@ -1071,6 +1095,9 @@ def main():
                     help='print the config4 sub-object alone (no config 2 / 3 runs)')
     ap.add_argument('--scaling', default='weak', choices=('weak', 'strong'),
                     help='config 2: 1 M frames per GPU (weak, default) or --frames in total (strong)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps of the headline (config 2, or 3 with --config 3), '
+                         'write the ELBO and the posteriors of its last step as DIR/<name>.npy')
     args = ap.parse_args()
     if args.frames is None:
         args.frames = 1_000_000 if args.config == 2 else 10_000_000
