@@ -129,6 +129,21 @@ class Batch(ctypes.Structure):
                 ('order', c_p)]
 
 
+class Bigram(ctypes.Structure):
+    'beer_bigram of include/beer_hip.h.'
+    _fields_ = [('n_states', ctypes.c_int32), ('n_phones', ctypes.c_int32),
+                ('max_degree', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('init', c_p), ('final', c_p),
+                ('in_ptr', c_p), ('in_src', c_p), ('in_w', c_p),
+                ('out_ptr', c_p), ('out_dst', c_p), ('out_w', c_p),
+                ('src', c_p), ('dst', c_p), ('block_w', c_p),
+                ('src_slot', c_p), ('dst_slot', c_p), ('pdf_ids', c_p)]
+
+
+BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
+BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
+
+
 class FeaConf(ctypes.Structure):
     'beer_feaconf of include/beer_hip.h.'
     _fields_ = [('flen', ctypes.c_int32), ('fstep', ctypes.c_int32),
@@ -165,6 +180,8 @@ SIGNATURES = {
     'beer_dirichlet_log_weights': _dir,
     'beer_sb_transform_stats': [c_i, c_i, c_p, c_p, c_p, c_p],
     'beer_sb_log_weights': [c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    'beer_sb_set_log_weights': [c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    'beer_sb_set_transform_stats': [c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     'beer_gamma_expected_stats': _gam, 'beer_gamma_log_norm': _gam,
     'beer_gamma_natural': _gam,
     'beer_gamma_from_natural': [c_i, c_i, c_p, c_p, c_p, c_p],
@@ -195,6 +212,8 @@ SIGNATURES = {
     'beer_hmm_posteriors_fused': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p, c_p,
                                   c_p, c_p],
     'beer_hmm_fb_log_count': [c_p, c_p, c_p, c_p],
+    'beer_hmm_posteriors_bigram': [c_i, c_p, ctypes.c_int32, c_l, c_p, c_p, c_i, c_p, c_d, c_p,
+                                   c_p, c_p, c_i, c_p, c_p],
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],

@@ -138,14 +138,24 @@ def decode_graph(loop, units):
     return loop, first, last
 
 
-PRIORS = ('dirichlet', 'dirichlet_process', 'gamma_dirichlet_process')
+PRIORS = ('dirichlet', 'dirichlet2', 'dirichlet_process', 'gamma_dirichlet_process',
+          'hierarchical_dirichlet_process')
+BIGRAM_PRIORS = ('dirichlet2', 'hierarchical_dirichlet_process')
 
 
 def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirichlet_process',
                concentration=None):
-    '`beer hmm mkphoneloop` (mkphoneloop.py:30-66).'
+    '''`beer hmm mkphoneloop` (mkphoneloop.py:30-80): a `BigramPhoneLoop` for the
+    bigram priors (`dirichlet2`, `hierarchical_dirichlet_process`), else a `PhoneLoop`.'''
     size = len(start_pdf)
     conc = concentration if concentration else size / 2
+    if weights_prior == 'dirichlet2':
+        cset = beer.CategoricalSet.create(torch.ones(size, size) / size, prior_strength=conc)
+        return beer.BigramPhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cset)
+    if weights_prior == 'hierarchical_dirichlet_process':
+        root = beer.SBCategorical.create(truncation=size, prior_strength=conc)
+        cset = beer.SBCategoricalSet.create(size, root, prior_strength=conc)
+        return beer.BigramPhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cset)
     if weights_prior == 'dirichlet':
         cat = beer.Categorical.create(torch.ones(size) / size, prior_strength=conc)
     elif weights_prior == 'dirichlet_process':
@@ -156,6 +166,22 @@ def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirich
     else:
         raise ValueError(f'unknown prior over the weights: {weights_prior!r}')
     return beer.PhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cat)
+
+
+def bigram_loop(ploop, weights_prior):
+    '''`beer hmm mkphoneloopbigram` (mkphoneloopbigram.py:14-49): a bigram loop on the
+    unigram loop's graph, emissions and phones.  `dirichlet2` ignores the unigram's weights
+    (every concentration 1 / P); the hierarchical Dirichlet process is rooted at the
+    unigram's own stick-breaking weights, with prior strength P / 2.'''
+    size = len(ploop.start_pdf)
+    if weights_prior == 'dirichlet2':
+        cset = beer.CategoricalSet.create(torch.ones(size, size) / size, prior_strength=1)
+    elif weights_prior == 'hierarchical_dirichlet_process':
+        cset = beer.SBCategoricalSet.create(size, ploop.categorical, prior_strength=size / 2)
+    else:
+        raise ValueError(f'unknown prior over the bigram weights: {weights_prior!r}')
+    return beer.BigramPhoneLoop.create(ploop.graph, ploop.start_pdf, ploop.end_pdf,
+                                       ploop.modelset, cset)
 
 
 def phones_of_path(path, start_pdf, per_frame=False):
@@ -272,6 +298,29 @@ class mkphoneloop:
         ploop = phone_loop(graph, start_pdf, end_pdf, emissions, args.weights_prior, args.concentration)
         _dump(ploop, args.out)
         logger.info(f'successfully created a phone-loop model with {size} phones')
+
+
+class mkphoneloopbigram:
+    'create a bigram phone-loop model'
+    PRIORS = BIGRAM_PRIORS
+
+    @staticmethod
+    def setup(parser):
+        # (the reference's default, gamma_dirichlet_process, is not one of its choices:
+        # the option has to be given)
+        parser.add_argument('--weights-prior', default='gamma_dirichlet_process',
+                            choices=mkphoneloopbigram.PRIORS,
+                            help='type of prior over the phone weights')
+        parser.add_argument('phoneloop', help='unigram phone loop')
+        parser.add_argument('out', help='bigram phone loop (out)')
+
+    @staticmethod
+    def main(args, logger):
+        ploop = _load(args.phoneloop)
+        ploop2 = bigram_loop(ploop, args.weights_prior)
+        _dump(ploop2, args.out)
+        logger.info('successfully created a bigram phone-loop model with '
+                    f'{len(ploop.start_pdf)} phones')
 
 
 class mkaligraph:
@@ -526,5 +575,5 @@ class posteriors:
         logger.info(f'successfully computed the posteriors for {count} utterances.')
 
 
-COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopgraph,
-            mkphones, posteriors, phonelist, train, update]
+COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
+            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update]

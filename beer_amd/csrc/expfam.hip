@@ -787,6 +787,68 @@ __global__ void sb_log_weights_big_kernel(int P, const T* __restrict__ conc,
     }
 }
 
+// n stick-breaking rows that share ONE ordering (the rows of a hierarchical Dirichlet
+// process follow their root's sticks and are never re-sorted, categoricalset.py:205-262):
+// one workgroup per row.  conc [n K, 2] -> log_w [n, K] (categories' order), the
+// arithmetic of sb_log_weights_kernel row by row.
+template <typename T>
+__global__ void sb_set_log_weights_kernel(int K, const T* __restrict__ conc,
+                                          const int64_t* __restrict__ ordering,
+                                          T* __restrict__ log_w) {
+    __shared__ double l1v[kSbMax];
+    __shared__ double lv[kSbMax];
+    const T* c = conc + (size_t)blockIdx.x * 2 * K;
+    T* out = log_w + (size_t)blockIdx.x * K;
+    for (int r = threadIdx.x; r < K; r += blockDim.x) {
+        const int i = (int)ordering[r];
+        const double a = (double)c[2 * i], b = (double)c[2 * i + 1], sd = digamma(a + b);
+        lv[r] = digamma(a) - sd;
+        l1v[r] = digamma(b) - sd;
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < K; r += blockDim.x) {
+        double acc = lv[r];
+        for (int q = 0; q < r; ++q) acc += l1v[q];
+        out[ordering[r]] = (T)acc;
+    }
+}
+
+// counts [n, K] -> the sticks' statistics [n K, 2] = (count_i, count_i + the counts of the
+// sticks after i in the shared ordering), categories' order (categoricalset.py:215-224)
+template <typename T>
+__global__ void sb_set_transform_kernel(int K, const T* __restrict__ counts,
+                                        const int64_t* __restrict__ ordering,
+                                        T* __restrict__ stats) {
+    __shared__ double v[kSbMax];              // the row's counts in stick order
+    const T* c = counts + (size_t)blockIdx.x * K;
+    T* out = stats + (size_t)blockIdx.x * 2 * K;
+    for (int r = threadIdx.x; r < K; r += blockDim.x) v[r] = (double)c[ordering[r]];
+    __syncthreads();
+    for (int r = threadIdx.x; r < K; r += blockDim.x) {
+        double tail = 0.0;
+        for (int q = K - 1; q > r; --q) tail += v[q];       // (from the last stick up)
+        const int i = (int)ordering[r];
+        out[2 * i] = c[i];
+        out[2 * i + 1] = (T)(tail + v[r]);
+    }
+}
+
+template <typename T>
+int sb_set_launch(int which, int n, int K, const void* in, const int64_t* ordering, void* out,
+                  void* stream) {
+    BEER_REQUIRE(n >= 0 && K >= 1 && K <= kSbMax);
+    if (n == 0) return BEER_OK;
+    BEER_REQUIRE(in && ordering && out);
+    if (which == 0)
+        hipLaunchKernelGGL(sb_set_log_weights_kernel<T>, dim3(n), dim3(256), 0, as_stream(stream),
+                           K, (const T*)in, ordering, (T*)out);
+    else
+        hipLaunchKernelGGL(sb_set_transform_kernel<T>, dim3(n), dim3(256), 0, as_stream(stream),
+                           K, (const T*)in, ordering, (T*)out);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
 template <typename T>
 int sb_transform_launch(int P, const void* counts, int64_t* ordering, void* stats, void* stream) {
     BEER_REQUIRE(P >= 1 && counts && ordering && stats);
@@ -908,6 +970,15 @@ int beer_sb_transform_stats(int dtype, int P, const void* counts, int64_t* order
 int beer_sb_log_weights(int dtype, int P, const void* conc, const int64_t* ordering, void* log_w,
                         void* log_1_v_sum, void* stream) {
     BEER_DISPATCH(dtype, sb_log_weights_launch, P, conc, ordering, log_w, log_1_v_sum, stream);
+}
+
+int beer_sb_set_log_weights(int dtype, int n, int K, const void* conc, const int64_t* ordering,
+                            void* log_w, void* stream) {
+    BEER_DISPATCH(dtype, sb_set_launch, 0, n, K, conc, ordering, log_w, stream);
+}
+int beer_sb_set_transform_stats(int dtype, int n, int K, const void* counts,
+                                const int64_t* ordering, void* stats, void* stream) {
+    BEER_DISPATCH(dtype, sb_set_launch, 1, n, K, counts, ordering, stats, stream);
 }
 
 int beer_gamma_expected_stats(int dtype, int n, const void* shape, const void* rate, void* out, void* stream) {

@@ -482,6 +482,78 @@ class DeviceGraph:
         return (torch.tensor(seg, dtype=torch.int32), torch.tensor(row_seg, dtype=torch.int32))
 
 
+class BigramImage:
+    '''Device image of a graph with a declared bigram block (beer_bigram of
+    include/beer_hip.h): the block trans[src][:, dst] as a dense P x P matrix, and
+    the rest of the graph as a low-degree CSR with the block's arcs removed (as the
+    hub arcs are removed from `DeviceGraph`'s low-degree image).  The dense matrix is
+    authoritative: the block is read from it, the hint only names its states.'''
+
+    def __init__(self, graph, src, dst, device, dtype):
+        trans = graph.trans_log_probs.detach()
+        trans_h = trans.to('cpu', torch.float64)
+        S = trans_h.shape[0]
+        finite = trans_h > -float('inf')
+        src_t, dst_t = torch.as_tensor(src).long(), torch.as_tensor(dst).long()
+        keep = finite.clone()
+        keep[src_t[:, None], dst_t[None, :]] = False
+        self.max_degree = int(max(keep.sum(0).max(), keep.sum(1).max())) if S else 0
+        dst_i, src_i = torch.nonzero(keep.t(), as_tuple=True)
+        in_ptr = torch.zeros(S + 1, dtype=torch.int32)
+        in_ptr[1:] = torch.cumsum(torch.bincount(dst_i, minlength=S), 0).to(torch.int32)
+        src_o, dst_o = torch.nonzero(keep, as_tuple=True)
+        out_ptr = torch.zeros(S + 1, dtype=torch.int32)
+        out_ptr[1:] = torch.cumsum(torch.bincount(src_o, minlength=S), 0).to(torch.int32)
+        src_slot = torch.full((S,), -1, dtype=torch.int32)
+        dst_slot = torch.full((S,), -1, dtype=torch.int32)
+        src_slot[src_t] = torch.arange(len(src_t), dtype=torch.int32)
+        dst_slot[dst_t] = torch.arange(len(dst_t), dtype=torch.int32)
+        pdf = graph.pdf_id_mapping
+        pdf_ids = torch.as_tensor(list(pdf) if pdf is not None else range(S), dtype=torch.int32)
+        i32 = lambda t: t.to(torch.int32)                       # noqa: E731
+        t_h = trans.to('cpu')
+        self.bufs = _hip.upload(dict(
+            init=graph.init_log_probs.detach().to('cpu', dtype),
+            final=graph.final_log_probs.detach().to('cpu', dtype),
+            in_ptr=in_ptr, in_src=i32(src_i), in_dst=i32(dst_i), in_w=t_h[src_i, dst_i].to(dtype),
+            out_ptr=out_ptr, out_src=i32(src_o), out_dst=i32(dst_o),
+            out_w=t_h[src_o, dst_o].to(dtype),
+            src=i32(src_t), dst=i32(dst_t),
+            block_w=t_h[src_t][:, dst_t].to(dtype).contiguous(),
+            src_slot=src_slot, dst_slot=dst_slot, pdf_ids=pdf_ids), device)
+        b = self.bufs
+        self._src_l, self._dst_l = b['src'].long(), b['dst'].long()
+        self.n_states, self.n_phones = S, len(src_t)
+        p = lambda name: b[name].data_ptr()                     # noqa: E731
+        self.struct = _hip.Bigram(S, self.n_phones, self.max_degree, 0, p('init'), p('final'),
+                                  p('in_ptr'), p('in_src'), p('in_w'),
+                                  p('out_ptr'), p('out_dst'), p('out_w'),
+                                  p('src'), p('dst'), p('block_w'),
+                                  p('src_slot'), p('dst_slot'), p('pdf_ids'))
+
+    @property
+    def supported(self):
+        'Within the limits of beer_hmm_posteriors_bigram.'
+        return 1 <= self.n_phones <= _hip.BIGRAM_MAX_PHONES and \
+            1 <= self.n_states <= _hip.BIGRAM_MAX_STATES and self.max_degree <= _hip.SEG
+
+    def block_weights(self):
+        'exp(trans[src][:, dst]) in fp64 as the kernel sees it (the image\'s dtype).'
+        return self.bufs['block_w'].double().exp()
+
+    def refresh(self, trans):
+        '''New transition log-probabilities on the same sparsity pattern: the weight
+        arrays re-gathered from the dense matrix on the device (no host round trip).'''
+        b = self.bufs
+        dtype = b['in_w'].dtype
+        t = trans.detach()
+        idx = lambda name: b[name].long()                        # noqa: E731
+        if b['in_w'].numel():
+            b['in_w'].copy_(t[idx('in_src'), idx('in_dst')].to(dtype))
+            b['out_w'].copy_(t[idx('out_src'), idx('out_dst')].to(dtype))
+        b['block_w'].copy_(t[self._src_l[:, None], self._dst_l[None, :]].to(dtype))
+
+
 class CompiledGraph(torch.nn.Module):
     'Inference graph of an HMM: initial, final and transition log-probabilities.'
 
@@ -505,6 +577,50 @@ class CompiledGraph(torch.nn.Module):
         if not same:
             self.__dict__.pop('_device_memo', None)
 
+    def set_bigram_block(self, src_states, src_log_w, dst_states, log_w_matrix):
+        '''Declare that trans_log_probs[src_i, dst_j] == src_log_w[i] + log_w_matrix[i, j]
+        (the P x P end -> start block of a bigram phone loop).  Like `set_hub`, purely an
+        acceleration hint: the dense matrix stays authoritative -- the block's weights are
+        read from it -- and the states are checked before the image is used
+        (`bigram_image`).'''
+        src, dst = [int(i) for i in src_states], [int(i) for i in dst_states]
+        old = self.__dict__.get('bigram')
+        same = old is not None and old[0] == src and old[2] == dst
+        self.bigram = (src, src_log_w.detach().clone(), dst, log_w_matrix.detach().clone())
+        if not same:
+            self.__dict__.pop('_bigram_memo', None)
+
+    def bigram_image(self, dtype):
+        '''`BigramImage` of the declared bigram block in `dtype`, or None when no block is
+        declared or the declared one does not qualify (repeated or out-of-range states,
+        more phones / states / residual arcs than the kernel takes).  Refreshed in place
+        when `trans_log_probs` was rewritten on the same pattern, rebuilt otherwise.'''
+        hint = self.__dict__.get('bigram')
+        if hint is None:
+            return None
+        src, _, dst, _ = hint
+        S = self.n_states
+        if len(src) != len(dst) or len(set(src)) != len(src) or len(set(dst)) != len(dst) or \
+                not all(0 <= i < S for i in src + dst) or not src or \
+                len(src) > _hip.BIGRAM_MAX_PHONES or S > _hip.BIGRAM_MAX_STATES:
+            return None
+        tensors = (self.init_log_probs, self.final_log_probs, self.trans_log_probs)
+        sig = tuple(t._version for t in tensors)
+        memo = self.__dict__.get('_bigram_memo')
+        if memo is not None and memo[0] == dtype and all(a is b for a, b in zip(memo[1], tensors)):
+            if memo[2] == sig:
+                return memo[3]
+            if self.__dict__.pop('_bigram_rewritten', False) and memo[2][:2] == sig[:2] and \
+                    self.trans_log_probs.device.type == 'cuda' and memo[3] is not None:
+                memo[3].refresh(self.trans_log_probs)
+                self.__dict__['_bigram_memo'] = (dtype, tensors, sig, memo[3])
+                return memo[3]
+        self.__dict__.pop('_bigram_rewritten', None)
+        img = BigramImage(self, src, dst, _hip.require_device(), dtype)
+        img = img if img.supported else None
+        self.__dict__['_bigram_memo'] = (dtype, tensors, sig, img)
+        return img
+
     def weights_rewritten(self):
         '''Tell the graph that `trans_log_probs` was rewritten in place on the
         same sparsity pattern (finite entries stay finite): its device image
@@ -512,8 +628,17 @@ class CompiledGraph(torch.nn.Module):
         the matrix lives on the GPU (index kernels on the current stream: part of
         a captured M-step when one is being recorded), at the next inference
         otherwise.'''
-        memo = self.__dict__.get('_device_memo')
         tensors = (self.init_log_probs, self.final_log_probs, self.trans_log_probs)
+        bmemo = self.__dict__.get('_bigram_memo')
+        if bmemo is not None and bmemo[3] is not None and self.trans_log_probs.is_cuda and \
+                all(a is b for a, b in zip(bmemo[1], tensors)) and \
+                bmemo[2][:2] == tuple(t._version for t in tensors[:2]):
+            bmemo[3].refresh(self.trans_log_probs)
+            self.__dict__['_bigram_memo'] = (bmemo[0], tensors,
+                                             tuple(t._version for t in tensors), bmemo[3])
+        elif bmemo is not None:
+            self.__dict__['_bigram_rewritten'] = True
+        memo = self.__dict__.get('_device_memo')
         if memo is not None and self.trans_log_probs.is_cuda and \
                 all(a is b for a, b in zip(memo[1], tensors)) and \
                 memo[2][:2] == tuple(t._version for t in tensors[:2]):
@@ -534,6 +659,8 @@ class CompiledGraph(torch.nn.Module):
         state = self.__dict__.copy()
         state.pop('_device_memo', None)
         state.pop('_weights_rewritten', None)
+        state.pop('_bigram_memo', None)
+        state.pop('_bigram_rewritten', None)
         state.pop('_batch_cache', None)
         return state
 

@@ -11,7 +11,8 @@ from . import _hip
 
 __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors',
            'scatter', 'gather_columns', 'scatter_columns', 'segment_sum', 'fused_ok',
-           'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space']
+           'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space', 'bigram_ok',
+           'posteriors_bigram']
 
 
 class HmmBatch:
@@ -55,6 +56,7 @@ class HmmBatch:
             ld_info = (gset.max_degree, 0, 0)                   # alignment chains: no hub
         else:
             self.dgraphs = [g.device_graph(dtype) for g in graphs]
+            self.source_graphs = list(graphs)
             n_states = [dg.n_states for dg in self.dgraphs]
             parts = [np.asarray(g.pdf_id_mapping, dtype=np.int32)
                      if (with_pdf_ids and g.pdf_id_mapping is not None)
@@ -288,6 +290,71 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
               _hip.ptr(frame_llh))
     counting_log_space.note(batch, hub_ws)
     return sr, g0, flow
+
+
+def bigram_ok(batch):
+    '''True when `posteriors_bigram` takes the batch on its kernel: one graph for every
+    utterance, with a declared bigram block (CompiledGraph.set_bigram_block) of at most
+    128 phones on at most 512 states, every other state with at most 8 arcs a side.
+    Chosen by the declared block, not by the graph's degree.'''
+    graphs = getattr(batch, 'source_graphs', None)
+    if not batch.shared_graph or not graphs or not hasattr(graphs[0], 'bigram_image'):
+        return False
+    return graphs[0].bigram_image(batch.dtype) is not None
+
+
+def posteriors_bigram(batch, pc_all, scale=1., utt_llh=None):
+    '''Gather + forward-backward + scatter of a free bigram loop in one launch
+    (`beer_hmm_posteriors_bigram`): (state_resps [n_frames, S_total] = scale * gamma at
+    the pdf ids, counts [P, P] fp64 = sum over utterances and frames of the transition
+    posteriors of the block, row i = source src_i).  `utt_llh` [nutt] fp64 +=
+    sum_t sum_s gamma * scale * pc.  Batches the kernel does not take (`bigram_ok`), and
+    sub-batches in which an utterance left fp64's range, go through the general
+    log-space path (`forward_backward(want_xi=True)`), with the same results.'''
+    dt, dev = batch.dtype, batch.device
+    pc_all = _hip.on_device(pc_all, dt)
+    S_total = pc_all.shape[1]
+    graph = batch.source_graphs[0] if getattr(batch, 'source_graphs', None) else None
+    img = graph.bigram_image(dt) if (graph is not None and batch.shared_graph) else None
+    if img is not None and torch.cuda.is_current_stream_capturing():
+        # (the flags are read on the host below: such an E-step cannot be recorded)
+        raise _hip.HipInvalid('posteriors_bigram reads its range flags on the host: '
+                              'not recordable as a HIP graph')
+    if img is not None:
+        if len(batch._pdf_ids_h) and int(batch._pdf_ids_h.max()) >= S_total:
+            raise ValueError(f'posteriors_bigram: a pdf id of the graph is not below {S_total}')
+        repeats, covers = batch.pdf_ids_profile(S_total)
+        atomic = repeats or not covers
+        sr = (torch.zeros if atomic else torch.empty)(batch.n_frames, S_total, dtype=dt,
+                                                      device=dev)
+        P, N = img.n_phones, batch.n_frames
+        alpha = torch.empty(N * img.n_states, dtype=torch.float64, device=dev)
+        uv = torch.empty(2, N, P, dtype=torch.float64, device=dev)
+        llh = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+        flags = torch.empty(batch.nutt, dtype=torch.int32, device=dev)
+        b = batch.bufs
+        _hip.call('beer_hmm_posteriors_bigram', _hip.dtype_code(dt), ctypes.byref(img.struct),
+                  batch.nutt, N, _hip.ptr(b['frame_off']), _hip.ptr(b['order']), S_total,
+                  _hip.ptr(pc_all), float(scale), _hip.ptr(alpha), _hip.ptr(uv), _hip.ptr(sr),
+                  1 if atomic else 0, _hip.ptr(llh), _hip.ptr(flags))
+        # (one look at the flags per sub-batch: an utterance the linear-domain recursion
+        #  could not hold is redone, with the whole sub-batch, in log space below)
+        if not bool(flags.any()):
+            counts = img.block_weights() * (uv[0].t() @ uv[1])
+            if utt_llh is not None:
+                utt_llh += llh
+            return sr, counts
+    # the general path: log-space forward-backward with the summed transition posteriors
+    if graph is None or graph.__dict__.get('bigram') is None:
+        raise ValueError('posteriors_bigram: one graph with a declared bigram block '
+                         '(CompiledGraph.set_bigram_block)')
+    pc_llhs = gather(batch, pc_all, scale)
+    gamma, xi, _, _, flow = forward_backward(batch, pc_llhs, want_xi=True, dense_xi=True)
+    sr, _ = scatter(batch, pc_llhs, gamma, S_total, scale, want_exp_llh=False, utt_llh=utt_llh)
+    src, _, dst, _ = graph.bigram
+    src_t = torch.as_tensor(src, device=dev)
+    dst_t = torch.as_tensor(dst, device=dev)
+    return sr, xi[src_t[:, None], dst_t[None, :]]
 
 
 def viterbi(batch, pc_llhs, map_pdf=False):

@@ -26,7 +26,7 @@ from .. import _hip, hmm_kernels as hk, kernels
 from ..models.gaussians import NormalSet
 from ..models.mixtures import Mixture, MixtureSet
 from ..models.modelset import JointModelSet
-from ..models.sequence import HMM, PhoneLoop
+from ..models.sequence import HMM, BigramPhoneLoop, PhoneLoop
 from ..models.vae import VAE
 from ..models.weights import SBCategorical
 from ..stats import FrameStats
@@ -349,12 +349,17 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     skey = ('hmm', nutt, float(datasize), str(dev))
     off, scales = statics.entry(skey, 'offsets', offsets_and_scales)
     xi_tot = g0_tot = flow_tot = None
+    bigram = free_loop and isinstance(model, BigramPhoneLoop)
+    counts_tot = None
     max_S = model.graph.n_states if free_loop else max(g.n_states for g in graphs)
     # scratch per frame: the responsibilities of the groups whose accumulation does
     # not recompute them, per-state likelihoods / posteriors, the trellis
     K_scratch = sum(S * G for grp, S, G in groups if G > 1 and not kernels.fused_accumulate_ok(
         FrameStats(X, _normalset(grp).cov_type), S, G, _normalset(grp).cov_type))
     bpf = (K_scratch + 2 * S_total) * X.element_size() + max_S * (3 * X.element_size() + 8)
+    if bigram:
+        model.declare_block()
+        bpf += 16 * len(model.start_pdf)          # the u / v rows the bigram counts come from
     if frame_images is None or not frame_images.covers(X):
         # frame fragment images built per sub-batch and freed with it (the caller keeps none)
         bpf += max((_hip.lib().beer_frame_image_bytes(
@@ -407,6 +412,14 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                 statics.items.pop(bkey)
                 batch, _, uniq, images = statics.entry(skey, bkey, make_batch)
         hard = viterbi or state_paths is not None
+        if bigram and not hard:
+            # the fused bigram kernel (the general path when the block does not qualify)
+            sr, counts = hk.posteriors_bigram(batch, pc_all, scale,
+                                              utt_llh=utt_llh[run[0]:run[-1] + 1])
+            counts_tot = counts if counts_tot is None else counts_tot + counts
+            _accumulate_emissions(groups, comps, accs, sr, stats)
+            done.record()
+            continue
         # phone counts come from the flows through the loop's hub (the eliminated
         # pivot); a loop whose end -> start arcs stayed ordinary arcs needs xi
         need_counts = free_loop and isinstance(model, PhoneLoop)
@@ -436,21 +449,7 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                 g0_tot = g0 if g0_tot is None else g0_tot + g0
             if flow is not None:
                 flow_tot = flow if flow_tot is None else flow_tot + flow
-        first = 0
-        for (grp, S, G), comp, acc in zip(groups, comps, accs):
-            ns = _normalset(grp)
-            sr_g = sr if len(groups) == 1 else sr[:, first:first + S].contiguous()
-            first += S
-            gstats = stats.as_cov(ns.cov_type)
-            if G == 1:
-                kernels.normal_accumulate(gstats, sr_g, None, S, 1, ns.cov_type, acc=acc)
-            elif isinstance(comp, tuple):
-                # responsibilities recomputed inside the accumulation: no [T, K] matrix
-                kernels.mixtureset_accumulate_fused(
-                    gstats, ns.means_precisions.natural_form(), comp[2], comp[1], sr_g, S, G,
-                    ns.cov_type, acc=acc)
-            else:
-                kernels.normal_accumulate(gstats, comp, sr_g, S, G, ns.cov_type, acc=acc)
+        _accumulate_emissions(groups, comps, accs, sr, stats)
         done.record()
     value_terms = (scales * utt_llh).sum()
     out = {}
@@ -460,6 +459,11 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         if isinstance(grp, MixtureSet):
             wparam = grp.categoricalset.weights
             out[wparam] = _like(wparam, kernels.weights_from_acc(acc, S, G))
+    if isinstance(model, BigramPhoneLoop):
+        if bigram and counts_tot is None and xi_tot is not None:       # (Viterbi training)
+            counts_tot = model.bigram_counts(xi_tot)
+        # (alignment graphs: zero counts -- INTEGRATION.md)
+        out.update(model.weights_accumulate(counts_tot if bigram else None))
     if isinstance(model, PhoneLoop):
         wparam = model.categorical.mean_field_factorization()[0][0]
         ref = wparam.stats
@@ -474,6 +478,25 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
             fake = torch.zeros(len(model.start_pdf), dtype=ref.dtype, device=ref.device)
             out.update(model.categorical.accumulate(fake[None, :]))
     return value_terms, out
+
+
+def _accumulate_emissions(groups, comps, accs, sr, stats):
+    'The emissions\' statistics of a sub-batch from its posteriors at the pdf ids.'
+    first = 0
+    for (grp, S, G), comp, acc in zip(groups, comps, accs):
+        ns = _normalset(grp)
+        sr_g = sr if len(groups) == 1 else sr[:, first:first + S].contiguous()
+        first += S
+        gstats = stats.as_cov(ns.cov_type)
+        if G == 1:
+            kernels.normal_accumulate(gstats, sr_g, None, S, 1, ns.cov_type, acc=acc)
+        elif isinstance(comp, tuple):
+            # responsibilities recomputed inside the accumulation: no [T, K] matrix
+            kernels.mixtureset_accumulate_fused(
+                gstats, ns.means_precisions.natural_form(), comp[2], comp[1], sr_g, S, G,
+                ns.cov_type, acc=acc)
+        else:
+            kernels.normal_accumulate(gstats, comp, sr_g, S, G, ns.cov_type, acc=acc)
 
 
 def _vae_batch(model, X, lengths, datasize, nsamples, llh_weight, kl_weight):

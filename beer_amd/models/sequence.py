@@ -12,9 +12,9 @@ from ..stats import reference_layout_enabled
 from .basemodel import DiscreteLatentModel
 from .gaussians import NormalSet
 from .modelset import DynamicallyOrderedModelSet
-from .weights import Categorical, SBCategorical
+from .weights import Categorical, CategoricalSet, SBCategorical, SBCategoricalSet
 
-__all__ = ['HMM', 'PhoneLoop']
+__all__ = ['HMM', 'PhoneLoop', 'BigramPhoneLoop']
 
 
 class HMM(DiscreteLatentModel):
@@ -281,3 +281,167 @@ class PhoneLoop(HMM):
             fake = torch.zeros(len(self.start_pdf), dtype=ref.dtype, device=ref.device)
             retval.update(self.categorical.accumulate(fake[None, :]))
         return retval
+
+
+class BigramPhoneLoop(HMM):
+    '''Phone-loop HMM with a bigram language model: a prior over the P x P phone
+    transition weights (`CategoricalSet`: Dirichlet rows; `SBCategoricalSet`: the
+    hierarchical Dirichlet process).  API and pickled attributes of
+    beer/models/phoneloop.py:104-191.
+
+    A free loop runs on the fused kernel of the declared bigram block
+    (`beer_hmm_posteriors_bigram`, csrc/hmm_bigram.hip) and counts the block's
+    transition posteriors only -- no first-frame term, unlike the unigram loop
+    (phoneloop.py:174-186).'''
+
+    @classmethod
+    def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,
+               prior_strength=1.0):
+        tensor = modelset.mean_field_factorization()[0][0].prior._tensors()[0]
+        if categoricalset is None:
+            weights = torch.ones(len(start_pdf), len(start_pdf), dtype=tensor.dtype,
+                                 device=tensor.device)
+            weights /= len(start_pdf)
+            categoricalset = CategoricalSet.create(weights, prior_strength)
+        return cls(graph, modelset, start_pdf, end_pdf, categoricalset)
+
+    def __init__(self, graph, modelset, start_pdf, end_pdf, categoricalset):
+        super().__init__(graph, modelset)
+        self.start_pdf = start_pdf
+        self.end_pdf = end_pdf
+        self.categoricalset = categoricalset
+        param = self.categoricalset.mean_field_factorization()[0][0]
+        param.register_callback(self._on_weights_update)
+        self._on_weights_update()
+
+    _index_tensors = PhoneLoop._index_tensors
+
+    def _emissions(self):
+        # (built from a unigram loop's `modelset`, the emissions come wrapped twice, as in
+        # the reference's mkphoneloopbigram: the pdf-id order is the graph's, not theirs)
+        ems = self.modelset.original_modelset
+        while isinstance(ems, DynamicallyOrderedModelSet):
+            ems = ems.original_modelset
+        return ems
+
+    def _on_weights_update(self):
+        '''trans[end_i, start_j] = ln(1 - loop_i) + L[i, j] (phoneloop.py:147-156), L the
+        prior's own E[ln w] of the one-hot rows (a `CategoricalSet` gives it transposed, the
+        stick-breaking set row by row: INTEGRATION.md), then the block is declared to the
+        graph for the fused kernel.'''
+        trans = self.graph.trans_log_probs
+        cset = self.categoricalset
+        # the reference's expected_log_likelihood of the one-hot rows, without the product:
+        # E[ln pi]^T for Dirichlet rows, E[ln pi] row by row for the stick-breaking set
+        log_weights = cset.log_weights().t() if isinstance(cset, CategoricalSet) \
+            else cset.log_weights()
+        log_weights = log_weights.to(dtype=trans.dtype, device=trans.device)
+        start_idxs = list(self.start_pdf.values())
+        end_idxs = list(self.end_pdf.values())
+        ends, starts = self._index_tensors(trans.device)
+        residuals = (1 - trans[ends, ends].exp()).log()
+        unique = len(set(end_idxs)) == len(end_idxs) and len(set(start_idxs)) == len(start_idxs)
+        if unique:
+            trans[ends[:, None], starts[None, :]] = residuals[:, None] + log_weights
+        else:                                    # repeated states: last write wins
+            for i, end_idx in enumerate(end_idxs):
+                trans[end_idx, start_idxs] = residuals[i] + log_weights[i]
+        self.graph.weights_rewritten()
+        if unique:
+            self.graph.set_bigram_block(end_idxs, residuals, start_idxs, log_weights)
+
+    # index arithmetic and kernels on device tensors when the graph and the weights live on
+    # the GPU: the update of the weights' group may be captured as a HIP graph
+    # (parameters.py: register_callback), as PhoneLoop's
+    def _weights_update_capturable(self):
+        if not self.graph.trans_log_probs.is_cuda:
+            return False
+        cset = self.categoricalset
+        conc = cset.mean_field_factorization()[0][0].posterior.params.concentrations
+        if not conc.is_cuda:
+            return False
+        if isinstance(cset, SBCategoricalSet) and not cset.ordering.is_cuda:
+            return False
+        self._index_tensors(self.graph.trans_log_probs.device)
+        return True
+
+    _on_weights_update.device_only = _weights_update_capturable
+
+    def mean_field_factorization(self):
+        from .mixtures import _merge_groups
+        return _merge_groups(self.modelset.mean_field_factorization(),
+                             self.categoricalset.mean_field_factorization())
+
+    def declare_block(self):
+        '''Declare the end -> start block to the graph if it is not (a model unpickled from
+        the reference, or moved to another device, has no declaration): the block as the
+        dense matrix holds it.'''
+        graph = self.graph
+        ends, starts = list(self.end_pdf.values()), list(self.start_pdf.values())
+        hint = graph.__dict__.get('bigram')
+        if hint is None or hint[0] != ends or hint[2] != starts:
+            block = graph.trans_log_probs[torch.as_tensor(ends)[:, None],
+                                          torch.as_tensor(starts)[None, :]]
+            graph.set_bigram_block(ends, torch.zeros(len(ends), dtype=block.dtype), starts, block)
+
+    def bigram_counts(self, xi):
+        '''The end -> start block [P, P] of transition posteriors summed over time
+        (`xi` [S, S], or the reference's per-frame [T-1, S, S]).'''
+        ends, starts = self._index_tensors(xi.device)
+        if xi.dim() == 3:
+            xi = xi.sum(dim=0)
+        return xi[ends[:, None], starts[None, :]]
+
+    def expected_log_likelihood(self, stats, inference_graph=None, viterbi=False,
+                                state_path=None, scale=1., utt_lengths=None):
+        '''As HMM.expected_log_likelihood; the free loop (no inference graph, no Viterbi,
+        summed transition posteriors) runs on the fused bigram kernel as a ragged batch of
+        one or of `utt_lengths` utterances.'''
+        if inference_graph is not None or viterbi or state_path is not None or \
+                (reference_layout_enabled() and utt_lengths is None):
+            self.cache.pop('bigram_counts', None)
+            self.cache.pop('trans_resps', None)
+            return super().expected_log_likelihood(stats, inference_graph, viterbi, state_path,
+                                                   scale, utt_lengths)
+        dense = kernels.is_dense(stats)
+        emissions = self._emissions()
+        pc_all = emissions.expected_log_likelihood(stats.detach())
+        self.modelset.cache['order'] = self.graph.pdf_id_mapping
+        T = pc_all.shape[0]
+        lengths = [T] if utt_lengths is None else [int(n) for n in utt_lengths]
+        if sum(lengths) != T:
+            raise ValueError('utt_lengths do not add up to the number of frames')
+        self.declare_block()
+        batch = hk.HmmBatch([self.graph], [0] * len(lengths), lengths, pc_all.dtype)
+        state_resps, counts = hk.posteriors_bigram(batch, pc_all, scale)
+        # sum_s gamma_ts * scale * l_ts per frame (hmm.py:87) from the scattered posteriors
+        exp_llh = (state_resps * _hip.on_device(pc_all)).sum(dim=1)
+        for key in ('resps', 'trans_resps', 'hub_flow', 'first_resps'):
+            self.cache.pop(key, None)
+        self.cache['bigram_counts'] = counts
+        self.cache['scaled_pdf_resps'] = state_resps
+        self.cache['scale'] = scale
+        return self._with_gradient(stats, exp_llh, state_resps, emissions, dense)
+
+    def accumulate(self, stats, parent_msg=None):
+        retval = HMM.accumulate(self, stats, parent_msg)
+        self.cache.pop('resps', None)
+        counts = self.cache.get('bigram_counts')
+        if counts is None and self.cache.get('trans_resps') is not None:
+            counts = self.bigram_counts(self.cache['trans_resps'])
+        retval.update(self.weights_accumulate(counts))
+        return retval
+
+    def weights_accumulate(self, counts):
+        '''Statistics of the bigram weights from the summed block counts [P, P]; None
+        (trained with alignment graphs): zero counts.  The reference crashes there
+        (`CategoricalSet.accumulate` needs responsibilities, `SBCategoricalSet.accumulate`
+        is not implemented); zero counts are what its code means to give.'''
+        param = self.categoricalset.mean_field_factorization()[0][0]
+        ref = param.posterior.params.concentrations
+        P = len(self.start_pdf)
+        if counts is None:
+            counts = torch.zeros(P, P, dtype=ref.dtype, device=ref.device)
+        counts = counts.to(dtype=ref.dtype, device=ref.device)
+        cstats = self.categoricalset.sufficient_statistics(counts)
+        return self.categoricalset.accumulate_from_jointresps(cstats[None])

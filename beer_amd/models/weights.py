@@ -24,7 +24,8 @@ from .basemodel import Model
 from .modelset import ModelSet
 from .parameters import ConjugateBayesianParameter
 
-__all__ = ['Categorical', 'SBCategorical', 'SBCategoricalHyperPrior', 'CategoricalSet']
+__all__ = ['Categorical', 'SBCategorical', 'SBCategoricalHyperPrior', 'CategoricalSet',
+           'SBCategoricalSet']
 
 
 def _twin(dist_cls, *std_params):
@@ -207,3 +208,114 @@ class SBCategoricalHyperPrior(SBCategorical):
         n_sticks = torch.full_like(tail, float(len(self.ordering)))
         self.concentration.stats = torch.stack([tail, n_sticks]).to(self.concentration.stats.device)
         self.concentration.natural_grad_update(lrate=1.)
+
+
+# ---- a set of stick-breaking categoricals under one root (hierarchical DP) ---------------
+
+class SBCategoricalSet(Model):
+    '''n_components stick-breaking categoricals (the rows of a bigram model) whose prior
+    is centred on a root `SBCategorical`: the hierarchical Dirichlet process of
+    beer/models/categoricalset.py:167-307.  Every row's sticks follow the ROOT's ordering
+    and are never re-sorted; the root itself is not re-estimated (the reference leaves its
+    update unregistered) and is not part of the mean-field groups.'''
+
+    @classmethod
+    def create(cls, n_components, root_sb_categorical, prior_strength=1.,
+               optim_cls=torch.optim.Adam, optim_args=None, epochs=15_000):
+        if optim_args is None:
+            optim_args = {'lr': 1e-3}
+        if not isinstance(root_sb_categorical, SBCategorical):
+            raise ValueError('the hierarchical Dirichlet process needs a stick-breaking root '
+                             f'(SBCategorical), got {type(root_sb_categorical).__name__}: a '
+                             'unigram trained with the "dirichlet" prior has no sticks')
+        mean = root_sb_categorical.mean
+        K = len(mean)
+        params = torch.ones(n_components, K, 2, dtype=mean.dtype, device=mean.device)
+        # the prior from the root's mean and 1 - its running sum, in CATEGORY order
+        # (categoricalset.py:141-154)
+        params[:, :, 0] = prior_strength * mean
+        params[:, :, 1] = prior_strength * (1 - mean.cumsum(dim=0))
+        prior = Dirichlet.from_std_parameters(params.reshape(-1, 2))
+        post = root_sb_categorical.stickbreaking.posterior.params.concentrations
+        posterior = Dirichlet.from_std_parameters(post.repeat(n_components, 1).clone())
+        param = ConjugateBayesianParameter(prior, posterior)
+        return cls(n_components, param, root_sb_categorical, prior_strength, optim_cls,
+                   optim_args, epochs)
+
+    def __init__(self, n_components, stickbreaking, root_sb_categorical, concentration,
+                 optim_cls, optim_args, epochs):
+        super().__init__()
+        self.n_components = n_components
+        self.stickbreaking = stickbreaking
+        self.root_sb_categorical = root_sb_categorical
+        self.concentration = concentration
+        self.optim_cls = optim_cls
+        self.optim_args = optim_args
+        self.epochs = epochs
+        stickbreaking.register_callback(self._transform_stats, notify_before_update=True)
+
+    @property
+    def ordering(self):
+        return self.root_sb_categorical.ordering
+
+    @property
+    def reverse_ordering(self):
+        return self.root_sb_categorical.reverse_ordering
+
+    def _conc(self):
+        return _hip.on_device(self.stickbreaking.posterior.params.concentrations)
+
+    def _transform_stats(self):
+        '''Before the update: the counts [n, K] of every row, in the root's stick order,
+        as the sticks' statistics [n K, 2]: (count of the stick, counts of it and of the
+        sticks after it) (categoricalset.py:215-224); `beer_sb_set_transform_stats`.'''
+        home = self.stickbreaking.stats.device
+        counts = _hip.on_device(self.stickbreaking.stats)
+        order = _hip.on_device(self.ordering)
+        K = order.shape[0]
+        pairs = torch.empty(self.n_components * K, 2, dtype=counts.dtype, device=counts.device)
+        _hip.call('beer_sb_set_transform_stats', _hip.dtype_code(counts.dtype),
+                  self.n_components, K, _hip.ptr(counts), _hip.ptr(order), _hip.ptr(pairs))
+        self.stickbreaking.stats = pairs.to(home)
+
+    def _log_prob_rows(self):
+        '''E[ln pi] of every row [n, K] in category order, every row's sticks in the root's
+        order: one `beer_sb_set_log_weights` launch.'''
+        conc = self._conc()
+        order = _hip.on_device(self.ordering)
+        K = order.shape[0]
+        out = torch.empty(self.n_components, K, dtype=conc.dtype, device=conc.device)
+        _hip.call('beer_sb_set_log_weights', _hip.dtype_code(conc.dtype), self.n_components, K,
+                  _hip.ptr(conc), _hip.ptr(order), _hip.ptr(out))
+        return out
+
+    @property
+    def mean(self):
+        c = self.stickbreaking.posterior.params.concentrations
+        c = c.reshape(self.n_components, -1, 2)[:, self.ordering.to(c.device), :]
+        norm = c.sum(dim=-1) + torch.finfo(c.dtype).eps
+        weights = c[:, :, 0] / norm
+        residual = (c[:, :, 1] / norm).cumprod(dim=1)
+        weights[:, 1:] = weights[:, 1:] * residual[:, :-1]
+        return weights[:, self.reverse_ordering.to(c.device)]
+
+    def sufficient_statistics(self, data):
+        return data
+
+    def mean_field_factorization(self):
+        return [[self.stickbreaking]]
+
+    def log_weights(self):
+        'E[ln pi] of every row [n, K], categories in their own order.'
+        return self._log_prob_rows()
+
+    def expected_log_likelihood(self, stats):
+        log_prob = self._log_prob_rows()
+        return stats @ log_prob.to(dtype=stats.dtype, device=stats.device)
+
+    def accumulate(self, stats):
+        raise NotImplementedError('SBCategoricalSet is trained from joint responsibilities '
+                                  '(accumulate_from_jointresps)')
+
+    def accumulate_from_jointresps(self, stats):
+        return {self.stickbreaking: stats.sum(dim=0)}

@@ -196,6 +196,17 @@ int beer_sb_transform_stats(int dtype, int P, const void* counts, int64_t* order
                             void* stats, void* stream);
 int beer_sb_log_weights(int dtype, int P, const void* conc, const int64_t* ordering,
                         void* log_w, void* log_1_v_sum, void* stream);
+/* n stick-breaking rows of K sticks that share ONE ordering: the rows of a hierarchical
+ * Dirichlet process (SBCategoricalSet, beer/models/categoricalset.py:167-307), which follow
+ * their root's ordering and are never re-sorted.  K <= 1024; one workgroup per row.
+ * beer_sb_set_log_weights: conc [n K, 2] -> log_w [n, K], E[ln pi] of every row in the
+ * categories' order (categoricalset.py:264-281).
+ * beer_sb_set_transform_stats: counts [n, K] -> stats [n K, 2] = (count_i, count_i + the
+ * counts of the sticks after i), categories' order (categoricalset.py:215-224). */
+int beer_sb_set_log_weights(int dtype, int n, int K, const void* conc, const int64_t* ordering,
+                            void* log_w, void* stream);
+int beer_sb_set_transform_stats(int dtype, int n, int K, const void* counts,
+                                const int64_t* ordering, void* stats, void* stream);
 /* E[ln pi] of S categoricals: the `eye -> sufficient_statistics -> stats @
  * E[T]` sequence of Mixture._log_weights (beer/models/mixture.py:45-48) and
  * MixtureSet._log_weights (mixtureset.py:64-67) -> out [S,G]. */
@@ -595,6 +606,60 @@ int beer_hmm_posteriors_fused(int dtype, const beer_batch* batch_h, int S_total,
                               double* hub_ws, void* state_resps, int atomic_out,
                               double* gamma0_sum, double* hub_flow, double* utt_llh,
                               void* frame_llh, void* stream);
+
+/* A phone loop with a BIGRAM language model (beer/models/phoneloop.py:104-191):
+ * its end -> start block trans[src[i], dst[j]] = ln(1 - loop_i) + E[ln w][i, j] is a
+ * full P x P matrix, kept apart from the rest of the graph (a low-degree CSR: the
+ * arcs of the block removed, every row <= BEER_SEG arcs).  Device arrays; weights in
+ * the model's dtype. */
+#define BEER_BIGRAM_MAX_PHONES 128
+#define BEER_BIGRAM_MAX_STATES 512
+typedef struct {
+    int32_t n_states;          /* S <= BEER_BIGRAM_MAX_STATES */
+    int32_t n_phones;          /* P <= BEER_BIGRAM_MAX_PHONES */
+    int32_t max_degree;        /* largest in / out degree of the residual CSR */
+    int32_t reserved;
+    const void* init;          /* [S] */
+    const void* final;         /* [S] */
+    const int32_t* in_ptr;     /* [S+1] residual arcs by destination */
+    const int32_t* in_src;
+    const void* in_w;
+    const int32_t* out_ptr;    /* [S+1] residual arcs by source */
+    const int32_t* out_dst;
+    const void* out_w;
+    const int32_t* src;        /* [P] the block's source states (phone ends) */
+    const int32_t* dst;        /* [P] its destination states (phone starts) */
+    const void* block_w;       /* [P, P] trans[src[i], dst[j]] */
+    const int32_t* src_slot;   /* [S] i of a source state, -1: none */
+    const int32_t* dst_slot;   /* [S] j of a destination state, -1: none */
+    const int32_t* pdf_ids;    /* [S] */
+} beer_bigram;
+
+/* The HMM inference step of a free bigram loop over a ragged batch of utterances,
+ * in ONE launch (graph.py:270-326, hmm.py:73-95): the pdf-id gather with the acoustic
+ * scale, forward-backward (scaled linear domain, fp64 trellis, the block as a
+ * matrix-vector product per frame from LDS), the scatter of scale * gamma to pdf ids
+ * and sum_t sum_s gamma * scale * pc per utterance.
+ *   frame_off     [nutt+1] device, frames of the batch (0-based), n_frames in all
+ *   order         [nutt] device, nullable: the order utterances are handed to waves
+ *   pc_all        [n_frames, S_total] per-pdf log-likelihoods
+ *   alpha_ws      [n_frames, S] fp64 scratch
+ *   uv_ws         [2, n_frames, P] fp64: U[f] = a_t(src) / n_t and V[f] = b_{t+1}
+ *                 beta_{t+1}(dst) of frame f = frame_off[u] + t (0 for the last frame
+ *                 of an utterance); the block's summed transition posteriors are
+ *                 C = exp(block) o (U^T V) (phoneloop.py:174-186)
+ *   state_resps   [n_frames, S_total]; atomic_out != 0: added into a zero-filled array
+ *                 (repeated pdf ids), else plain stores (distinct ids covering S_total)
+ *   utt_llh       [nutt] fp64, written (not added)
+ *   flags         [nutt] int32: 1 where an utterance left fp64's range (it then
+ *                 contributes nothing valid: redo the batch in log space)
+ * EINVAL beyond BEER_BIGRAM_MAX_PHONES / _STATES or BEER_SEG residual arcs. */
+int beer_hmm_posteriors_bigram(int dtype, const beer_bigram* graph, int32_t nutt,
+                               int64_t n_frames, const int64_t* frame_off,
+                               const int32_t* order, int S_total, const void* pc_all,
+                               double scale, double* alpha_ws, double* uv_ws,
+                               void* state_resps, int atomic_out, double* utt_llh,
+                               int32_t* flags, void* stream);
 
 /* Per-frame transition posteriors in the reference's own layout, xi [T-1, S, S]
  * (beer/graph.py:308-323: normalised per frame, NaN -> 0), for ONE utterance,
