@@ -28,7 +28,6 @@ from ..models.mixtures import Mixture, MixtureSet
 from ..models.modelset import JointModelSet
 from ..models.sequence import HMM, BigramPhoneLoop, PhoneLoop
 from ..models.vae import VAE
-from ..models.weights import SBCategorical
 from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
@@ -110,23 +109,22 @@ def pack_utterances(utterances):
 
 
 def _groups(emissions):
-    'Flatten an emission model into [(MixtureSet | NormalSet, S, G)].'
+    '''Flatten an emission model into [(MixtureSet | NormalSet, S, G)].  A nested
+    MixtureSet is one group of S mixtures of its G leaves (`MixtureSet.leaf_log_weights`).'''
     if isinstance(emissions, JointModelSet):
         out = []
         for m in emissions.modelsets:
             out += _groups(m)
         return out
     if isinstance(emissions, MixtureSet):
-        if not isinstance(emissions.modelset, NormalSet):
-            raise NotImplementedError('MixtureSet components must be a NormalSet')
-        return [(emissions, len(emissions), emissions.n_comp_per_mixture)]
+        return [(emissions, len(emissions), emissions.n_leaves_per_mixture)]
     if isinstance(emissions, NormalSet):
         return [(emissions, len(emissions), 1)]
     raise NotImplementedError(f'unsupported emission model {type(emissions).__name__}')
 
 
 def _normalset(group):
-    return group.modelset if isinstance(group, MixtureSet) else group
+    return group.normalset if isinstance(group, MixtureSet) else group
 
 
 def _sub_batches(lengths, bytes_per_frame, max_frames):
@@ -241,7 +239,7 @@ def _like(param, t):
 
 
 def _mixture_batch(model, X, lengths, datasize, labels, max_frames, statics=None):
-    ns = model.modelset
+    ns = model.normalset
     K, cov = len(ns), ns.cov_type
     dev, dtype = X.device, X.dtype
     exp_T = ns.means_precisions.natural_form()
@@ -266,12 +264,26 @@ def _mixture_batch(model, X, lengths, datasize, labels, max_frames, statics=None
     off, off_dev, scales = statics.entry(skey, 'offsets', offsets_and_scales)
     lab_dev = None if labels is None else \
         _hip.on_device(torch.as_tensor(labels)).to(torch.int64).contiguous()
+    if lab_dev is not None and model.nested:
+        # labels name the outer components: M mixtures of their leaves, one-hot state
+        # responsibilities (Mixture._nested_expected_log_likelihood)
+        M = len(model.modelset)
+        lw_sets = model.modelset.leaf_log_weights()
     for run in _sub_batches(lengths, K * X.element_size(), max_frames):
         done = _throttle()
         f0, f1 = int(off[run[0]]), int(off[run[-1] + 1])
         stats = FrameStats(X[f0:f1], cov)
         lab = None if lab_dev is None else lab_dev[f0:f1]
         wide = kernels.wide_mixture_split(stats, K, cov) if lab is None else None
+        seg = off_dev[run[0]:run[-1] + 2] - f0
+        if lab is not None and model.nested:
+            set_norm, resps = kernels.mixtureset_estep(stats, exp_T, lw_sets, M, K // M, cov)
+            onehot = torch.zeros_like(set_norm).scatter_(1, lab.view(-1, 1), 1.)
+            hk.segment_sum(kernels.rowdot(set_norm, onehot), seg, len(run),
+                           out=utt_llh[run[0]:run[-1] + 1])
+            kernels.normal_accumulate(stats, resps, onehot, M, K // M, cov, acc=acc)
+            done.record()
+            continue
         if lab is None and kernels.packed_path_ok(stats, K, cov):
             # responsibilities go to the accumulation already split for its fp16 products
             log_norm, resps = kernels.mixture_estep_packed(stats, exp_T, lw, K, cov)
@@ -280,17 +292,11 @@ def _mixture_batch(model, X, lengths, datasize, labels, max_frames, statics=None
             log_norm, resps = kernels.wide_mixture_estep(stats, exp_T, lw, K, cov, wide)
         else:
             log_norm, resps = kernels.mixtureset_estep(stats, exp_T, lw, 1, K, cov, labels=lab)
-        seg = off_dev[run[0]:run[-1] + 2] - f0
         hk.segment_sum(log_norm.view(-1), seg, len(run), out=utt_llh[run[0]:run[-1] + 1])
         kernels.normal_accumulate(stats, resps, None, K, 1, cov, acc=acc)
         done.record()
     value_terms = (scales * utt_llh).sum()
-    wparam = model.categorical.mean_field_factorization()[0][0]
-    if isinstance(model.categorical, SBCategorical):
-        wacc = -2. * acc[:, -2]
-    else:
-        wacc = kernels.weights_from_acc(acc, 1, K).view(-1)
-    out = {wparam: _like(wparam, wacc), ns.means_precisions: _like(ns.means_precisions, acc)}
+    out = {**model._weights_accumulate(acc), ns.means_precisions: _like(ns.means_precisions, acc)}
     return value_terms, out
 
 
@@ -302,7 +308,7 @@ def _emission_estep(groups, stats, dtype, for_accumulate=False):
     cols, comps = [], []
     for grp, S, G in groups:
         ns = _normalset(grp)
-        lw = grp._log_weights() if isinstance(grp, MixtureSet) else None
+        lw = grp.leaf_log_weights() if isinstance(grp, MixtureSet) else None
         gstats = stats.as_cov(ns.cov_type)
         fused = for_accumulate and G > 1 and \
             kernels.fused_accumulate_ok(gstats, S, G, ns.cov_type)
@@ -457,8 +463,7 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         ns = _normalset(grp)
         out[ns.means_precisions] = _like(ns.means_precisions, acc)
         if isinstance(grp, MixtureSet):
-            wparam = grp.categoricalset.weights
-            out[wparam] = _like(wparam, kernels.weights_from_acc(acc, S, G))
+            out.update(grp.weights_accumulate(acc))
     if isinstance(model, BigramPhoneLoop):
         if bigram and counts_tot is None and xi_tot is not None:       # (Viterbi training)
             counts_tot = model.bigram_counts(xi_tot)
@@ -527,14 +532,15 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
     inference_graph=..., scale=..., viterbi=...)` calls.
 
     Args:
-        model: `Mixture`, `HMM` or `PhoneLoop`.
+        model: `Mixture` (nested ones included), `HMM` or `PhoneLoop`.
         utterances: list of [T_u, D] tensors, or `(X_packed, lengths)`.
         datasize: frames in the whole training set (<= 0: this shard).
         inference_graphs: optional list of per-utterance `CompiledGraph`
             (alignment graphs); None = the model's own graph.
         scale: acoustic scale (HMM only).
         viterbi / state_paths: hard-alignment training branches (HMM only).
-        labels: optional int64 [sum T_u] component labels (Mixture only).
+        labels: optional int64 [sum T_u] component labels (Mixture only; the outer
+            components of a nested one).
         nsamples, llh_weight, kl_weight: `VAE.expected_log_likelihood`
             arguments (VAE only; the batch is one minibatch, its value keeps
             the autograd graph of the networks).

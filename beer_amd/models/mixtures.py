@@ -7,6 +7,12 @@ llh + logsumexp + responsibilities straight from the frames) and `accumulate`
 runs `beer_normal_accumulate` (responsibility-weighted N_k, sum r x,
 sum r xx^T in fp64): two kernel calls replace the reference's
 cat / mul / mm / logsumexp / exp / mm sequence and its [T, Q] tensor.
+
+Nested mixtures (components that are themselves a `MixtureSet`, at any depth) run
+as the flat mixture over their leaves: a leaf's log-weight is the sum of its
+ancestors' E[ln pi], the softmax over all leaves gives the value and the joint
+responsibilities, and every level's weight statistics are sums of the leaf counts
+over its subtrees ("Nested mixtures").  The same kernels run.
 """
 
 import torch
@@ -15,7 +21,7 @@ from .. import kernels
 from .basemodel import DiscreteLatentModel
 from .gaussians import NormalSet
 from .modelset import ModelSet
-from .weights import Categorical, CategoricalSet, SBCategorical
+from .weights import Categorical, CategoricalSet, SBCategorical, SBCategoricalSet
 
 __all__ = ['Mixture', 'MixtureSet']
 
@@ -39,6 +45,33 @@ def _like(param, t):
     return t.to(dtype=ref.dtype, device=ref.device)
 
 
+def _leaves(modelset):
+    'The NormalSet under a (possibly nested) set of mixtures.'
+    while isinstance(modelset, MixtureSet):
+        modelset = modelset.modelset
+    if not isinstance(modelset, NormalSet):
+        raise NotImplementedError('Mixture components must be a NormalSet or a MixtureSet '
+                                  f'of NormalSets, got {type(modelset).__name__}')
+    return modelset
+
+
+def _leaf_counts(acc):
+    'N_k of every leaf [K] (fp64) from accumulated Gaussian statistics [K, Q].'
+    return -2. * acc[:, -2]
+
+
+def _weight_stats(weights, counts):
+    '''{parameter: statistics} of the weights `weights` (one categorical or a set of them)
+    from the counts of their categories ([n] or [rows, n], fp64): the raw counts for
+    stick-breaking weights, the Dirichlet's statistics (last column: the row total) else.'''
+    param = weights.mean_field_factorization()[0][0]
+    if isinstance(weights, (SBCategorical, SBCategoricalSet)):
+        return {param: _like(param, counts)}
+    stats = counts.clone()
+    stats[..., -1] = counts.sum(dim=-1)
+    return {param: _like(param, stats)}
+
+
 class Mixture(DiscreteLatentModel):
     'Bayesian mixture model.'
 
@@ -55,8 +88,23 @@ class Mixture(DiscreteLatentModel):
         super().__init__(modelset)
         self.categorical = categorical
 
+    @property
+    def nested(self):
+        'True when the components are themselves mixtures (a MixtureSet).'
+        return isinstance(self.modelset, MixtureSet)
+
+    @property
+    def normalset(self):
+        'The Gaussians at the leaves: the components, or those of the nested sets.'
+        return _leaves(self.modelset)
+
     def _log_weights(self, tensorconf=None):
-        return self.categorical.log_weights()
+        'E[ln pi] of every component; of every LEAF when nested (the sum over its ancestors).'
+        lw = self.categorical.log_weights()
+        if not self.nested:
+            return lw
+        inner = self.modelset.leaf_log_weights()
+        return (lw.to(inner.dtype)[:, None] + inner).reshape(-1)
 
     def mean_field_factorization(self):
         return _merge_groups(self.modelset.mean_field_factorization(),
@@ -70,7 +118,7 @@ class Mixture(DiscreteLatentModel):
         i.e. logsumexp_k(l_tk + E ln pi_k); with `labels` the log-likelihood
         of the labelled component (mixture.py:70-93).'''
         if not _fused(self.modelset):
-            raise NotImplementedError('Mixture components must be a NormalSet')
+            return self._nested_expected_log_likelihood(stats, labels)
         ns = self.modelset
         K = len(ns)
         if kernels.is_dense(stats):
@@ -114,30 +162,81 @@ class Mixture(DiscreteLatentModel):
         self.cache['resps'] = resps
         return kernels.attach_stats_grad(stats, value, resps, nparams)
 
+    def _nested_expected_log_likelihood(self, stats, labels):
+        '''Components that are mixtures: the flat mixture over the K leaves.  Without labels
+        the value is logsumexp over the leaves of l_tk + (sum of the ancestors' E ln pi),
+        with labels the labelled component's log-normaliser (its own leaves only, the outer
+        weight left out); the cache holds the joint responsibilities over the leaves.  No
+        gradient: the reference's MixtureSet detaches its log-normaliser (mixtureset.py:93).'''
+        ns = self.normalset
+        K, M = len(ns), len(self.modelset)
+        nparams = ns.means_precisions.natural_form()
+        dense = kernels.is_dense(stats)
+        if dense:
+            pc = kernels.dense_llh(stats, nparams, ns.means_precisions.likelihood_fn.dim)
+        if labels is None:
+            lw = self._log_weights().view(1, K)
+            if dense:
+                log_norm, resps = kernels.dense_softmax(pc, lw, 1, K)
+            else:
+                wide = kernels.wide_mixture_split(stats, K, ns.cov_type)
+                if wide:
+                    log_norm, resps = kernels.wide_mixture_estep(stats, nparams, lw, K,
+                                                                 ns.cov_type, wide)
+                else:
+                    log_norm, resps = kernels.mixtureset_estep(stats, nparams, lw, 1, K,
+                                                               ns.cov_type)
+            self.cache['resps'], self.cache['state_resps'] = resps, None
+            return log_norm.view(-1).detach()
+        # the M outer components as M mixtures of their leaves
+        lw = self.modelset.leaf_log_weights()
+        if dense:
+            log_norm, resps = kernels.dense_softmax(pc, lw, M, K // M)
+        else:
+            log_norm, resps = kernels.mixtureset_estep(stats, nparams, lw, M, K // M,
+                                                       ns.cov_type)
+        lab = torch.as_tensor(labels).to(device=log_norm.device, dtype=torch.int64).view(-1, 1)
+        onehot = torch.zeros_like(log_norm).scatter_(1, lab, 1.)
+        self.cache['resps'], self.cache['state_resps'] = resps, onehot
+        return kernels.rowdot(log_norm, onehot)
+
+    def _weights_accumulate(self, acc):
+        '{weights parameter: statistics} of every level from the Gaussian statistics [K, Q].'
+        K = acc.shape[0]
+        if not self.nested:
+            wparam = self.categorical.mean_field_factorization()[0][0]
+            if isinstance(self.categorical, SBCategorical):
+                # stick-breaking weights take the raw counts N_k (categorical.py:149-151)
+                wacc = -2. * acc[:, -2]
+            else:
+                wacc = kernels.weights_from_acc(acc, 1, K).view(-1)
+            return {wparam: _like(wparam, wacc)}
+        counts = _leaf_counts(acc).view(len(self.modelset), -1)
+        return {**_weight_stats(self.categorical, counts.sum(dim=-1)),
+                **self.modelset.leaf_weights_accumulate(counts)}
+
     def accumulate(self, stats):
-        ns = self.modelset
+        ns = self.normalset
         K = len(ns)
+        sr = self.cache.get('state_resps')
+        S, G = (K, 1) if sr is None else (sr.shape[1], K // sr.shape[1])
         if kernels.is_dense(stats):
-            acc = kernels.dense_accumulate(stats, self.cache['resps'], None, K, 1)
+            acc = kernels.dense_accumulate(stats, self.cache['resps'], sr, S, G)
         else:
-            acc = kernels.normal_accumulate(stats, self.cache['resps'], None, K, 1,
-                                            ns.cov_type)
-        wparam = self.categorical.mean_field_factorization()[0][0]
-        if isinstance(self.categorical, SBCategorical):
-            # stick-breaking weights take the raw counts N_k (categorical.py:149-151)
-            wacc = -2. * acc[:, -2]
-        else:
-            wacc = kernels.weights_from_acc(acc, 1, K).view(-1)
-        return {wparam: _like(wparam, wacc),
+            acc = kernels.normal_accumulate(stats, self.cache['resps'], sr, S, G, ns.cov_type)
+        return {**self._weights_accumulate(acc),
                 ns.means_precisions: _like(ns.means_precisions, acc)}
 
     def posteriors(self, data):
+        'Responsibilities of the components [T, K]; nested: the leaves\' summed per component.'
         stats = self.sufficient_statistics(data)
-        ns = self.modelset
+        ns = self.normalset
         K = len(ns)
         _, resps = kernels.mixtureset_estep(
             stats, ns.means_precisions.natural_form(), self._log_weights().view(1, K),
             1, K, ns.cov_type)
+        if self.nested:
+            resps = resps.view(len(resps), len(self.modelset), -1).sum(dim=-1)
         return resps
 
 
@@ -159,8 +258,52 @@ class MixtureSet(ModelSet):
     def n_comp_per_mixture(self):
         return len(self.modelset) // len(self)
 
+    @property
+    def nested(self):
+        'True when the components are themselves mixtures (a MixtureSet).'
+        return isinstance(self.modelset, MixtureSet)
+
+    @property
+    def normalset(self):
+        'The Gaussians at the leaves: the components, or those of the nested sets.'
+        return _leaves(self.modelset)
+
+    @property
+    def n_leaves_per_mixture(self):
+        'Gaussians under every mixture of the set (`n_comp_per_mixture` when not nested).'
+        return len(self.normalset) // len(self)
+
     def _log_weights(self, tensorconf=None):
         return self.categoricalset.log_weights()
+
+    def leaf_log_weights(self):
+        '''E[ln pi] of every leaf Gaussian of every mixture [S, L]: the sum of the E[ln pi]
+        of the leaf and of its ancestors inside this set.'''
+        lw = self._log_weights()
+        if not self.nested:
+            return lw
+        inner = self.modelset.leaf_log_weights()
+        S, M = lw.shape
+        return (lw.to(inner.dtype)[:, :, None] + inner.view(S, M, -1)).reshape(S, -1)
+
+    def leaf_weights_accumulate(self, counts):
+        '''{weights parameter: statistics} of this set and of the sets under it from the
+        counts of the leaves [S, L] (fp64): a level's counts are the leaf counts summed
+        over the subtrees of its categories.'''
+        per = counts.reshape(len(self), self.n_comp_per_mixture, -1)
+        out = _weight_stats(self.categoricalset, per.sum(dim=-1))
+        if self.nested:
+            out.update(self.modelset.leaf_weights_accumulate(per.reshape(-1, per.shape[-1])))
+        return out
+
+    def weights_accumulate(self, acc):
+        '''{weights parameter: statistics} of every level from the leaves' Gaussian
+        statistics [S * L, Q].'''
+        if not self.nested and isinstance(self.categoricalset, CategoricalSet):
+            wparam = self.categoricalset.weights
+            S, G = len(self), self.n_comp_per_mixture
+            return {wparam: _like(wparam, kernels.weights_from_acc(acc, S, G))}
+        return self.leaf_weights_accumulate(_leaf_counts(acc).view(len(self), -1))
 
     def mean_field_factorization(self):
         return _merge_groups(self.modelset.mean_field_factorization(),
@@ -170,40 +313,38 @@ class MixtureSet(ModelSet):
         return self.modelset.sufficient_statistics(data)
 
     def expected_log_likelihood(self, stats):
-        'Per-state mixture log-normaliser [T, S]; caches the component resps.'
-        if not _fused(self.modelset):
-            raise NotImplementedError('MixtureSet components must be a NormalSet')
-        ns = self.modelset
-        S, G = len(self), self.n_comp_per_mixture
+        '''Per-state mixture log-normaliser [T, S]; caches the component resps (the
+        joint responsibilities of the leaves when nested).'''
+        ns = self.normalset
+        S, G = len(self), self.n_leaves_per_mixture
         if kernels.is_dense(stats):
             # statistics-in: no gradient, the log-normaliser is detached
             # (mixtureset.py:93)
             fn = ns.means_precisions.likelihood_fn
             pc = kernels.dense_llh(stats, ns.means_precisions.natural_form(), fn.dim)
-            log_norm, resps = kernels.dense_softmax(pc, self._log_weights(), S, G)
+            log_norm, resps = kernels.dense_softmax(pc, self.leaf_log_weights(), S, G)
         else:
             log_norm, resps = kernels.mixtureset_estep(
-                stats, ns.means_precisions.natural_form(), self._log_weights(), S, G,
+                stats, ns.means_precisions.natural_form(), self.leaf_log_weights(), S, G,
                 ns.cov_type)
         self.cache['resps'] = resps.view(-1, S, G)
         return log_norm
 
     def accumulate(self, stats, resps):
         'Joint (state x component) responsibilities -> weights + Gaussian stats.'
-        ns = self.modelset
-        S, G = len(self), self.n_comp_per_mixture
+        ns = self.normalset
+        S, G = len(self), self.n_leaves_per_mixture
         comp = self.cache['resps'].reshape(-1, S * G)
         if kernels.is_dense(stats):
             acc = kernels.dense_accumulate(stats, comp, resps, S, G)
         else:
             acc = kernels.normal_accumulate(stats, comp, resps, S, G, ns.cov_type)
-        wacc = kernels.weights_from_acc(acc, S, G)
-        wparam = self.categoricalset.weights
-        return {wparam: _like(wparam, wacc),
+        return {**self.weights_accumulate(acc),
                 ns.means_precisions: _like(ns.means_precisions, acc)}
 
     def __len__(self):
-        return len(self.categoricalset)
+        cset = self.categoricalset
+        return cset.n_components if isinstance(cset, SBCategoricalSet) else len(cset)
 
     def __getitem__(self, key):
         ncpm = self.n_comp_per_mixture
