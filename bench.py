@@ -2,32 +2,39 @@
 """Headline benchmark: frames/sec per VB iteration (E-step + all-reduce + M-step).
 
     python bench.py --gpus N --steps K --warmup W            # the driver's line
+    python bench.py --gpus N --steps K --warmup W --full     # + everything else (below)
     python bench.py --gpus N --config 3 [--cov full] [--frames 10000000]   # config 3 alone
     python bench.py ... --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
 
 The default line is BASELINE config 2 (`configs[1]`, the configuration the metric is
 quoted on): GMM, K = 256 full-covariance Gaussians, D = 40, 1,000,000 fp32 frames PER
 GPU in 8192-frame "utterances" (weak scaling; `--scaling strong` shards 1 M frames over
-the ranks instead).  It carries two sub-objects for BASELINE config 3 (`configs[2]`),
-measured by the same process(es) right after: `config3` -- monophone phone-loop HMM, 40
-phones x 3 states x 16 diagonal Gaussians, D = 40, a FIXED corpus of 10 M frames in ~33 k
-utterances sharded over the ranks by frame count (strong scaling), forward-backward + VB
-update -- and `config3_full`, the same model with full covariances on 2 M frames
-(`--no-config3` skips both).
+the ranks instead).
+
+A plain run does only what its headline needs: set-up, `--warmup` steps, the `--steps` timed
+steps (kernel and phase times read from the HIP events of those steps), `--dump-outputs` and
+the line.  `--full` adds what is measured or checked beside them: the fp64 oracle check of the
+timed kernels, the `f32_exact` leg, the clock probe, the captured variant, the CPU baselines
+and the other configurations.  With `--full` the default line carries two sub-objects for
+BASELINE config 3 (`configs[2]`), measured by the same process(es) right after: `config3` --
+monophone phone-loop HMM, 40 phones x 3 states x 16 diagonal Gaussians, D = 40, a FIXED
+corpus of 10 M frames in ~33 k utterances sharded over the ranks by frame count (strong
+scaling), forward-backward + VB update -- and `config3_full`, the same model with full
+covariances on 2 M frames (`--no-config3` skips both), then configs 4, 1 and 5 (one process).
 
 float32 models multiply on the bf16 matrix pipes with every operand held exactly as three
 bf16 pieces and six partial products per multiplication (fp32 accumulation): operands and
-accumulation are float32's own -- `value` is on that arithmetic; `f32_exact` repeats the
-iteration on the exact fp32 MFMA.
+accumulation are float32's own -- `value` is on that arithmetic; `f32_exact` (`--full`) repeats
+the iteration on the exact fp32 MFMA.
 
 One process per GPU, ONE RCCL all-reduce of the accumulated statistics per
 iteration, replicated M-step.  With --gpus N > 1 and no launcher in the
 environment (no WORLD_SIZE) the script spawns its own N ranks; under
 `python -m torch.distributed.run` it takes RANK / LOCAL_RANK / WORLD_SIZE from
 the environment.  Rank 0 prints ONE compact JSON line on stdout (benchlib/format.py: the
-contract's keys, the headline's roofline and cpu_baseline, a `summary` of the other
-configurations; < 4 KB); the full objects -- per-kernel tables, the other configurations' own
-rooflines and baselines -- go to bench_detail.json and to stderr.
+contract's keys, the headline's roofline and, with `--full`, its cpu_baseline and a `summary`
+of the other configurations; < 4 KB); the full objects -- per-kernel tables, the other
+configurations' own rooflines and baselines -- go to bench_detail.json and to stderr.
 """
 
 import argparse
@@ -295,11 +302,6 @@ def run_gmm(args, rank, world, device, backend, dump_dir=None):
                    'parallelism': f'dp{world}', 'frames_per_gpu': frames,
                    'components': K, 'dim': D},
         **census,
-        'elbo_rel_err_vs_cpu_fp64': elbo_err, 'stats_rel_err_vs_cpu_fp64': stats_err,
-        'parity_vs_cpu_fp64': parity,
-        'parity_check': 'first 65536 frames through the timed kernels (packed hand-over) vs the '
-                        'fp64 numpy oracle, in both float32 arithmetics; statistics per block '
-                        '(counts / first / second moments against their own largest entry)',
         'elbo_per_frame': float(elbo) / (len(lengths) * world * datasize),
         'f32_mode': mode,
         'f32_arithmetic': 'bf16x3: every fp32 operand exactly as three bf16 pieces, six partial '
@@ -314,6 +316,14 @@ def run_gmm(args, rank, world, device, backend, dump_dir=None):
         'kernels': kern,
     }
     out['roofline'].update(profiled(pmc_key, out['roofline']))
+    if parity:
+        out.update({
+            'elbo_rel_err_vs_cpu_fp64': elbo_err, 'stats_rel_err_vs_cpu_fp64': stats_err,
+            'parity_vs_cpu_fp64': parity,
+            'parity_check': 'first 65536 frames through the timed kernels (packed hand-over) vs '
+                            'the fp64 numpy oracle, in both float32 arithmetics; statistics per '
+                            'block (counts / first / second moments against their own largest '
+                            'entry)'})
     if exact:
         out['f32_exact'] = exact
     if world == 1 and not args.no_extras:
@@ -568,7 +578,7 @@ def run_hmm(args, rank, world, device, backend, cov=None, total_frames=None, ste
         out['shard']['captured_mode'] = it.mode
     if with_cpu_baseline and not args.no_cpu_baseline and world == 1 and cov == 'diagonal':
         out['cpu_baseline'] = cpu_baseline_hmm()
-    fi = frame_image_report(images)
+    fi = frame_image_report(images) if args.full else None      # (a build timed on its own)
     if fi:
         out['frame_image'] = fi
     return out
@@ -1059,7 +1069,7 @@ def _spawned(rank, args, port):
     worker(args)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -1073,34 +1083,50 @@ def main():
     ap.add_argument('--cov', default='diagonal', help='config 3: covariance type of the emissions')
     ap.add_argument('--max-frames', type=int, default=1 << 24,
                     help='config 3: frames per launch of the batched E-step')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-exact', action='store_true', help='config 2: skip the f32_exact leg')
-    ap.add_argument('--no-check', action='store_true', help='config 2: skip the oracle check')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline\'s timed steps: the oracle check, the '
+                         'f32_exact leg, the clock probe, the captured variant, the CPU baselines '
+                         'and the other configurations (the --no-* options below pick from these)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+    ap.add_argument('--no-exact', action='store_true', help='--full, config 2: skip the f32_exact leg')
+    ap.add_argument('--no-check', action='store_true', help='--full, config 2: skip the oracle check')
     ap.add_argument('--no-mstep-graph', action='store_true',
                     help='launch the M-step kernel by kernel instead of replaying its captured HIP graph')
     ap.add_argument('--no-extras', action='store_true',
-                    help='profiling runs: no clock probe, no captured variant (their launches carry '
-                         'the names of the timed ones)')
+                    help='--full, profiling runs: no clock probe, no captured variant (their launches '
+                         'carry the names of the timed ones)')
     ap.add_argument('--no-config3', action='store_true',
-                    help='default line: skip the config3 / config3_full sub-objects')
+                    help='--full: skip the config3 / config3_full sub-objects')
     ap.add_argument('--no-config4', action='store_true',
-                    help='default line: skip the config4 sub-object (HMM-VAE, one process)')
+                    help='--full: skip the config4 sub-object (HMM-VAE, one process)')
     ap.add_argument('--no-config1', action='store_true',
-                    help='default line: skip the config1 sub-object (latency of one small iteration)')
+                    help='--full: skip the config1 sub-object (latency of one small iteration)')
     ap.add_argument('--no-config5', action='store_true',
-                    help='default line: skip the config5 sub-object (recipe end to end)')
+                    help='--full: skip the config5 sub-object (recipe end to end)')
     ap.add_argument('--config5-only', action='store_true',
-                    help='print the config5 sub-object alone')
+                    help='with --full: print the config5 sub-object alone')
     ap.add_argument('--config4-only', action='store_true',
-                    help='print the config4 sub-object alone (no config 2 / 3 runs)')
+                    help='with --full: print the config4 sub-object alone (no config 2 / 3 runs)')
     ap.add_argument('--scaling', default='weak', choices=('weak', 'strong'),
                     help='config 2: 1 M frames per GPU (weak, default) or --frames in total (strong)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps of the headline (config 2, or 3 with --config 3), '
                          'write the ELBO and the posteriors of its last step as DIR/<name>.npy')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.frames is None:
         args.frames = 1_000_000 if args.config == 2 else 10_000_000
+    if not args.full:
+        if args.config4_only or args.config5_only:
+            ap.error('--config4-only / --config5-only measure other configurations: add --full')
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line -- nothing
+        # measured or checked beside them
+        args.no_check = args.no_exact = args.no_extras = args.no_cpu_baseline = True
+        args.no_config3 = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher: spawn the ranks ourselves (one process per GPU, loopback rendezvous)
         import torch.multiprocessing as mp

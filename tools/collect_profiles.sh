@@ -7,9 +7,9 @@ set -e
 cd "$(dirname "$0")/.."
 R=${1:-r06}; O=${2:-gpurun_out/r6prof}
 rm -f profiles/${R}_pmc.json
-C2="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config3 --no-extras"
-C3="python bench.py --config 3 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
-C3F="python bench.py --config 3 --cov full --frames 2000000 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+C2="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config3 --no-extras"
+C3="python bench.py --full --config 3 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+C3F="python bench.py --full --config 3 --cov full --frames 2000000 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
 python tools/pmc_summary.py $R "--command=$C2" --skip=5/25 $O/c2_pmc1 $O/c2_pmc2 $O/c2_pmc3
 python tools/pmc_summary.py $R "--command=$C3" --tag=c3 --skip=2/8 $O/c3_pmc1 $O/c3_pmc2 $O/c3_pmc3
 python tools/pmc_summary.py $R "--command=$C3F" --tag=c3full --skip=2/8 $O/c3full_pmc1 $O/c3full_pmc2 $O/c3full_pmc3

@@ -7,9 +7,9 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r5prof; rm -rf $O; mkdir -p $O
 T="timeout 420"
-C2="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config3"
-C3="python bench.py --config 3 --steps 6 --warmup 2 --no-cpu-baseline"
-C3F="python bench.py --config 3 --cov full --frames 2000000 --steps 6 --warmup 2 --no-cpu-baseline"
+C2="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config3"
+C3="python bench.py --full --config 3 --steps 6 --warmup 2 --no-cpu-baseline"
+C3F="python bench.py --full --config 3 --cov full --frames 2000000 --steps 6 --warmup 2 --no-cpu-baseline"
 C4="python tools/probes/c4_prior_path.py full 5"
 C4D="python tools/probes/c4_prior_path.py diagonal 5"
 P1="SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
@@ -32,20 +32,20 @@ run c3 6 2 "$C3" c3
 run c3full 6 2 "$C3F" c3full
 run c4 5 2 "$C4" c4
 run c4d 5 2 "$C4D" c4d
-$T rocprofv3 --kernel-trace --stats -f csv -d $O/c5_stats -- python bench.py --config5-only --no-cpu-baseline > $O/c5_stats.log 2>&1
+$T rocprofv3 --kernel-trace --stats -f csv -d $O/c5_stats -- python bench.py --full --config5-only --no-cpu-baseline > $O/c5_stats.log 2>&1
 find $O/c5_stats -name '*kernel_trace.csv' -delete
-$T rocprofv3 --kernel-trace --stats -f csv -d $O/c4bench_stats -- python bench.py --config4-only --no-cpu-baseline > $O/c4bench_stats.log 2>&1
+$T rocprofv3 --kernel-trace --stats -f csv -d $O/c4bench_stats -- python bench.py --full --config4-only --no-cpu-baseline > $O/c4bench_stats.log 2>&1
 find $O/c4bench_stats -name '*kernel_trace.csv' -delete
 du -sh $O
 bash tools/collect_profiles.sh r05 gpurun_out/r5prof --profiles-only > $O/collect.log 2>&1
 # the lines: the driver's (prices frac_profiled / traffic on profiles/r05_kernel_times.json and
 # r05_pmc.json, which the collector call above has just written from THIS box's passes), and the
 # workloads alone
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2>>$O/err.log
-$T python bench.py --config 3 --steps 6 --warmup 2 > $O/bench_c3.json 2>>$O/err.log
-$T python bench.py --config 3 --cov full --frames 2000000 --no-cpu-baseline --steps 6 --warmup 2 > $O/bench_c3full.json 2>>$O/err.log
-$T python bench.py --config4-only > $O/bench_c4.json 2>>$O/err.log
-$T python bench.py --config5-only > $O/bench_c5.json 2>>$O/err.log
-BEER_BENCH_BACKEND=gloo $T python bench.py --gpus 2 --no-cpu-baseline --steps 5 --warmup 2 --no-config3 2>>$O/err.log | grep '^{' > $O/bench_g2_gloo.json
-BEER_BENCH_BACKEND=gloo $T python bench.py --gpus 8 --config 3 --no-cpu-baseline --steps 3 --warmup 2 2>>$O/err.log | grep '^{' > $O/bench_g8_gloo_config3.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2>>$O/err.log
+$T python bench.py --full --config 3 --steps 6 --warmup 2 > $O/bench_c3.json 2>>$O/err.log
+$T python bench.py --full --config 3 --cov full --frames 2000000 --no-cpu-baseline --steps 6 --warmup 2 > $O/bench_c3full.json 2>>$O/err.log
+$T python bench.py --full --config4-only > $O/bench_c4.json 2>>$O/err.log
+$T python bench.py --full --config5-only > $O/bench_c5.json 2>>$O/err.log
+BEER_BENCH_BACKEND=gloo $T python bench.py --full --gpus 2 --no-cpu-baseline --steps 5 --warmup 2 --no-config3 2>>$O/err.log | grep '^{' > $O/bench_g2_gloo.json
+BEER_BENCH_BACKEND=gloo $T python bench.py --full --gpus 8 --config 3 --no-cpu-baseline --steps 3 --warmup 2 2>>$O/err.log | grep '^{' > $O/bench_g8_gloo_config3.json
 tail -c 900 $O/bench.json; tail -5 $O/err.log

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=$1; shift
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-CMD=${BENCH_CMD:-"python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-exact --no-check"}
+CMD=${BENCH_CMD:-"python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-exact --no-check"}
 i=0
 for P in "$@"; do
   i=$((i+1))

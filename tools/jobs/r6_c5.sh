@@ -1,8 +1,8 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r6c5; rm -rf $O; mkdir -p $O
-timeout 600 python bench.py --config5-only > $O/c5.json 2> $O/c5.err; echo rc $?
-timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --config5-only --no-cpu-baseline > $O/stats.log 2>&1
+timeout 600 python bench.py --full --config5-only > $O/c5.json 2> $O/c5.err; echo rc $?
+timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $O/stats -- python bench.py --full --config5-only --no-cpu-baseline > $O/stats.log 2>&1
 find $O/stats -name '*kernel_trace.csv' -delete
 python - <<'P'
 import json,glob,csv

@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r6l2; rm -rf $O; mkdir -p $O
-C3="env BEER_ACCFI_PERSIST=1 python bench.py --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+C3="env BEER_ACCFI_PERSIST=1 python bench.py --full --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
 timeout 600 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum -f csv -d $O/p1 -- $C3 > $O/p1.log 2>&1
 python - <<'P'
 import csv,glob,collections

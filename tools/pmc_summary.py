@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Summarise rocprofv3 PMC passes of `bench.py` into profiles/<round>_pmc.json.
 
-    python tools/pmc_summary.py r02 [--command='python bench.py ...'] [--tag=c3] \
+    python tools/pmc_summary.py r02 [--command='python bench.py --full ...'] [--tag=c3] \
         gpurun_out/pmc_a gpurun_out/pmc_b gpurun_out/pmc_c
 
 Each directory holds one `rocprofv3 --kernel-trace --pmc ...` pass.  Only the
@@ -35,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     rnd, dirs = sys.argv[1], sys.argv[2:]
-    command = 'python bench.py --steps 3 --warmup 1 --no-cpu-baseline'
+    command = 'python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline'
     if dirs and dirs[0].startswith('--command='):
         command, dirs = dirs[0][len('--command='):], dirs[1:]
     tag = ''

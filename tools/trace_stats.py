@@ -3,7 +3,7 @@
 launches, for the kernels the rooflines are priced on.
 
     python tools/trace_stats.py <trace dir> <out.csv> <profiles/rNN_kernel_times.json> \
-        --tag=c3 --steps=6 --warmup=2 "--command=python bench.py ..."
+        --tag=c3 --steps=6 --warmup=2 "--command=python bench.py --full ..."
 
 Of every kernel (by name) the FULL-SIZE launches are kept (duration above half of the longest:
 a parity check on a slice of the frames is not a launch of the workload), then the first
