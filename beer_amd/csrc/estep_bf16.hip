@@ -138,7 +138,7 @@ constexpr int kImgMaxNK = 4;
 __host__ __device__ inline int stat_slab(int j) { return j + j / 7; }
 // k-steps (8 slabs each), padded to an even count: the K1 loop is unrolled by two
 __host__ __device__ inline int nk16_of(int cov, int D) {
-    return ((nslab_of(cov, D) + 7) / 8 + 1) / 2 * 2;
+    return ((nslabx_of(cov, D) + 7) / 8 + 1) / 2 * 2;
 }
 // Row stride (floats) of K1's LDS frame tile: the D values, the constants 1 and
 // 2^-24 and at least 6 zeros (the padding slabs read them), with stride / 4 odd --
@@ -157,12 +157,29 @@ constexpr float kConstEps = 5.9604644775390625e-8f;      // 2^-24
 constexpr int kBlockU4 = NP * 64;      // u4 per (k-step, tile) block of the P image: 3 KiB
 
 // Value of contraction entry (slab, e) for component k (the logic of pack_kernel in
-// estep_mfma.hip); the constant slabs are filled by the caller (const_share).
+// estep_mfma.hip; full covariance in the band layout, estep_tiles.h); the constant slabs
+// are filled by the caller (const_share).
 __device__ inline double entry_value(int cov, int D, int K, int k, int slab, int e,
                                      const float* __restrict__ row, bool* is_const) {
-    const int D4 = d4_of(D), Dp = 4 * D4, nslab = nslab_of(cov, D);
+    const int D4 = d4_of(D), Dp = 4 * D4, nslab = nslabx_of(cov, D);
     *is_const = false;
     if (slab >= nslab) return 0.0;
+    if (band_layout(cov, D)) {
+        const int nb = band_nslab(D);
+        if (slab == nslab - 1) {
+            *is_const = true;
+            return 0.0;
+        }
+        if (k >= K) return 0.0;
+        if (slab >= nb) {
+            const int b = 4 * (slab - nb) + e;
+            return b < D ? (double)row[b] : 0.0;
+        }
+        int a, b;
+        if (!band_pair(D, slab, e, &a, &b)) return 0.0;
+        return b == a ? -0.5 * (double)row[D + a * D + a]
+                      : -0.5 * ((double)row[D + a * D + b] + (double)row[D + b * D + a]);
+    }
     const int t = slab_entry(cov, D, slab);
     const int a = t & 0xff, b = ((t >> 8) & 0xff) + e, sq = t >> 16;
     if (a == Dp && b - e == Dp) {
@@ -221,12 +238,8 @@ __global__ __launch_bounds__(256) void packx_kernel(int cov, int D, int K, int N
     // consecutive slots per lane -- see lognorm_epilogue_lane_major
     const int c = lane_major ? kk % NT : 4 * (kk / 64) + (kk % 4);
     const int i = lane_major ? kk / NT : (kk % 64) / 4;
-    if (slot == 0)
-        for (int s = threadIdx.x; s < (nk + 1) * 8; s += blockDim.x) {
-            // padding slabs read the zero columns behind the constants of a frame row
-            const int Dp = 4 * d4_of(D);
-            tab[s] = s < nslab_of(cov, D) ? slab_entry(cov, D, s) : ((Dp + 2) | ((Dp + 4) << 8));
-        }
+    if (slot == 0)    // (padding slabs read the zero columns behind the constants of a frame row)
+        for (int s = threadIdx.x; s < (nk + 1) * 8; s += blockDim.x) tab[s] = slabx_entry(cov, D, s);
     // the component's expected statistics, staged once (the entries are gathered from
     // all over the row: from global memory every gather was a dependent L2 round trip)
     const int Qs = stats_dim(cov, D);
@@ -244,7 +257,7 @@ __global__ __launch_bounds__(256) void packx_kernel(int cov, int D, int K, int N
         dst[512] = p[1];
         dst[1024] = p[2];
     };
-    const int nslab = nslab_of(cov, D);
+    const int nslab = nslabx_of(cov, D);
     for (int q = threadIdx.x; q < nent; q += blockDim.x) {
         bool is_const;
         const double v = entry_value(cov, D, K, k, q / 4, q % 4, rowl, &is_const);
@@ -375,6 +388,7 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
     static_assert(!BL || (NT == 16 && MT == 2 && !IMG), "half k-steps of 8 tiles, hipcc-scheduled form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int LD = ld16_of(D);                                // 16-byte aligned rows
+    const int Dp = 4 * d4_of(D);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
@@ -446,13 +460,19 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
     // three-way split -> words 2h, 2h+1 of every piece
     auto make_half = [&](int s, int m, int h, AFrag& f) {
         const int t = tl[8 * s + h];
-        const int a = t & 0xff, j = (t >> 8) & 0xff;
-        const bool sq = SQ && (t >> 16) != 0;
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(xrow[m] + j);
-        const float xx = xrow[m][a];
         f32x4 p;
+        if constexpr (SQ) {
+            const int a = t & 0xff, j = (t >> 8) & 0xff;
+            const bool sq = (t >> 16) != 0;
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(xrow[m] + j);
+            const float xx = xrow[m][a];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) p[e] = bb[e] * (sq ? bb[e] : xx);     // v_cndmask, no branch
+            for (int e = 0; e < 4; ++e) p[e] = bb[e] * (sq ? bb[e] : xx);     // v_cndmask, no branch
+        } else {
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(xrow[m] + (t & 0xff));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) p[e] = bb[e] * xrow[m][band_col(t, e, Dp)];
+        }
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             unsigned w3[3];
@@ -512,7 +532,7 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
             const int hm = bi % MT, hh = bi / MT;             // the half built in this batch
             const int64_t blk = (int64_t)s * NT + (bi + 1) * BT;
             int t = 0;
-            f32x4 bb = {0.f, 0.f, 0.f, 0.f}, p = {0.f, 0.f, 0.f, 0.f};
+            f32x4 bb = {0.f, 0.f, 0.f, 0.f}, p = {0.f, 0.f, 0.f, 0.f}, yy = {0.f, 0.f, 0.f, 0.f};
             float xx = 0.f;
             Split3Steps st[2];
 #pragma unroll
@@ -532,11 +552,13 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
                 } else if (n == 8) {
                     t = tl[8 * (s + 1) + hh];                 // (the table is padded by one k-step)
                 } else if (n == 12) {
-                    bb = *reinterpret_cast<const f32x4*>(xrow[hm] + ((t >> 8) & 0xff));
-                    xx = xrow[hm][t & 0xff];
+                    bb = *reinterpret_cast<const f32x4*>(xrow[hm] + (SQ ? (t >> 8) & 0xff : t & 0xff));
+                    if (SQ) xx = xrow[hm][t & 0xff];
+                } else if (!SQ && n >= 13 && n < 17) {
+                    yy[n - 13] = xrow[hm][band_col(t, n - 13, Dp)];
                 } else if (n >= 18 && n < 22) {
                     const bool sq = SQ && (t >> 16) != 0;
-                    float v = bb[n - 18] * (sq ? bb[n - 18] : xx);
+                    float v = bb[n - 18] * (SQ ? (sq ? bb[n - 18] : xx) : yy[n - 18]);
                     pin(v);
                     p[n - 18] = v;
                 } else if (n >= 22 && n < 29) {
@@ -692,7 +714,7 @@ int launch_llhx(int64_t nframes, int D, int K, int S, int G, int gl, int jw, int
                 int xt_floats = 0, const void* img = nullptr) {
     const int LD = ld16_of(D);
     // k-steps that hold slabs: the slab count is the table's (full: SQ = false)
-    const int nku = (nslab_of(SQ ? g_cov_of_launch : BEER_FULL, D) + 7) / 8;
+    const int nku = (nslabx_of(SQ ? g_cov_of_launch : BEER_FULL, D) + 7) / 8;
     constexpr int FB = 16 * MT * (kThreads / 64);
     size_t lds = (size_t)FB * LD * sizeof(float) + (size_t)(nk + 1) * 8 * sizeof(int);
     if (BL) lds = ((lds + 1023) & ~(size_t)1023) + 2 * (size_t)(8 * kBlockU4 * 16);
@@ -718,9 +740,9 @@ int launch_llhx(int64_t nframes, int D, int K, int S, int G, int gl, int jw, int
 // xt_image_kernel transposed it -- copied global -> LDS by the DMA path
 // (global_load_lds_dwordx4: the images are lane-linear by construction), tile t + 1
 // in flight while tile t is multiplied, one barrier per tile.
-// Workgroup = 4 waves, one per SIMD; a wave owns 128 components x 8 statistic
-// tiles (256 accumulators): A fragments = three ds_read_b128 per component tile,
-// loaded once per k-step and reused by the 8 statistic tiles; B fragments =
+// Workgroup = 4 waves, one per SIMD; a wave owns 128 components x NQ (6 .. 8) statistic
+// tiles (32 NQ accumulators): A fragments = three ds_read_b128 per component tile,
+// loaded once per k-step and reused by the NQ statistic tiles; B fragments =
 // products of two X^T rows over the lane's 8 frames, split on the fly, reused by
 // the 8 component tiles.  A workgroup sums at most BEER_OPT_AX_MAXFRAMES frames in fp32 --
 // one rounding per 32-frame MFMA -- and adds its partial sums to the fp64 image
@@ -748,7 +770,7 @@ constexpr int kAxXS = kAxFT + 4;      // X^T row stride (floats), 16-byte aligne
 // chain at K = 256).
 // (the chain length: BEER_OPT_AX_MAXFRAMES, default beer::kAxMaxFramesDefault = 4096)
 constexpr int kPiece = 4096;          // granule of the X^T image (bytes)
-constexpr int kAxMC = 8, kAxNQ = 8, kAxWaves = 4;
+constexpr int kAxMC = 8, kAxWaves = 4;
 
 inline int xt_rows(int D) { return D + 2; }                              // + ones, zeros
 inline int xt_pieces(int D) { return (xt_rows(D) * kAxXS * 4 + kPiece - 1) / kPiece; }
@@ -777,13 +799,14 @@ __global__ __launch_bounds__(256) void xt_image_kernel(int64_t nframes, int D, i
     }
 }
 
-template <bool SR>
+// NQ (statistic tiles per wave, 6 .. 8): accx_nq().
+template <bool SR, int NQ>
 __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
     int64_t nframes, int D, int K, int nslab, int NX, const float* __restrict__ Xt,
     const unsigned* __restrict__ Rimg, const int* __restrict__ tab,
     int64_t frames_per_block, double* __restrict__ Sp, int gx, int gy, int gz,
-    const float* __restrict__ Gt, int lgG, int sx) {
-    constexpr int MC = kAxMC, NQ = kAxNQ, WAVES = kAxWaves, NB = 2;
+    const float* __restrict__ Gt, int lgG, int sx, int band) {
+    constexpr int MC = kAxMC, WAVES = kAxWaves, NB = 2;
     static_assert(16 * MC == kPackedComps && kAxFT == kPackedFrames, "the packed image is this kernel's LDS tile");
     constexpr int plane = kPackedPlaneWords * 4;                  // bytes of one piece plane
     // NX = 4 KiB pieces of the transposed frame tile (1 .. 9: D <= 128).  Two buffers of
@@ -820,13 +843,19 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
     const int gbytes = SR ? ((16 * MC) >> lgG) * kAxFT * 4 : 0;   // gamma^T of one block-tile
     const int gkb = (gbytes + 1023) >> 10;
 
+    // (band: the table of the band layout, estep_tiles.h: band_entry)
     auto factors = [&](int uu, int& a, int& b) {
         const int col = 16 * (tile0 + uu) + i, slab = col >> 2;
         a = b = Dp + 2;
         if (slab < nslab) {
             const int t = tab[slab];
-            b = ((t >> 8) & 0xff) + (col & 3);
-            a = (t >> 16) ? b : (t & 0xff);
+            if (band) {
+                a = (t & 0xff) + (col & 3);
+                b = band_col(t, col & 3, Dp);
+            } else {
+                b = ((t >> 8) & 0xff) + (col & 3);
+                a = (t >> 16) ? b : (t & 0xff);
+            }
         }
     };
     // byte offsets of the lane's 8 frames (k-step 0) in the two X^T rows of its
@@ -986,7 +1015,10 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
                 if (BEER_K2_ABL < 2 || (tile == 0 && ks == 0)) load_a(buf, ks);
 #pragma unroll
                 for (int uu = 0; uu < NQ; ++uu) {
-                    const int cur = uu & 1;
+                    // (the two B buffers alternate along the tile's 2 NQ steps, which
+                    // makes the parity right for an odd NQ too: the last step, 2 NQ - 1,
+                    // is odd, and the next tile starts in buffer 0)
+                    const int cur = (ks * NQ + uu) & 1;
                     // The B fragment of the next statistic tile (of tile 0 of the next
                     // k-step; the one of the next TILE comes from the other buffer, after
                     // the barrier), built behind this tile's 48 MFMAs, one filler each, every
@@ -2166,6 +2198,19 @@ inline int ntx_for(int S, int K) { return S > 1 ? 16 : (K <= 64 ? 4 : (K <= 128 
 inline int nchunksx_for(int S, int K) { return S > 1 ? (K + 255) / 256 : 1; }
 size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 
+// statistic tiles per wave of accx_kernel: the NQ in 6 .. 8 that executes the fewest
+// tiles, gx NQ per wave (a workgroup holds a CU: idle waves cost their SIMD's time too);
+// ties go to the larger NQ (fewer workgroups, each of which copies the R tiles).  The
+// 54 tiles of a full covariance at D = 40 (band layout): NQ = 7, 2 x 4 x 7 = 56.
+inline int accx_nq(int ntiles) {
+    int best = 0, cost = 0;
+    for (int nq = 8; nq >= 6; --nq) {
+        const int c = (ntiles + kAxWaves * nq - 1) / (kAxWaves * nq) * nq;
+        if (best == 0 || c < cost) { cost = c; best = nq; }
+    }
+    return best;
+}
+
 // bytes of the P image: nchunks x nk x NT blocks + one look-ahead batch
 inline size_t p_image_bytes(int nchunks, int nk, int NT) {
     return up256(((size_t)nchunks * nk * NT + 4) * kBlockU4 * 16);
@@ -2179,18 +2224,21 @@ namespace {
 template __global__ void llhx_kernel<16, 4, 4, true, false, false>(
     int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
     double*, float*, int, int, int, const float*, const u4*);
+template __global__ void llhx_kernel<16, 2, 4, true, false, false, false, true>(
+    int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
+    double*, float*, int, int, int, const float*, const u4*);
 template __global__ void llhx_kernel<16, 2, 1, false, true, true>(
     int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
     double*, float*, int, int, int, const float*, const u4*);
 template __global__ void llhx_kernel<16, 2, 1, false, true, true, true>(
     int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
     double*, float*, int, int, int, const float*, const u4*);
-template __global__ void accx_kernel<false>(int64_t, int, int, int, int, const float*, const unsigned*,
-                                            const int*, int64_t, double*, int, int, int,
-                                            const float*, int, int);
-template __global__ void accx_kernel<true>(int64_t, int, int, int, int, const float*, const unsigned*,
-                                           const int*, int64_t, double*, int, int, int,
-                                           const float*, int, int);
+template __global__ void accx_kernel<false, 7>(int64_t, int, int, int, int, const float*, const unsigned*,
+                                               const int*, int64_t, double*, int, int, int,
+                                               const float*, int, int, int);
+template __global__ void accx_kernel<true, 7>(int64_t, int, int, int, int, const float*, const unsigned*,
+                                              const int*, int64_t, double*, int, int, int,
+                                              const float*, int, int, int);
 template __global__ void lnfi_kernel<3, 16>(int64_t, int, int, int, const u4*, const u4*, float*, double*,
                                             int64_t, const float*);
 template __global__ void accfi_kernel<3, 8>(int64_t, int, int, int, int, int, int, const u4*, const u4*,
@@ -2443,7 +2491,7 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
 
 size_t accx_base_workspace_bytes(int cov, int D, int K) {
     if (!supported_acc_x(D, K)) return 0;
-    const int nslab = nslab_of(cov, D);
+    const int nslab = nslabx_of(cov, D);
     return up256((size_t)K * nslab * 4 * sizeof(double)) + up256((size_t)nslab * sizeof(int)) + 1024;
 }
 
@@ -2477,7 +2525,7 @@ int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, co
     if (SR && (S * G != K || !supported_acc_sets(cov, D, S, G) ||
                ws_bytes < accxs_workspace_bytes(cov, nframes, D, S, G)))
         return BEER_EINVAL;
-    const int nslab = nslab_of(cov, D), nq = nslab * 4;
+    const int nslab = nslabx_of(cov, D), nq = nslab * 4;
     char* w = reinterpret_cast<char*>(ws);
     double* Sp = reinterpret_cast<double*>(w);
     w += up256((size_t)K * nq * sizeof(double));
@@ -2486,7 +2534,7 @@ int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, co
                                          accx_base_workspace_bytes(cov, D, K));
     hipError_t e = hipMemsetAsync(Sp, 0, (size_t)K * nq * sizeof(double), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(tab_kernel, dim3(1), dim3(256), 0, s, cov, D, tab);
+    hipLaunchKernelGGL(tabx_kernel, dim3(1), dim3(256), 0, s, cov, D, nslab, tab);
     BEER_LAUNCH_CHECK();
     const int64_t tiles = (nframes + kAxFT - 1) / kAxFT;
     const int NX = xt_pieces(D);
@@ -2511,7 +2559,8 @@ int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, co
         BEER_LAUNCH_CHECK();
         while ((1 << lgG) < G) ++lgG;
     }
-    const int gx = (ntiles + kAxNQ * kAxWaves - 1) / (kAxNQ * kAxWaves);
+    const int NQ = accx_nq(ntiles);
+    const int gx = (ntiles + NQ * kAxWaves - 1) / (NQ * kAxWaves);
     const int gy = (K + 16 * kAxMC - 1) / (16 * kAxMC);
     // one workgroup per CU (120 KB of LDS, 512 registers per lane): whole rounds of 256
     // workgroups, at most BEER_OPT_AX_MAXFRAMES frames each
@@ -2531,20 +2580,27 @@ int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, co
     if (sx) lds = (size_t)NX * kPiece + 2 * (size_t)NP * kPackedPlaneWords * 4 + (SR ? 2 * 4096 : 0);
     const int64_t nyz = ((int64_t)gy * gz + 7) / 8 * 8;
     const dim3 grid((unsigned)(nyz * gx));
-#define BEER_ACCX(SR_)                                                                           \
+    const int band = band_layout(cov, D) ? 1 : 0;
+#define BEER_ACCX(SR_, NQ_)                                                                      \
     do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accx_kernel<SR_>),               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);         \
-        hipLaunchKernelGGL((accx_kernel<SR_>), grid, dim3(64 * kAxWaves), lds, s, nframes, D, K, \
-                           nslab, NX, Xt, reinterpret_cast<const unsigned*>(Rimg), tab, fpb, Sp, \
-                           gx, gy, (int)gz, Gt, lgG, sx);                                        \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accx_kernel<SR_, NQ_>),          \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
+        hipLaunchKernelGGL((accx_kernel<SR_, NQ_>), grid, dim3(64 * kAxWaves), lds, s, nframes, \
+                           D, K, nslab, NX, Xt, reinterpret_cast<const unsigned*>(Rimg), tab,    \
+                           fpb, Sp, gx, gy, (int)gz, Gt, lgG, sx, band);                         \
     } while (0)
-    if (SR) BEER_ACCX(true);
-    else BEER_ACCX(false);
+#define BEER_ACCX_NQ(SR_)                                                                        \
+    do {                                                                                         \
+        if (NQ == 6) BEER_ACCX(SR_, 6); else if (NQ == 7) BEER_ACCX(SR_, 7);                     \
+        else BEER_ACCX(SR_, 8);                                                                  \
+    } while (0)
+    if (SR) BEER_ACCX_NQ(true);
+    else BEER_ACCX_NQ(false);
+#undef BEER_ACCX_NQ
 #undef BEER_ACCX
     BEER_LAUNCH_CHECK();
     const int64_t total = (int64_t)K * stats_dim(cov, D);
-    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
+    hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
                        D, K, Sp, acc);
     BEER_LAUNCH_CHECK();
     return BEER_OK;
@@ -2583,11 +2639,6 @@ size_t frame_image_bytes(int cov, int64_t nframes, int D) {
     return (size_t)tiles * frame_image_tile_u4(nk_used, img_nqt(nk_used)) * 16 +
            up256((size_t)(nk + 1) * 8 * sizeof(int));
 }
-__global__ void tabx_kernel(int cov, int D, int nk, int* __restrict__ tab) {
-    const int Dp = 4 * d4_of(D);
-    for (int s = threadIdx.x; s < (nk + 1) * 8; s += blockDim.x)
-        tab[s] = s < nslab_of(cov, D) ? slab_entry(cov, D, s) : ((Dp + 2) | ((Dp + 4) << 8));
-}
 int frame_image(int cov, int64_t nframes, int D, const float* X, void* image, hipStream_t s) {
     if (!supported_frame_image(cov, D)) return BEER_EINVAL;
     if (nframes == 0) return BEER_OK;
@@ -2595,7 +2646,7 @@ int frame_image(int cov, int64_t nframes, int D, const float* X, void* image, hi
     const int64_t tiles = (nframes + 31) / 32;
     int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(image) +
                                       (size_t)tiles * frame_image_tile_u4(nk_used, img_nqt(nk_used)) * 16);
-    hipLaunchKernelGGL(tabx_kernel, dim3(1), dim3(256), 0, s, cov, D, nk, tab);
+    hipLaunchKernelGGL(tabx_kernel, dim3(1), dim3(256), 0, s, cov, D, (nk + 1) * 8, tab);
     const size_t lds = (size_t)(nk + 1) * 8 * sizeof(int) +
                        (size_t)4 * (32 * ld16_of(D) + (D + 2) * kAfXS) * sizeof(float);
     hipLaunchKernelGGL(frame_image_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), lds, s,
@@ -2695,7 +2746,7 @@ int acc_fused_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float*
 #undef BEER_ACCFI
         BEER_LAUNCH_CHECK();
         const int64_t total_i = (int64_t)Kreal * stats_dim(cov, D);
-        hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total_i + 255) / 256)), dim3(256), 0, s,
+        hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total_i + 255) / 256)), dim3(256), 0, s,
                            cov, D, Kreal, Sp, acc);
         BEER_LAUNCH_CHECK();
         return BEER_OK;
@@ -2716,7 +2767,7 @@ int acc_fused_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float*
 #undef BEER_ACCF
     BEER_LAUNCH_CHECK();
     const int64_t total = (int64_t)Kreal * stats_dim(cov, D);
-    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
+    hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
                        D, Kreal, Sp, acc);
     BEER_LAUNCH_CHECK();
     return BEER_OK;

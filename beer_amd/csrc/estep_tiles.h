@@ -188,6 +188,89 @@ __host__ __device__ inline int slab_index(int cov, int D, int a, int j) {
     const int before = 4 * (q * D4 - q * (q - 1) / 2) + r * (D4 - q);
     return before + (j - q);
 }
+// Band enumeration of a full covariance's quadratic terms (the bf16x3 kernels of
+// estep_bf16.hip only; the exact kernels keep the slabs above).  The slabs above pad
+// every row a of the triangle out to the aligned block that holds a (880 quadratic
+// columns for 820 products at D = 40).  Here a frame row is indexed a' in [0, Dp),
+// dimensions >= D are zero, and the pairs are walked by wrap-around diagonal d =
+// 0 .. Dp/2: band slab (a4, d) holds x[a4 + e] * x[(a4 + e + d) mod Dp], e = 0..3, a4
+// over the Dp/4 aligned starts -- at d = Dp/2 only a4 < Dp/2, whose pairs are the
+// others' mirror images otherwise.  Every unordered pair appears exactly once; when Dp %
+// 8 == 4 the last slab of d = Dp/2 straddles, its entries a >= Dp/2 repeat pairs already
+// counted and carry 0.  Dp (Dp + 1) / 8 slabs when Dp % 8 == 0 (205 at D = 40), then the
+// D4 linear slabs and the constant slab as above: 216 slabs = 27 k-steps at D = 40.
+// Table entry (one int, the same for every kind of slab):
+//     j | (step << 8) | (b << 16)
+// product e = x[j + e] * x[w(b + step e)], w(i) = i < Dp ? i : i - Dp.  b < 2 Dp always:
+// band slabs have j = a4, step 1, b = a4 + d; linear slab q j = 4q, step 0, b = 2 Dp
+// (x[Dp] = 1); the constant j = Dp, b = 2 Dp; padding j = Dp + 4 (zeros), b = 2 Dp + 2.
+__host__ __device__ inline bool band_layout(int cov, int D) { return cov == BEER_FULL; }
+__host__ __device__ inline int band_nslab(int D) {
+    const int Dp = 4 * d4_of(D), h = Dp / 2;
+    return h * (Dp / 4) + (h + 3) / 4;
+}
+__host__ __device__ inline int band_entry(int D, int s) {
+    const int D4 = d4_of(D), Dp = 4 * D4, nb = band_nslab(D);
+    if (s < nb) {
+        const int d = s / D4, a4 = 4 * (s - d * D4);
+        return a4 | (1 << 8) | ((a4 + d) << 16);
+    }
+    if (s < nb + D4) return (4 * (s - nb)) | ((2 * Dp) << 16);   // linear
+    if (s == nb + D4) return Dp | ((2 * Dp) << 16);                // constant
+    return (Dp + 4) | ((2 * Dp + 2) << 16);                        // padding
+}
+// the second factor's column w(b + step e) of table entry t (i - Dp wraps round as unsigned
+// below Dp: the minimum is one v_min_u32)
+__host__ __device__ __forceinline__ int band_col(int t, int e, int Dp) {
+    const unsigned c = (unsigned)((t >> 16) + ((t >> 8) & 1) * e), w = c - (unsigned)Dp;
+    return (int)(w < c ? w : c);
+}
+// entry position 4 slab + e of the product x_a x_b (a, b < D, any order)
+__host__ __device__ inline int band_pos(int D, int a, int b) {
+    const int D4 = d4_of(D), Dp = 4 * D4;
+    if (a > b) { const int t = a; a = b; b = t; }
+    int d = b - a, start = a;
+    if (2 * d > Dp) { d = Dp - d; start = b; }
+    return 4 * (d * D4 + start / 4) + start % 4;
+}
+// (band slab s, entry e) -> the pair (a, b); false: the entry holds no pair of its own
+// (a dimension >= D, or the repeated half of the straddling slab)
+__host__ __device__ inline bool band_pair(int D, int s, int e, int* a, int* b) {
+    const int D4 = d4_of(D), Dp = 4 * D4;
+    const int d = s / D4;
+    *a = 4 * (s - d * D4) + e;
+    *b = (*a + d) % Dp;
+    if (*a >= D || *b >= D) return false;
+    return !(2 * d == Dp && 2 * *a >= Dp);
+}
+
+// The layout of the bf16x3 kernels, selected by band_layout(): slab count, table entry
+// (padding beyond the slabs: zero columns), entry positions of the statistics
+__host__ __device__ inline int nslabx_of(int cov, int D) {
+    return band_layout(cov, D) ? band_nslab(D) + d4_of(D) + 1 : nslab_of(cov, D);
+}
+__host__ __device__ inline int slabx_entry(int cov, int D, int s) {
+    if (band_layout(cov, D)) return band_entry(D, s);
+    const int Dp = 4 * d4_of(D);
+    return s < nslab_of(cov, D) ? slab_entry(cov, D, s) : ((Dp + 2) | ((Dp + 4) << 8));
+}
+// position of x_a x_b (a, b < D, full), of linear term a (b == -1) and of the count (a == -1)
+// (slab_pos: the same in the slabs of the exact kernels)
+__host__ __device__ inline int slab_pos(int cov, int D, int a, int b) {
+    const int D4 = d4_of(D), Dp = 4 * D4;
+    if (a < 0) return slab_index(cov, D, Dp, D4) * 4;
+    if (b < 0) return slab_index(cov, D, Dp, a / 4) * 4 + a % 4;
+    if (a > b) { const int t = a; a = b; b = t; }
+    return slab_index(cov, D, a, b / 4) * 4 + b % 4;
+}
+__host__ __device__ inline int slabx_pos(int cov, int D, int a, int b) {
+    if (!band_layout(cov, D)) return slab_pos(cov, D, a, b);
+    const int D4 = d4_of(D), nb = band_nslab(D);
+    if (a < 0) return 4 * (nb + D4);
+    if (b < 0) return 4 * nb + a;
+    return band_pos(D, a, b);
+}
+
 // The constant term of component `row` (E[T], any float type) that constant slab
 // `slab` carries.  Full covariance: one slab, the whole constant.  Diagonal /
 // isotropic: a closing slab holds -1/2 sum_d (lambda mu)_d^2 / lambda_d over the
@@ -242,11 +325,17 @@ __global__ void tab_kernel(int cov, int D, int* __restrict__ tab) {
 // Sp [K][nslab*4] (packed sums) -> acc [K][Q] += in the reference's layout:
 // full [sum r x, -.5 sum r x x^T (dense D x D), -.5 N, +.5 N], diagonal
 // [sum r x, -.5 sum r x^2, -.5 N, +.5 N], isotropic [sum r x, -.5 sum r |x|^2,
-// -.5 N, +.5 D N].
-__global__ void unpack_kernel(int cov, int D, int K, const double* __restrict__ Sp,
-                              double* __restrict__ acc) {
-    const int D4 = d4_of(D), Dp = 4 * D4, nq = nslab_of(cov, D) * 4;
+// -.5 N, +.5 D N].  BAND: the sums are in the layout of the bf16x3 kernels
+// (band_layout()), else in the slabs of the exact kernels.
+template <bool BAND>
+__device__ inline void unpack_stats(int cov, int D, int K, const double* __restrict__ Sp,
+                                    double* __restrict__ acc) {
+    const bool band = BAND && band_layout(cov, D);
+    const int nq = (band ? nslabx_of(cov, D) : nslab_of(cov, D)) * 4;
     const int Q = stats_dim(cov, D);
+    auto pos = [&](int a, int b) {
+        return band ? slabx_pos(cov, D, a, b) : slab_pos(cov, D, a, b);
+    };
     const int64_t total = (int64_t)K * Q;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
@@ -254,24 +343,34 @@ __global__ void unpack_kernel(int cov, int D, int K, const double* __restrict__ 
         const double* s = Sp + (size_t)k * nq;
         double v;
         if (q < D) {
-            v = s[slab_index(cov, D, Dp, q / 4) * 4 + q % 4];
+            v = s[pos(q, -1)];
         } else if (q >= Q - 2) {
-            const double n = s[slab_index(cov, D, Dp, D4) * 4];
+            const double n = s[pos(-1, 0)];
             v = (q == Q - 2) ? -0.5 * n : (cov == BEER_ISO ? 0.5 * (double)D * n : 0.5 * n);
         } else if (cov == BEER_FULL) {
-            int a = (q - D) / D, b = (q - D) % D;
-            if (a > b) { const int t = a; a = b; b = t; }
-            v = -0.5 * s[slab_index(cov, D, a, b / 4) * 4 + b % 4];
+            v = -0.5 * s[pos((q - D) / D, (q - D) % D)];
         } else if (cov == BEER_DIAG) {
-            const int d = q - D;
-            v = -0.5 * s[slab_index(cov, D, d, d / 4) * 4 + d % 4];
+            v = -0.5 * s[pos(q - D, q - D)];
         } else {
             double tot = 0.0;
-            for (int d = 0; d < D; ++d) tot += s[slab_index(cov, D, d, d / 4) * 4 + d % 4];
+            for (int d = 0; d < D; ++d) tot += s[pos(d, d)];
             v = -0.5 * tot;
         }
         acc[idx] += v;
     }
+}
+__global__ void unpack_kernel(int cov, int D, int K, const double* __restrict__ Sp,
+                              double* __restrict__ acc) {
+    unpack_stats<false>(cov, D, K, Sp, acc);
+}
+__global__ void unpackx_kernel(int cov, int D, int K, const double* __restrict__ Sp,
+                               double* __restrict__ acc) {
+    unpack_stats<true>(cov, D, K, Sp, acc);
+}
+// slab table of the bf16x3 kernels: n entries (the slabs, then padding)
+__global__ void tabx_kernel(int cov, int D, int n, int* __restrict__ tab) {
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x)
+        tab[s] = slabx_entry(cov, D, s);
 }
 
 }  // namespace
