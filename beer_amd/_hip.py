@@ -211,6 +211,11 @@ SIGNATURES = {
     'beer_hmm_forward_backward': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_posteriors_fused': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p, c_p,
                                   c_p, c_p],
+    'beer_hmm_posteriors_fused_counts': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p,
+                                         c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_forward_backward_counts': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                         c_p],
+    'beer_hmm_last_frame_sum': [c_i, c_p, c_p, c_p, c_p],
     'beer_hmm_fb_log_count': [c_p, c_p, c_p, c_p],
     'beer_hmm_posteriors_bigram': [c_i, c_p, ctypes.c_int32, c_l, c_p, c_p, c_i, c_p, c_d, c_p,
                                    c_p, c_p, c_i, c_p, c_p],

@@ -144,11 +144,16 @@ BIGRAM_PRIORS = ('dirichlet2', 'hierarchical_dirichlet_process')
 
 
 def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirichlet_process',
-               concentration=None):
+               concentration=None, train_transitions=False, transitions_prior_strength=1.):
     '''`beer hmm mkphoneloop` (mkphoneloop.py:30-80): a `BigramPhoneLoop` for the
-    bigram priors (`dirichlet2`, `hierarchical_dirichlet_process`), else a `PhoneLoop`.'''
+    bigram priors (`dirichlet2`, `hierarchical_dirichlet_process`), else a `PhoneLoop`.
+    `train_transitions` (not in the reference): the units' transition probabilities are
+    learned too (PhoneLoop only).'''
     size = len(start_pdf)
     conc = concentration if concentration else size / 2
+    if train_transitions and weights_prior in BIGRAM_PRIORS:
+        raise ValueError('learned transitions (--train-transitions) are not supported on a '
+                         f'bigram phone loop (--weights-prior {weights_prior})')
     if weights_prior == 'dirichlet2':
         cset = beer.CategoricalSet.create(torch.ones(size, size) / size, prior_strength=conc)
         return beer.BigramPhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cset)
@@ -165,7 +170,9 @@ def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirich
                                                   hyper_prior_strength=1.)
     else:
         raise ValueError(f'unknown prior over the weights: {weights_prior!r}')
-    return beer.PhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cat)
+    return beer.PhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cat,
+                                 train_transitions=train_transitions,
+                                 transitions_prior_strength=transitions_prior_strength)
 
 
 def bigram_loop(ploop, weights_prior):
@@ -174,6 +181,9 @@ def bigram_loop(ploop, weights_prior):
     (every concentration 1 / P); the hierarchical Dirichlet process is rooted at the
     unigram's own stick-breaking weights, with prior strength P / 2.'''
     size = len(ploop.start_pdf)
+    if getattr(ploop, 'transitions', None) is not None:
+        raise ValueError('learned transitions are not supported on a bigram phone loop: make '
+                         'the bigram loop from a unigram loop without --train-transitions')
     if weights_prior == 'dirichlet2':
         cset = beer.CategoricalSet.create(torch.ones(size, size) / size, prior_strength=1)
     elif weights_prior == 'hierarchical_dirichlet_process':
@@ -286,6 +296,11 @@ class mkphoneloop:
                             help='concentration of the Dirichlet Process')
         parser.add_argument('--weights-prior', default='gamma_dirichlet_process',
                             choices=mkphoneloop.PRIORS, help='prior over the phone weights')
+        parser.add_argument('--train-transitions', action='store_true',
+                            help='learn the transition probabilities of the units too '
+                                 '(Dirichlet priors; not in the reference)')
+        parser.add_argument('--transitions-prior-strength', type=float, default=1.,
+                            help='prior strength of the learned transition probabilities')
         parser.add_argument('decode_graph', help='decoding graph')
         parser.add_argument('hmms', help="phones' hmm")
         parser.add_argument('out', help='phone loop model')
@@ -295,7 +310,9 @@ class mkphoneloop:
         graph, start_pdf, end_pdf = _load(args.decode_graph)
         _, emissions = _load(args.hmms)
         size = len(start_pdf)
-        ploop = phone_loop(graph, start_pdf, end_pdf, emissions, args.weights_prior, args.concentration)
+        ploop = phone_loop(graph, start_pdf, end_pdf, emissions, args.weights_prior,
+                           args.concentration, args.train_transitions,
+                           args.transitions_prior_strength)
         _dump(ploop, args.out)
         logger.info(f'successfully created a phone-loop model with {size} phones')
 

@@ -863,12 +863,21 @@ __device__ __forceinline__ int expo_field(double v) {
 // atomics (1.07 M frames x 100 states of them cost the recipes' alignment-graph training 0.7 ms of
 // a 6.4 ms epoch); needs S_total <= kWvRowMax.
 constexpr int kWvRowMax = 512;
-template <typename T, int SPL, int DEG, bool FUSED, bool XI, int OUTM>
-__global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_wave_kernel(
+// CNT (with XI): the transition counts of learned transition probabilities instead of the dense
+// xi_sum -- the arcs' sums go to `arc_counts` in the low-degree image's out-CSR order (graph 0 for
+// every utterance), and `src_flow[j]` receives the expected exits of state j: its flow into the hub
+// (sum_t a_t(j) w_src(j) H'_{t+1} / norm_t, H' the backward hub value) plus its posterior at the
+// last frame (the utterance ends by leaving j; 0 where the final weight is 0).
+// (CNT is compiled for one wave per SIMD less: the per-arc sums and the source flows take the
+// registers that kept the recipe's shape, 120 states on two slots a lane, from spilling)
+template <typename T, int SPL, int DEG, bool FUSED, bool XI, int OUTM, bool CNT>
+__global__ __launch_bounds__(64 * kWvWaves, (BEER_FB_OCC - (CNT ? 1 : 0)) * 4 / kWvWaves) void fb_wave_kernel(
     beer_batch b, const T* __restrict__ pc, int S_total, T scale, double* __restrict__ alpha_ws,
     double* __restrict__ hubf_ws, T* __restrict__ out, T resp_scale,
     double* __restrict__ xi_sum, double* __restrict__ gamma0_sum, double* __restrict__ hub_flow,
-    double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh) {
+    double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh,
+    double* __restrict__ arc_counts, double* __restrict__ src_flow) {
+    static_assert(!CNT || XI, "the counts are the per-arc sums of xi");
     typedef Lin<T> R;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -907,7 +916,7 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
     double iw[SPL][DEG], ow[SPL][DEG], hs_w[SPL], hd_w[SPL], fin_w[SPL];
     bool st[SPL];
     int64_t ll_off[SPL], a_off[SPL];                       // element offsets per frame 0
-    double xi_r[XI ? SPL : 1][DEG], flow_r[SPL];
+    double xi_r[XI ? SPL : 1][DEG], flow_r[SPL], sf_r[CNT ? SPL : 1];
     const int32_t* ids = FUSED ? b.pdf_ids + b.pdf_off[gid] : nullptr;
 #pragma unroll
     for (int p = 0; p < SPL; ++p) {
@@ -916,6 +925,7 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
         own[p] = cur0 + 8 * j;
         hs_w[p] = hd_w[p] = fin_w[p] = 0.0;
         flow_r[p] = 0.0;
+        if (CNT) sf_r[p] = 0.0;
         int ib = 0, ie = 0, ob = 0, oe = 0, id = 0;
         if (st[p]) {
             ib = L.in_ptr[j]; ie = L.in_ptr[j + 1];
@@ -1159,7 +1169,7 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
     // then lb_t = b_t beta_t for frame t - 1
     auto finish_frame = [&](int64_t t, const double (&a_cur)[SPL], const T (&lt_cur)[SPL],
                             double (&beta)[SPL], const double (&lbd)[SPL][DEG], double hf_cur,
-                            bool inner, double mt, bool scale_now) {
+                            bool inner, double mt, bool scale_now, double hb) {
         double gq[SPL], gsum = 0.0;
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
@@ -1210,6 +1220,8 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
                     const double ai = a_cur[p] * inv;
 #pragma unroll
                     for (int k = 0; k < DEG; ++k) xi_r[p][k] = __builtin_fma(ai * ow[p][k], lbd[p][k], xi_r[p][k]);
+                    // (the exits through the hub: hb = sum_s w_dst(s) b_{t+1}(s) beta_{t+1}(s))
+                    if (CNT) sf_r[p] = __builtin_fma(ai * hs_w[p], hb, sf_r[p]);
                 }
                 if (has_hub && hub_flow)
                     flow_r[p] = __builtin_fma(hfi * hd_w[p], lb_own[p], flow_r[p]);
@@ -1272,7 +1284,12 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
         T one[1][SPL];
 #pragma unroll
         for (int p = 0; p < SPL; ++p) one[0][p] = lt_cur[p];
-        finish_frame(t, a_cur, lt_cur, beta, lbd, 0.0, false, frames_max(one, 1), true);
+        finish_frame(t, a_cur, lt_cur, beta, lbd, 0.0, false, frames_max(one, 1), true, 0.0);
+        // (the exits at the end of the utterance: the posteriors of its last frame)
+        if constexpr (CNT) {
+#pragma unroll
+            for (int p = 0; p < SPL; ++p) sf_r[p] = g0v[p];
+        }
     }
     auto backward_step = [&](int64_t t, const A_t (&a_t)[SPL], const T (&lt_cur)[SPL], double hf_cur,
                              double mt, bool scale_now) {
@@ -1290,7 +1307,7 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
             }
             beta[p] = acc;
         }
-        finish_frame(t, a_cur, lt_cur, beta, lbd, hf_cur, true, mt, scale_now);
+        finish_frame(t, a_cur, lt_cur, beta, lbd, hf_cur, true, mt, scale_now, hub);
     };
     for (int t0 = T_ - 2; t0 >= 0; t0 -= PF) {
         const double mt = frames_max(lt_ring, PF);        // (frames before the start: frame 0 again)
@@ -1332,6 +1349,13 @@ __global__ __launch_bounds__(64 * kWvWaves, BEER_FB_OCC * 4 / kWvWaves) void fb_
             for (int k = 0; k < DEG; ++k)
                 if (ow[p][k] > 0.0 && xi_r[p][k] != 0.0)
                     atomicAdd(xi_sum + (size_t)j * S + (odst[p][k] - lb0) / 8, xi_r[p][k]);
+        }
+        if constexpr (CNT) {
+            const int ob = L.out_ptr[j];
+#pragma unroll
+            for (int k = 0; k < DEG; ++k)
+                if (ow[p][k] > 0.0 && xi_r[p][k] != 0.0) atomicAdd(arc_counts + ob + k, xi_r[p][k]);
+            if (sf_r[p] != 0.0) atomicAdd(src_flow + j, sf_r[p]);
         }
         if (hub_flow && hd_w[p] > 0.0) atomicAdd(hub_flow + j, flow_r[p]);
     }
@@ -1381,12 +1405,14 @@ __device__ __forceinline__ double rel_base(R m) {
     return m > (R)-INFINITY ? (double)m : 0.0;
 }
 
-template <typename T, int SPL, int DEG, bool FUSED, bool XI>
+template <typename T, int SPL, int DEG, bool FUSED, bool XI, bool CNT>
 __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
     beer_batch b, const T* __restrict__ pc, int S_total, T scale, double* __restrict__ alpha_ws,
     double* __restrict__ hubf_ws, T* __restrict__ out, T resp_scale, int atomic_out,
     double* __restrict__ xi_sum, double* __restrict__ gamma0_sum, double* __restrict__ hub_flow,
-    double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh) {
+    double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh,
+    double* __restrict__ arc_counts, double* __restrict__ src_flow) {
+    static_assert(!CNT || XI, "the counts are the per-arc sums of xi");
     typedef Rel<T> R;
     typedef typename R::r_t r_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1435,7 +1461,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
     T iw[SPL][DEG], ow[SPL][DEG], hs_w[SPL], hd_w[SPL], fin_w[SPL];
     bool st[SPL];
     int64_t ll_off[SPL], a_off[SPL];                       // element offsets per frame 0
-    double xi_r[XI ? SPL : 1][DEG], flow_r[SPL];
+    double xi_r[XI ? SPL : 1][DEG], flow_r[SPL], sf_r[CNT ? SPL : 1];
     const int32_t* ids = FUSED ? b.pdf_ids + b.pdf_off[gid] : nullptr;
 #pragma unroll
     for (int p = 0; p < SPL; ++p) {
@@ -1444,6 +1470,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
         own[p] = cur0 + 8 * j;
         hs_w[p] = hd_w[p] = fin_w[p] = ninf<T>();
         flow_r[p] = 0.0;
+        if (CNT) sf_r[p] = 0.0;
         int ib = 0, ie = 0, ob = 0, oe = 0, id = 0;
         if (st[p]) {
             ib = L.in_ptr[j]; ie = L.in_ptr[j + 1];
@@ -1604,7 +1631,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
     double hf_next = NINF;
     auto finish_frame = [&](int64_t t, const double (&a_cur)[SPL], const T (&lt_cur)[SPL],
                             const double (&beta)[SPL], const double (&vout)[SPL][DEG],
-                            double hf_cur, bool inner) {
+                            double hf_cur, bool inner, double hb) {
         double ab[SPL];
         r_t m = (r_t)-INFINITY;
 #pragma unroll
@@ -1639,6 +1666,8 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
                     out[b.llh_off[u] + t * S + a_off[p]] = (T)gv;
                 }
                 if (t == 0 && gamma0_sum) atomicAdd(gamma0_sum + a_off[p], gv);
+                // (the exits at the end of the utterance: the posteriors of its last frame)
+                if (CNT && !inner) sf_r[p] += (ok && gv == gv) ? gv : 0.0;
             }
             if (inner) {
                 if (XI) {
@@ -1647,6 +1676,11 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
                     for (int k = 0; k < DEG; ++k) {
                         const double val = (double)R::ex(ai + vout[p][k]);
                         xi_r[p][k] += (ok && val == val) ? val : 0.0;
+                    }
+                    if (CNT) {
+                        // (the exits through the hub: hb = the backward hub value of frame t + 1)
+                        const double val = (double)R::ex(ai + (double)hs_w[p] + hb);
+                        sf_r[p] += (ok && val == val) ? val : 0.0;
                     }
                 }
                 if (has_hub && hub_flow) {
@@ -1684,7 +1718,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
             lt_next[p] = load_ll(t > 0 ? t - 1 : 0, p);
         }
         if (has_hub && t > 0) hf_next = hubf[t - 1];
-        finish_frame(t, a_cur, lt_cur, beta, vout, NINF, false);
+        finish_frame(t, a_cur, lt_cur, beta, vout, NINF, false, NINF);
     }
     for (int64_t t = T_ - 2; t >= 0; --t) {
         double a_cur[SPL], beta[SPL], vout[SPL][DEG];
@@ -1707,7 +1741,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
             for (int k = 0; k < DEG; ++k) vout[p][k] = (double)ow[p][k] + lds(odst[p][k]);
             beta[p] = lane_lse(vout[p], (double)hs_w[p] + hub);
         }
-        finish_frame(t, a_cur, lt_cur, beta, vout, hf_cur, true);
+        finish_frame(t, a_cur, lt_cur, beta, vout, hf_cur, true, hub);
     }
 #undef BEER_WAVE_ORDER
     if (lognorm_mean && lane == 0) lognorm_mean[u] = (T)(ln_acc / (double)T_);
@@ -1724,6 +1758,13 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
             for (int k = 0; k < DEG; ++k)
                 if (ow[p][k] > ninf<T>() && xi_r[p][k] != 0.0)
                     atomicAdd(xi_sum + (size_t)j * S + (odst[p][k] - lb0) / 8, xi_r[p][k]);
+        }
+        if constexpr (CNT) {
+            const int ob = L.out_ptr[j];
+#pragma unroll
+            for (int k = 0; k < DEG; ++k)
+                if (ow[p][k] > ninf<T>() && xi_r[p][k] != 0.0) atomicAdd(arc_counts + ob + k, xi_r[p][k]);
+            if (sf_r[p] != 0.0) atomicAdd(src_flow + j, sf_r[p]);
         }
         if (hub_flow && hd_w[p] > ninf<T>()) atomicAdd(hub_flow + j, flow_r[p]);
     }
@@ -1933,6 +1974,19 @@ __global__ __launch_bounds__(256) void xi_dense_kernel(int64_t nframes, int S,
         o[e] = finite && sm > 0.0 ? (T)(exp(term(e) - m) / sm) : (T)0;
 }
 
+// sum over the utterances of the state posteriors of their LAST frame (the end-of-utterance
+// exits of learned transitions on the general path): one workgroup per utterance, graph 0
+template <typename T>
+__global__ __launch_bounds__(256) void last_frame_kernel(beer_batch b, const T* __restrict__ gamma,
+                                                         double* __restrict__ out) {
+    const int u = blockIdx.x;
+    const int64_t T_ = b.frame_off[u + 1] - b.frame_off[u];
+    if (T_ <= 0) return;
+    const int S = b.graphs[0].n_states;
+    const T* g = gamma + b.llh_off[u] + (T_ - 1) * S;
+    for (int s = threadIdx.x; s < S; s += blockDim.x) atomicAdd(out + s, (double)g[s]);
+}
+
 // ---- launchers -------------------------------------------------------------
 
 template <typename T>
@@ -2001,9 +2055,11 @@ template <typename T, bool FUSED>
 int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, double* alpha_ws,
                    double* hub_ws, T* out, T resp_scale, int atomic_out, double* xi_sum,
                    double* gamma0_sum, double* hub_flow, double* utt_llh, T* lognorm_mean,
-                   T* frame_llh, hipStream_t s) {
+                   T* frame_llh, hipStream_t s, double* arc_counts = nullptr,
+                   double* src_flow = nullptr) {
     const dim3 grid((unsigned)((b->nutt + kWvWaves - 1) / kWvWaves)), block(64 * kWvWaves);
     const bool xi = !FUSED && xi_sum != nullptr;
+    const bool cnt = arc_counts != nullptr;
     const int spl = b->max_states <= 64 ? 1 : (b->max_states <= 128 ? 2 : 4);
     const int deg = b->max_degree <= 2 ? 2 : (b->max_degree <= 4 ? 4 : 8);
     const bool rows = FUSED && atomic_out == 2;
@@ -2012,48 +2068,52 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
                        (rows ? (size_t)kWvWaves * kWvRowMax * sizeof(T) : 0);
     const bool all_log = beer::option(BEER_OPT_FB_LOG) != 0;
     // the linear-domain kernel, then the log-space one for the utterances it flagged
-#define BEER_WV(SPL_, DEG_, XI_)                                                                \
+#define BEER_WV(SPL_, DEG_, XI_, CNT_)                                                          \
     do {                                                                                        \
         if (all_log)                                                                            \
             hipLaunchKernelGGL(fb_flag_all_kernel, dim3((unsigned)((b->nutt + 255) / 256)),     \
                                dim3(256), 0, s, *b, hub_ws);                                    \
         else if (rows)                                                                          \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 2 : 0>), grid, \
-                               block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out,    \
-                               resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean, \
-                               frame_llh);                                                     \
+            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 2 : 0, CNT_>), \
+                               grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
+                               out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
+                               lognorm_mean, frame_llh, arc_counts, src_flow);                  \
         else if (FUSED && atomic_out)                                                           \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 1 : 0>), grid, \
+            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 1 : 0, CNT_>), \
+                               grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
+                               out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
+                               lognorm_mean, frame_llh, arc_counts, src_flow);                  \
+        else                                                                                    \
+            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, 0, CNT_>), grid,      \
                                block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out,    \
                                resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean, \
-                               frame_llh);                                                     \
-        else                                                                                    \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, 0>), grid, block,     \
-                               lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out,           \
-                               resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean, \
-                               frame_llh);                                                     \
-        hipLaunchKernelGGL((fb_wave_log_kernel<T, SPL_, DEG_, FUSED, XI_>), grid, block, lds,  \
-                           s, *b, pc, S_total, scale, alpha_ws, hub_ws, out, resp_scale,       \
+                               frame_llh, arc_counts, src_flow);                                \
+        hipLaunchKernelGGL((fb_wave_log_kernel<T, SPL_, DEG_, FUSED, XI_, CNT_>), grid, block,  \
+                           lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out, resp_scale,  \
                            atomic_out, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean,    \
-                           frame_llh);                                                         \
+                           frame_llh, arc_counts, src_flow);                                   \
     } while (0)
-#define BEER_WV_DEG(SPL_, XI_)                                                                  \
+#define BEER_WV_DEG(SPL_, XI_, CNT_)                                                            \
     do {                                                                                        \
-        if (deg == 2) BEER_WV(SPL_, 2, XI_);                                                    \
-        else if (deg == 4) BEER_WV(SPL_, 4, XI_);                                               \
-        else BEER_WV(SPL_, 8, XI_);                                                             \
+        if (deg == 2) BEER_WV(SPL_, 2, XI_, CNT_);                                              \
+        else if (deg == 4) BEER_WV(SPL_, 4, XI_, CNT_);                                         \
+        else BEER_WV(SPL_, 8, XI_, CNT_);                                                       \
     } while (0)
-#define BEER_WV_SPL(XI_)                                                                        \
+#define BEER_WV_SPL(XI_, CNT_)                                                                  \
     do {                                                                                        \
-        if (spl == 1) BEER_WV_DEG(1, XI_);                                                      \
-        else if (spl == 2) BEER_WV_DEG(2, XI_);                                                 \
-        else BEER_WV_DEG(4, XI_);                                                               \
+        if (spl == 1) BEER_WV_DEG(1, XI_, CNT_);                                                \
+        else if (spl == 2) BEER_WV_DEG(2, XI_, CNT_);                                           \
+        else BEER_WV_DEG(4, XI_, CNT_);                                                         \
     } while (0)
-    if constexpr (FUSED) {
-        BEER_WV_SPL(false);
+    // (CNT: the transition counts of learned transition probabilities, new instantiations;
+    //  the others are the kernels as they were)
+    if (cnt) {
+        BEER_WV_SPL(true, true);
+    } else if constexpr (FUSED) {
+        BEER_WV_SPL(false, false);
     } else {
-        if (xi) BEER_WV_SPL(true);
-        else BEER_WV_SPL(false);
+        if (xi) BEER_WV_SPL(true, false);
+        else BEER_WV_SPL(false, false);
     }
 #undef BEER_WV_SPL
 #undef BEER_WV_DEG
@@ -2084,6 +2144,66 @@ int beer_hmm_posteriors_fused(int dtype, const beer_batch* b, int S_total, const
     return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
                                         hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
                                         gamma0_sum, hub_flow, utt_llh, nullptr, (double*)frame_llh, s);
+}
+
+int beer_hmm_posteriors_fused_counts(int dtype, const beer_batch* b, int S_total,
+                                     const void* pc_all, double scale, double* alpha_ws,
+                                     double* hub_ws, void* state_resps, int atomic_out,
+                                     double* gamma0_sum, double* hub_flow, double* utt_llh,
+                                     void* frame_llh, double* arc_counts, double* src_flow,
+                                     void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && S_total >= 1);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(wave_fb_ok(b) && b->n_graphs == 1);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_all && alpha_ws && hub_ws && state_resps && arc_counts && src_flow);
+    hipStream_t s = as_stream(stream);
+    if (dtype == BEER_F32)
+        return wave_fb_launch<float, true>(b, (const float*)pc_all, S_total, (float)scale,
+                                           alpha_ws, hub_ws, (float*)state_resps, (float)scale,
+                                           atomic_out, nullptr, gamma0_sum, hub_flow, utt_llh,
+                                           nullptr, (float*)frame_llh, s, arc_counts, src_flow);
+    return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
+                                        hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
+                                        gamma0_sum, hub_flow, utt_llh, nullptr, (double*)frame_llh,
+                                        s, arc_counts, src_flow);
+}
+
+int beer_hmm_forward_backward_counts(int dtype, const beer_batch* b, const void* pc_llhs,
+                                     double* alpha_ws, double* hub_ws, void* gamma,
+                                     double* gamma0_sum, double* hub_flow, double* arc_counts,
+                                     double* src_flow, void* lognorm_mean, void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(wave_fb_ok(b) && b->n_graphs == 1);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_llhs && alpha_ws && hub_ws && gamma && arc_counts && src_flow);
+    hipStream_t s = as_stream(stream);
+    if (dtype == BEER_F32)
+        return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
+                                            alpha_ws, hub_ws, (float*)gamma, 1.f, 0, nullptr,
+                                            gamma0_sum, hub_flow, nullptr, (float*)lognorm_mean,
+                                            nullptr, s, arc_counts, src_flow);
+    return wave_fb_launch<double, false>(b, (const double*)pc_llhs, b->max_states, 1.0,
+                                         alpha_ws, hub_ws, (double*)gamma, 1.0, 0, nullptr,
+                                         gamma0_sum, hub_flow, nullptr, (double*)lognorm_mean,
+                                         nullptr, s, arc_counts, src_flow);
+}
+
+int beer_hmm_last_frame_sum(int dtype, const beer_batch* b, const void* gamma, double* out,
+                            void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->n_graphs == 1);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(gamma && out);
+    if (dtype == BEER_F32)
+        hipLaunchKernelGGL(last_frame_kernel<float>, dim3(b->nutt), dim3(256), 0, as_stream(stream),
+                           *b, (const float*)gamma, out);
+    else
+        hipLaunchKernelGGL(last_frame_kernel<double>, dim3(b->nutt), dim3(256), 0,
+                           as_stream(stream), *b, (const double*)gamma, out);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
 }
 
 int beer_hmm_gather(int dtype, const beer_batch* batch_h, int S_total, const void* pc_all,

@@ -469,6 +469,36 @@ class DeviceGraph:
                 b['ld_src_w'][src] = t[src, dst0].to(dtype)
                 b['ld_dst_w'][dst] = (t[src0, dst].double() - t[src0, dst0].double()).to(dtype)
 
+    def lowdeg_arcs(self):
+        '''(source, destination) int64 device tensors of the low-degree image's arcs in its
+        out-CSR order -- the order of the transition counts of `beer_hmm_*_counts`.'''
+        b = self.bufs
+        return b['ld_out_src'].long(), b['ld_out_dst'].long()
+
+    def hub_states(self):
+        '(sources, destinations) int64 device tensors of the image\'s hub (one hub).'
+        b = self.bufs
+        src_ptr, dst_ptr = self._hub_ptr
+        return (b['ld_src_list'][src_ptr[0]:src_ptr[1]].long(),
+                b['ld_dst_list'][dst_ptr[0]:dst_ptr[1]].long())
+
+    def arc_positions(self, rows, cols):
+        '''Position of every arc (rows[i], cols[i]) in the low-degree image's out-CSR order
+        (int64 device tensor, memoised per index list); ValueError if one is not there.'''
+        key = (tuple(rows), tuple(cols))
+        memo = self.__dict__.setdefault('_arc_pos', {})
+        if key not in memo:
+            src, dst = (t.cpu() for t in self.lowdeg_arcs())
+            pos = torch.full((self.n_states, self.n_states), -1, dtype=torch.int64)
+            pos[src, dst] = torch.arange(len(src))
+            found = pos[torch.as_tensor(rows, dtype=torch.int64),
+                        torch.as_tensor(cols, dtype=torch.int64)]
+            if bool((found < 0).any()):
+                raise ValueError('a learned transition is not an arc of the graph\'s '
+                                 'low-degree image')
+            memo[key] = found.to(self.bufs['ld_out_src'].device)
+        return memo[key]
+
     @staticmethod
     def _segments(ptr):
         'Cut every CSR row into runs of <= SEG arcs: (arc offsets, row -> seg range).'

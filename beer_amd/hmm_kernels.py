@@ -12,7 +12,8 @@ from . import _hip
 __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors',
            'scatter', 'gather_columns', 'scatter_columns', 'segment_sum', 'fused_ok',
            'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space', 'bigram_ok',
-           'posteriors_bigram']
+           'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
+           'last_frame_sum']
 
 
 class HmmBatch:
@@ -254,14 +255,19 @@ def fused_ok(batch):
 FUSED_ROW_MAX = 512          # kWvRowMax of hmm.hip: pdf ids of a set that fit a wave's LDS row
 
 
-def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, frame_llh=None):
+def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, frame_llh=None,
+                     want_transitions=False):
     '''Gather + forward-backward + scatter of a shard in one launch
     (`beer_hmm_posteriors_fused`): (state_resps [n_frames, S_total] = scale *
     gamma at the pdf ids, gamma0_sum [S] or None, hub_flow [S] or None);
     `utt_llh` [nutt] fp64 += sum_t sum_s gamma * scale * pc; `frame_llh` [n_frames]
     (the batch's dtype) receives that sum per frame (hmm.py:87).  `want_counts`
     (one graph for the whole batch): the posteriors of the first frame and the
-    flows through the graph's hub -- what PhoneLoop counts (phoneloop.py:88-95).'''
+    flows through the graph's hub -- what PhoneLoop counts (phoneloop.py:88-95).
+    `want_transitions` (one graph): the same launch also counts the transitions of learned
+    transition probabilities (`beer_hmm_posteriors_fused_counts`, every other output bit for
+    bit the same) and a fourth value is returned: ('arcs', arc_counts, src_flow) -- see
+    `transition_counts`.'''
     dt, dev = batch.dtype, batch.device
     pc_all = _hip.on_device(pc_all, dt)
     S_total = pc_all.shape[1]
@@ -284,12 +290,93 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
     if frame_llh is not None and (frame_llh.dtype != dt or frame_llh.numel() != batch.n_frames or
                                   not frame_llh.is_contiguous() or frame_llh.device != sr.device):
         raise ValueError('frame_llh: a contiguous [n_frames] tensor of the batch\'s dtype and device')
-    _hip.call('beer_hmm_posteriors_fused', _hip.dtype_code(dt), batch.ref(), S_total,
-              _hip.ptr(pc_all), float(scale), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(sr),
-              out_mode, _hip.ptr(g0), _hip.ptr(flow), _hip.ptr(utt_llh),
-              _hip.ptr(frame_llh))
+    args = (_hip.dtype_code(dt), batch.ref(), S_total, _hip.ptr(pc_all), float(scale),
+            _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(sr), out_mode, _hip.ptr(g0),
+            _hip.ptr(flow), _hip.ptr(utt_llh), _hip.ptr(frame_llh))
+    if want_transitions:
+        arc_counts, src_flow = _count_buffers(batch)
+        _hip.call('beer_hmm_posteriors_fused_counts', *args, _hip.ptr(arc_counts),
+                  _hip.ptr(src_flow))
+    else:
+        _hip.call('beer_hmm_posteriors_fused', *args)
     counting_log_space.note(batch, hub_ws)
+    if want_transitions:
+        return sr, g0, flow, ('arcs', arc_counts, src_flow)
     return sr, g0, flow
+
+
+def lowdeg_arcs(batch):
+    '''(source, destination) int64 device tensors of the arcs of the batch's ONE graph's
+    low-degree image, in its out-CSR order: what `arc_counts` of the count kernels are
+    indexed by (hub arcs are not in it).'''
+    if not batch.shared_graph or getattr(batch.dgraphs[0], 'lowdeg', None) is None:
+        raise ValueError('transition counts need one graph with a low-degree image for the batch')
+    return batch.dgraphs[0].lowdeg_arcs()
+
+
+def _count_buffers(batch):
+    if not batch.shared_graph or not fused_ok(batch):
+        raise ValueError('the one-wave transition counts: one graph for the whole batch, of at '
+                         f'most {FUSED_MAX_STATES} states with at most {_hip.SEG} arcs a state '
+                         'besides one declared hub of at most 64 phones')
+    dev = batch.device
+    S = batch.n_states[0]
+    n_arcs = batch.dgraphs[0].lowdeg.n_arcs
+    return (torch.zeros(max(n_arcs, 1), dtype=torch.float64, device=dev),
+            torch.zeros(S, dtype=torch.float64, device=dev))
+
+
+def last_frame_sum(batch, gamma, out=None):
+    '''sum over the utterances of the posteriors of their last frame, [S] fp64
+    (`beer_hmm_last_frame_sum`; one graph for the batch).'''
+    if not batch.shared_graph:
+        raise ValueError('last-frame posteriors need one graph for the batch')
+    if out is None:
+        out = torch.zeros(batch.n_states[0], dtype=torch.float64, device=batch.device)
+    _hip.call('beer_hmm_last_frame_sum', _hip.dtype_code(batch.dtype), batch.ref(),
+              _hip.ptr(gamma), _hip.ptr(out))
+    return out
+
+
+def forward_backward_counts(batch, pc_llhs):
+    '''Forward-backward with the transition counts of learned transition probabilities, for
+    every batch of one graph that `forward_backward` takes: (gamma packed, gamma0_sum [S],
+    hub_flow [S] or None, xi_sum [S, S] or None, counts).  On the one-wave kernels
+    (`beer_hmm_forward_backward_counts`, `fused_ok`) counts = ('arcs', arc_counts, src_flow)
+    and the phone counts come from hub_flow; beyond them (more than 256 states, hubs of more
+    than 64 phones) the general kernel's dense xi_sum -- hub arcs in the matrix -- and the
+    posteriors of the last frames: counts = ('dense', xi_sum, last).  See `transition_counts`.'''
+    dt, dev = batch.dtype, batch.device
+    if not batch.shared_graph:
+        raise ValueError('transition counts need one graph for the whole batch')
+    if not fused_ok(batch):
+        gamma, xi, g0, _, _ = forward_backward(batch, pc_llhs, want_xi=True, dense_xi=True)
+        return gamma, g0, None, xi, ('dense', xi, last_frame_sum(batch, gamma))
+    arc_counts, src_flow = _count_buffers(batch)
+    S = batch.n_states[0]
+    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
+    alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
+    hub_ws = torch.empty(_hip.MAX_HUBS * batch.n_frames, dtype=torch.float64, device=dev)
+    g0 = torch.zeros(S, dtype=torch.float64, device=dev)
+    flow = torch.zeros(S, dtype=torch.float64, device=dev)
+    _hip.call('beer_hmm_forward_backward_counts', _hip.dtype_code(dt), batch.ref(),
+              _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma),
+              _hip.ptr(g0), _hip.ptr(flow), _hip.ptr(arc_counts), _hip.ptr(src_flow), None)
+    batch.last_alpha = alpha
+    batch.last_alpha_is_log = False
+    counting_log_space.note(batch, hub_ws)
+    return gamma, g0, flow, None, ('arcs', arc_counts, src_flow)
+
+
+def path_counts(batch, path, xi):
+    '''The hard counts of a state path, ('dense', xi, last): the dense xi_sum of
+    `path_posteriors(want_xi=True)` and how often each state ends an utterance.'''
+    path = _hip.on_device(torch.as_tensor(path)).to(torch.int64).reshape(-1)
+    last_states = path[batch.bufs['frame_off'][1:] - 1]
+    last = torch.zeros(xi.shape[0], dtype=torch.float64, device=xi.device)
+    last.index_add_(0, last_states, torch.ones(len(last_states), dtype=torch.float64,
+                                               device=xi.device))
+    return ('dense', xi, last)
 
 
 def bigram_ok(batch):

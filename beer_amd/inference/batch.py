@@ -355,6 +355,12 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     skey = ('hmm', nutt, float(datasize), str(dev))
     off, scales = statics.entry(skey, 'offsets', offsets_and_scales)
     xi_tot = g0_tot = flow_tot = None
+    # learned transition probabilities (HMM.transitions): their counts come out of the
+    # forward-backward launches, summed over the sub-batches in arc / state order
+    learned = model.transitions is not None
+    if learned and not free_loop:
+        model._refuse_transitions('alignment graphs (inference_graphs)')
+    tcounts_tot = None
     bigram = free_loop and isinstance(model, BigramPhoneLoop)
     counts_tot = None
     max_S = model.graph.n_states if free_loop else max(g.n_states for g in graphs)
@@ -430,7 +436,20 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         # pivot); a loop whose end -> start arcs stayed ordinary arcs needs xi
         need_counts = free_loop and isinstance(model, PhoneLoop)
         hubbed = need_counts and getattr(getattr(batch.dgraphs[0], 'lowdeg', None), 'n_hubs', 0) >= 1
-        if not hard and hk.fused_ok(batch) and (hubbed or not need_counts):
+        if learned and not hard and hk.fused_ok(batch) and (hubbed or not need_counts):
+            # the same launch with the transition counts
+            sr, g0, flow, tc = hk.posteriors_fused(batch, pc_all, scale, want_counts=need_counts,
+                                                   utt_llh=utt_llh[run[0]:run[-1] + 1],
+                                                   want_transitions=True)
+            xi = None
+        elif learned and not hard:
+            # the one-wave kernels' counts, or -- graphs beyond them -- the general kernel's
+            # dense xi (hub arcs in the matrix) and the last frames' posteriors
+            pc_llhs = hk.gather(batch, pc_all, scale)
+            gamma, g0, flow, xi, tc = hk.forward_backward_counts(batch, pc_llhs)
+            sr, _ = hk.scatter(batch, pc_llhs, gamma, S_total, scale, want_exp_llh=False,
+                               utt_llh=utt_llh[run[0]:run[-1] + 1])
+        elif not hard and hk.fused_ok(batch) and (hubbed or not need_counts):
             # gather + forward-backward + scatter in one launch, one wave per utterance
             sr, g0, flow = hk.posteriors_fused(batch, pc_all, scale, want_counts=need_counts,
                                                utt_llh=utt_llh[run[0]:run[-1] + 1])
@@ -444,10 +463,15 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                     path = torch.cat([torch.as_tensor(state_paths[u]).reshape(-1) for u in run])
                 gamma, xi, g0 = hk.path_posteriors(batch, path, want_xi=free_loop)
                 flow = None
+                if learned:
+                    tc = hk.path_counts(batch, path, xi)
             else:
                 gamma, xi, g0, _, flow = hk.forward_backward(batch, pc_llhs, want_xi=free_loop)
             sr, _ = hk.scatter(batch, pc_llhs, gamma, S_total, scale, want_exp_llh=False,
                                utt_llh=utt_llh[run[0]:run[-1] + 1])
+        if learned:
+            tc = model.transition_counts(batch.dgraphs[0], tc)
+            tcounts_tot = tc if tcounts_tot is None else tcounts_tot + tc
         if free_loop:
             if xi is not None:
                 xi_tot = xi if xi_tot is None else xi_tot + xi
@@ -464,6 +488,8 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         out[ns.means_precisions] = _like(ns.means_precisions, acc)
         if isinstance(grp, MixtureSet):
             out.update(grp.weights_accumulate(acc))
+    if learned:
+        out.update(model.transitions.accumulate_counts(tcounts_tot))
     if isinstance(model, BigramPhoneLoop):
         if bigram and counts_tot is None and xi_tot is not None:       # (Viterbi training)
             counts_tot = model.bigram_counts(xi_tot)

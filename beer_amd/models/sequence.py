@@ -9,24 +9,315 @@ import torch
 
 from .. import _hip, hmm_kernels as hk, kernels
 from ..stats import reference_layout_enabled
-from .basemodel import DiscreteLatentModel
+from .basemodel import DiscreteLatentModel, Model
 from .gaussians import NormalSet
 from .modelset import DynamicallyOrderedModelSet
 from .weights import Categorical, CategoricalSet, SBCategorical, SBCategoricalSet
 
-__all__ = ['HMM', 'PhoneLoop', 'BigramPhoneLoop']
+__all__ = ['HMM', 'PhoneLoop', 'BigramPhoneLoop', 'HMMTransitions']
+
+
+class HMMTransitions(Model):
+    '''Learned transition probabilities of the units of an HMM (not in the reference, whose
+    transition probabilities are the constants of conf/hmm.yml).  Every emitting state that
+    owns categories has one per outgoing arc inside its unit, and the unit's end state one
+    more, `exit` (the probability of leaving the unit: the residual of a phone loop's end
+    state).  States are grouped by their number of categories into one `CategoricalSet`
+    (Dirichlet rows) per arity, so that E[ln a], the KL and the update are the existing
+    Dirichlet kernels.  Category c of the flat order (groups in `arities` order, rows, slots)
+    is the arc `cat_src[c]` -> `cat_dst[c]`, or the exit of `cat_src[c]` when `cat_dst[c]`
+    is -1.'''
+
+    @classmethod
+    def create(cls, trans_log_probs, end_states=(), start_states=(), prior_strength=1.):
+        '''From a compiled graph's transition log-probabilities: `end_states` / `start_states`
+        name the units' end / start states (a phone loop's end_pdf / start_pdf values: the
+        block end -> start is not learned); without them every state with an incomplete row
+        owns an exit.  Units are the connected parts of the graph once that block is removed;
+        a unit whose exit is reached from more than one state is refused (ValueError).  Prior
+        concentrations: prior_strength x the graph's transition probabilities.'''
+        trans = trans_log_probs.detach().to('cpu', torch.float64)
+        S = trans.shape[0]
+        ends, starts = [int(i) for i in end_states], [int(i) for i in start_states]
+        if len(set(ends)) != len(ends) or len(set(starts)) != len(starts):
+            raise ValueError('learned transitions need distinct end / start states per unit')
+        if set(ends) & set(starts):
+            raise ValueError('learned transitions need units of at least two emitting states '
+                             '(a unit whose start state is its end state)')
+        intra = torch.isfinite(trans) & (trans.exp() > 0)
+        if ends:
+            intra[torch.as_tensor(ends)[:, None], torch.as_tensor(starts)[None, :]] = False
+        probs = torch.where(intra, trans.exp(), torch.zeros_like(trans))
+        mass = probs.sum(dim=1)
+        exits = set(ends) if ends else {j for j in range(S) if mass[j] < 1 - 1e-6}
+        # units: connected parts of the intra-unit arcs
+        parent = list(range(S))
+
+        def root(i):
+            while parent[i] != i:
+                parent[i] = parent[parent[i]]
+                i = parent[i]
+            return i
+        for i, j in torch.nonzero(intra).tolist():
+            parent[root(i)] = root(j)
+        per_unit = {}
+        for e in exits:
+            per_unit.setdefault(root(e), []).append(e)
+        for r, members in per_unit.items():
+            if len(members) > 1:
+                raise ValueError('learned transitions: a unit whose exit is reached from more '
+                                 f'than one state (states {sorted(members)})')
+        if ends:
+            # every other state of a unit must keep all of its mass inside the unit
+            leak = [j for j in range(S) if j not in exits and mass[j] < 1 - 1e-6 and
+                    bool(torch.isfinite(trans[j]).any())]
+            if leak:
+                raise ValueError('learned transitions: a unit whose exit is reached from more '
+                                 f'than one state (states {leak[:8]} leave their unit)')
+        rows = {}
+        for j in range(S):
+            dsts = torch.nonzero(intra[j]).view(-1).tolist()
+            cats = [(d, float(probs[j, d])) for d in dsts]
+            if j in exits:
+                cats.append((-1, max(float(1 - mass[j]), 0.)))
+            if cats:
+                rows[j] = cats
+        if not rows:
+            raise ValueError('learned transitions: the graph has no arcs to learn')
+        arities = sorted({len(c) for c in rows.values()})
+        sets, src, dst, group_states = [], [], [], []
+        for n in arities:
+            states = [j for j in sorted(rows) if len(rows[j]) == n]
+            w = torch.tensor([[p for _, p in rows[j]] for j in states],
+                             dtype=trans_log_probs.dtype)
+            sets.append(CategoricalSet.create(w, prior_strength))
+            group_states.append(states)
+            for j in states:
+                src += [j] * n
+                dst += [d for d, _ in rows[j]]
+        return cls(sets, arities, group_states, src, dst)
+
+    def __init__(self, categoricalsets, arities, group_states, cat_src, cat_dst):
+        super().__init__()
+        self.categoricalsets = torch.nn.ModuleList(categoricalsets)
+        self.arities = list(arities)
+        self.group_states = [list(g) for g in group_states]
+        self.cat_src, self.cat_dst = list(cat_src), list(cat_dst)
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.pop('_index_memo', None)
+        return state
+
+    # -- categories
+    def parameters_of_groups(self):
+        return [cs.mean_field_factorization()[0][0] for cs in self.categoricalsets]
+
+    def mean_field_factorization(self):
+        'One group of their own: every arity\'s Dirichlet rows.'
+        return [self.parameters_of_groups()]
+
+    def intra(self):
+        '(categories, sources, destinations) of the arcs inside the units.'
+        cats = [c for c, d in enumerate(self.cat_dst) if d >= 0]
+        return cats, [self.cat_src[c] for c in cats], [self.cat_dst[c] for c in cats]
+
+    def exits(self):
+        '{state: category} of the units\' exits.'
+        return {self.cat_src[c]: c for c, d in enumerate(self.cat_dst) if d < 0}
+
+    def index_tensors(self, device, end_states=()):
+        '''int64 tensors on `device`, made once per (device, end states): (intra categories,
+        their sources, their destinations, exit categories, their states, the exit categories
+        of `end_states` in that order).'''
+        key = (str(device), tuple(end_states))
+        memo = self.__dict__.setdefault('_index_memo', {})
+        if key not in memo:
+            cats, src, dst = self.intra()
+            ex = self.exits()
+            missing = [e for e in end_states if e not in ex]
+            if missing:
+                raise ValueError(f'learned transitions: end states {missing} own no exit')
+            t = lambda v: torch.as_tensor(v, dtype=torch.int64, device=device)   # noqa: E731
+            memo[key] = (t(cats), t(src), t(dst), t(list(ex.values())), t(list(ex.keys())),
+                         t([ex[e] for e in end_states]))
+        return memo[key]
+
+    def log_probs(self):
+        'E[ln a] of every category, flat [n_categories] (one Dirichlet kernel per arity).'
+        parts = [cs.log_weights().reshape(-1) for cs in self.categoricalsets]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def expected_probs(self):
+        'E[a] of every category, flat [n_categories].'
+        parts = []
+        for p in self.parameters_of_groups():
+            conc = p.posterior.params.concentrations
+            parts.append((conc / conc.sum(dim=-1, keepdim=True)).reshape(-1))
+        return torch.cat(parts)
+
+    def accumulate_counts(self, counts):
+        '''Statistics of every arity's Dirichlet rows from the counts of every category,
+        flat [n_categories] (any device / dtype).'''
+        out, first = {}, 0
+        for cs, n, states in zip(self.categoricalsets, self.arities, self.group_states):
+            ref = cs.mean_field_factorization()[0][0].posterior.params.concentrations
+            block = counts[first:first + n * len(states)].to(dtype=ref.dtype, device=ref.device)
+            first += n * len(states)
+            cstats = cs.sufficient_statistics(block.view(len(states), n))
+            out.update(cs.accumulate_from_jointresps(cstats[None]))
+        return out
+
+    def counts_from_kernel(self, arc_pos, arc_counts, src_flow):
+        '''Category counts [n_categories] fp64 from the one-wave count kernels' outputs: the
+        intra-unit arcs at their positions `arc_pos` in the low-degree image's arc order, the
+        exits from the source flows.'''
+        cats, _, _, ex_cat, ex_src, _ = self.index_tensors(arc_counts.device)
+        counts = torch.zeros(len(self.cat_src), dtype=torch.float64, device=arc_counts.device)
+        counts[cats] = arc_counts[arc_pos]
+        counts[ex_cat] = src_flow[ex_src]
+        return counts
+
+    def counts_from_dense(self, xi, last):
+        '''Category counts [n_categories] fp64 from a dense xi_sum [S, S] that holds every arc
+        (the general kernel's, or a state path's) and the last frames' posteriors [S]: the
+        arcs inside the units, and an exit = the rest of its state's row + its last frames.'''
+        cats, src, dst, ex_cat, ex_src, _ = self.index_tensors(xi.device)
+        xi = xi.to(torch.float64)
+        inside = xi[src, dst]
+        counts = torch.zeros(len(self.cat_src), dtype=torch.float64, device=xi.device)
+        counts[cats] = inside
+        kept = torch.zeros(xi.shape[0], dtype=torch.float64, device=xi.device).index_add_(
+            0, src, inside)
+        counts[ex_cat] = (xi.sum(dim=1) - kept + last.to(torch.float64))[ex_src]
+        return counts
+
+    # -- Model protocol (the statistics come from the HMM's E-step)
+    def sufficient_statistics(self, data):
+        return data
+
+    def expected_log_likelihood(self, stats):
+        raise NotImplementedError('the transitions are scored inside the HMM\'s E-step')
+
+    def accumulate(self, stats, parent_msg=None):
+        return self.accumulate_counts(stats)
+
+
+def _transitions_of(model):
+    return getattr(model, 'transitions', None)
 
 
 class HMM(DiscreteLatentModel):
-    'Hidden Markov Model with fixed transition probabilities.'
+    '''Hidden Markov Model; its transition probabilities are fixed unless it was created
+    with `train_transitions=True` (`transitions`: `HMMTransitions`, None = fixed).'''
 
     @classmethod
-    def create(cls, graph, modelset):
-        return cls(graph, modelset)
+    def create(cls, graph, modelset, train_transitions=False, transitions_prior_strength=1.):
+        transitions = HMMTransitions.create(graph.trans_log_probs,
+                                            prior_strength=transitions_prior_strength) \
+            if train_transitions else None
+        return cls(graph, modelset, transitions)
 
-    def __init__(self, graph, modelset):
+    def __init__(self, graph, modelset, transitions=None):
         super().__init__(DynamicallyOrderedModelSet(modelset))
         self.graph = graph
+        self.transitions = transitions
+        if transitions is not None:
+            self._attach_transitions()
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            # (models pickled before transitions could be learned, the reference's included)
+            if name == 'transitions':
+                return None
+            raise
+
+    # -- learned transitions --------------------------------------------------------
+    def _attach_transitions(self):
+        for param in self.transitions.parameters_of_groups():
+            param.register_callback(self._on_transitions_update)
+        self._on_transitions_update()
+
+    def _exit_states(self):
+        return ()
+
+    def _write_transitions(self):
+        'trans[i, j] = E[ln a_ij] of every arc inside a unit; returns E[ln a] of every category.'
+        trans = self.graph.trans_log_probs
+        logp = self.transitions.log_probs().to(dtype=trans.dtype, device=trans.device)
+        cats, src, dst = self.transitions.index_tensors(trans.device, self._exit_states())[:3]
+        trans[src, dst] = logp[cats]
+        return logp
+
+    def _on_transitions_update(self):
+        '''The graph's intra-unit transition log-probabilities rewritten with E[ln a] after an
+        update of the transitions; the device image is refreshed in place.'''
+        self._write_transitions()
+        self.graph.weights_rewritten()
+
+    # index arithmetic on device tensors when the graph and the transitions live on the GPU:
+    # the update of the transitions' group may be captured as a HIP graph
+    def _transitions_update_capturable(self):
+        trans = self.graph.trans_log_probs
+        if not trans.is_cuda:
+            return False
+        if not all(p.posterior.params.concentrations.is_cuda
+                   for p in self.transitions.parameters_of_groups()):
+            return False
+        # (what the callbacks index with, and what they share, is made NOW: a host -> device
+        # copy or an allocation inside a recording cannot be kept)
+        self.transitions.index_tensors(trans.device, self._exit_states())
+        self._shared_logs()
+        return True
+
+    def _shared_logs(self):
+        'What the callbacks of two mean-field groups share (PhoneLoop); nothing here.'
+        return None
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.pop('_shared_memo', None)
+        return state
+
+    _on_transitions_update.device_only = _transitions_update_capturable
+
+    def expected_transition_probs(self):
+        '''The learned transition probabilities E[a] (posterior means): ([S, S] fp64 with
+        E[a_ij] on the arcs inside the units, 0 elsewhere; [S] fp64 with every end state's
+        E[a_exit], 0 elsewhere).  ValueError when the transitions are not learned.'''
+        if self.transitions is None:
+            raise ValueError('the transition probabilities of this model are not learned '
+                             '(create it with train_transitions=True)')
+        S = self.graph.n_states
+        probs = self.transitions.expected_probs().detach().to('cpu', torch.float64)
+        cats, src, dst = self.transitions.intra()
+        mat = torch.zeros(S, S, dtype=torch.float64)
+        mat[torch.as_tensor(src, dtype=torch.int64), torch.as_tensor(dst, dtype=torch.int64)] = \
+            probs[torch.as_tensor(cats, dtype=torch.int64)]
+        ex = torch.zeros(S, dtype=torch.float64)
+        for state, c in self.transitions.exits().items():
+            ex[state] = probs[c]
+        return mat, ex
+
+    def transition_counts(self, dgraph, counts):
+        '''Counts of every category of the learned transitions [n_categories] fp64 from what a
+        forward-backward call gave (hmm_kernels: `posteriors_fused(want_transitions=True)`,
+        `forward_backward_counts`, `path_counts`): ('arcs', arc_counts, src_flow) on the
+        device image `dgraph` of the model's graph, or ('dense', xi_sum, last).'''
+        kind, a, b = counts
+        if kind == 'dense':
+            return self.transitions.counts_from_dense(a, b)
+        _, src, dst = self.transitions.intra()
+        pos = dgraph.arc_positions(src, dst)
+        return self.transitions.counts_from_kernel(pos, a, b)
+
+    @staticmethod
+    def _refuse_transitions(what):
+        raise ValueError(f'learned transitions (train_transitions=True) with {what} are not '
+                         'supported: per-utterance graphs would need a category map per '
+                         'compiled arc')
 
     # -- helpers ---------------------------------------------------------------
     def _emissions(self):
@@ -57,7 +348,10 @@ class HMM(DiscreteLatentModel):
 
     # -- Model interface ---------------------------------------------------------
     def mean_field_factorization(self):
-        return self.modelset.mean_field_factorization()
+        mff = self.modelset.mean_field_factorization()
+        if self.transitions is not None:
+            mff = list(mff) + self.transitions.mean_field_factorization()
+        return mff
 
     def sufficient_statistics(self, data):
         return self.modelset.sufficient_statistics(data)
@@ -70,6 +364,10 @@ class HMM(DiscreteLatentModel):
         the reference) treats the frames as that many consecutive utterances,
         each decoded with the same graph, in one ragged batch.'''
         trans_posts = inference_graph is None
+        learned = self.transitions is not None
+        if learned and inference_graph is not None:
+            self._refuse_transitions('alignment graphs (inference_graph)')
+        self.cache.pop('trans_counts', None)
         graph = self.graph if inference_graph is None else inference_graph
         dense = kernels.is_dense(stats)
         emissions = self._emissions()
@@ -97,8 +395,15 @@ class HMM(DiscreteLatentModel):
         if fused:
             # (the per-frame value sum_s gamma l comes out of the same launch)
             exp_llh = torch.empty(T, dtype=pc_all.dtype, device=pc_all.device)
-            state_resps, g0, flow = hk.posteriors_fused(batch, pc_all, scale,
-                                                        want_counts=need_counts, frame_llh=exp_llh)
+            if learned:
+                state_resps, g0, flow, tc = hk.posteriors_fused(
+                    batch, pc_all, scale, want_counts=need_counts, frame_llh=exp_llh,
+                    want_transitions=True)
+                self.cache['trans_counts'] = self.transition_counts(batch.dgraphs[0], tc)
+            else:
+                state_resps, g0, flow = hk.posteriors_fused(batch, pc_all, scale,
+                                                            want_counts=need_counts,
+                                                            frame_llh=exp_llh)
             self.cache.pop('resps', None)
             if trans_posts:
                 self.cache['trans_resps'] = None
@@ -111,6 +416,14 @@ class HMM(DiscreteLatentModel):
         if viterbi or state_path is not None:
             path = hk.viterbi(batch, pc_llhs) if state_path is None else state_path
             gamma, xi, g0 = hk.path_posteriors(batch, path, want_xi=trans_posts)
+            if learned:
+                self.cache['trans_counts'] = self.transition_counts(
+                    batch.dgraphs[0], hk.path_counts(batch, path, xi))
+        elif learned:
+            # forward-backward with the transition counts (one-wave kernels: no dense xi, the
+            # phone counts come from the first-frame posteriors and the hub flows)
+            gamma, g0, flow, xi, tc = hk.forward_backward_counts(batch, pc_llhs)
+            self.cache['trans_counts'] = self.transition_counts(batch.dgraphs[0], tc)
         else:
             per_frame = trans_posts and reference_layout_enabled() and utt_lengths is None
             # (per frame: the general kernel -- log-space forward values, hub arcs in the matrix)
@@ -153,7 +466,10 @@ class HMM(DiscreteLatentModel):
 
     def accumulate(self, stats, parent_msg=None):
         # scale * resps scattered back to pdf ids was produced with the E-step.
-        return {**self._emissions().accumulate(stats, self.cache['scaled_pdf_resps'])}
+        retval = {**self._emissions().accumulate(stats, self.cache['scaled_pdf_resps'])}
+        if self.transitions is not None:
+            retval.update(self.transitions.accumulate_counts(self.cache['trans_counts']))
+        return retval
 
     # -- DiscreteLatentModel interface ------------------------------------------------
     def decode(self, data, inference_graph=None, scale=1.):
@@ -180,22 +496,63 @@ class PhoneLoop(HMM):
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
-               prior_strength=1.0):
+               prior_strength=1.0, train_transitions=False, transitions_prior_strength=1.):
+        '''`train_transitions` (not in the reference): learn the units' transition
+        probabilities too (`HMMTransitions`: Dirichlet rows whose prior concentrations are
+        `transitions_prior_strength` x the graph's transition probabilities).'''
         tensor = modelset.mean_field_factorization()[0][0].prior._tensors()[0]
         if categorical is None:
             weights = torch.ones(len(start_pdf), dtype=tensor.dtype, device=tensor.device)
             weights /= len(start_pdf)
             categorical = Categorical.create(weights, prior_strength)
-        return cls(graph, modelset, start_pdf, end_pdf, categorical)
+        transitions = HMMTransitions.create(
+            graph.trans_log_probs, list(end_pdf.values()), list(start_pdf.values()),
+            transitions_prior_strength) if train_transitions else None
+        return cls(graph, modelset, start_pdf, end_pdf, categorical, transitions)
 
-    def __init__(self, graph, modelset, start_pdf, end_pdf, categorical):
+    def __init__(self, graph, modelset, start_pdf, end_pdf, categorical, transitions=None):
         super().__init__(graph, modelset)
         self.start_pdf = start_pdf
         self.end_pdf = end_pdf
         self.categorical = categorical
+        self.transitions = transitions
         param = self.categorical.mean_field_factorization()[0][0]
         param.register_callback(self._on_weights_update)
-        self._on_weights_update()
+        if transitions is not None:
+            self._attach_transitions()          # (rewrites the exits too: _on_weights_update)
+        else:
+            self._on_weights_update()
+
+    def _exit_states(self):
+        return list(self.end_pdf.values())
+
+    def _on_transitions_update(self):
+        '''Intra-unit entries <- E[ln a], then the phone exits <- E[ln a_exit] + E[ln w]: the
+        graph is the same whichever of the two callbacks the optimizer runs first.'''
+        logp = self._write_transitions()
+        ex, lw = self._shared_logs()
+        end_cats = self.transitions.index_tensors(ex.device, self._exit_states())[5]
+        ex.copy_(logp[end_cats])
+        self._write_exits(ex, lw)
+
+    _on_transitions_update.device_only = HMM._transitions_update_capturable
+
+    def _shared_logs(self):
+        '''(E[ln a_exit] of the phones' end states [P], E[ln w] of the phones [P]) for learned
+        transitions: two tensors on the graph's device that stay where they are.  Each of the
+        two callbacks writes its own group's half in place and reads the other half from here,
+        never the other group's posterior or memo: a HIP graph recorded for one group's update
+        would go on reading those after the other group has replaced them.'''
+        trans = self.graph.trans_log_probs
+        key = (str(trans.device), trans.dtype)
+        memo = self.__dict__.get('_shared_memo')
+        if memo is None or memo[0] != key:
+            end_cats = self.transitions.index_tensors(trans.device, self._exit_states())[5]
+            ex = self.transitions.log_probs().to(dtype=trans.dtype, device=trans.device)[end_cats]
+            lw = self.categorical.log_weights().to(dtype=trans.dtype, device=trans.device).clone()
+            memo = (key, ex, lw)
+            self.__dict__['_shared_memo'] = memo
+        return memo[1], memo[2]
 
     def _index_tensors(self, device):
         '''(end states, start states) of the phones as device index tensors,
@@ -217,11 +574,24 @@ class PhoneLoop(HMM):
         trans = self.graph.trans_log_probs
         log_weights = self.categorical.log_weights().to(dtype=trans.dtype,
                                                         device=trans.device)
+        if self.transitions is not None:
+            # learned transitions: the residual is E[ln a_exit] of the end state, as the
+            # transitions' callback last wrote it
+            residuals, shared_lw = self._shared_logs()
+            shared_lw.copy_(log_weights)
+            self._write_exits(residuals, shared_lw)
+            return
+        ends, starts = self._index_tensors(trans.device)
+        residuals = (1 - trans[ends, ends].exp()).log()
+        self._write_exits(residuals, log_weights)
+
+    def _write_exits(self, residuals, log_weights):
+        'trans[end_i, start_j] = residuals[i] + log_weights[j], then the device image and hub.'
+        trans = self.graph.trans_log_probs
         start_idxs = list(self.start_pdf.values())
         end_idxs = list(self.end_pdf.values())
         # all phones at once (the reference loops over them; same elementwise ops)
         ends, starts = self._index_tensors(trans.device)
-        residuals = (1 - trans[ends, ends].exp()).log()
         if len(set(end_idxs)) == len(end_idxs):
             trans[ends[:, None], starts[None, :]] = residuals[:, None] + log_weights[None, :]
         else:                                    # repeated end states: last write wins
@@ -241,14 +611,19 @@ class PhoneLoop(HMM):
             return False
         # (the index tensors are made NOW: their host -> device copy cannot be recorded)
         self._index_tensors(self.graph.trans_log_probs.device)
+        if self.transitions is not None:
+            return self._transitions_update_capturable()
         return True
 
     _on_weights_update.device_only = _weights_update_capturable
 
     def mean_field_factorization(self):
         from .mixtures import _merge_groups
-        return _merge_groups(self.modelset.mean_field_factorization(),
-                             self.categorical.mean_field_factorization())
+        mff = _merge_groups(self.modelset.mean_field_factorization(),
+                            self.categorical.mean_field_factorization())
+        if self.transitions is not None:
+            mff = mff + self.transitions.mean_field_factorization()
+        return mff
 
     def phone_counts(self, xi_sum, gamma0, hub_flow=None):
         '''sum_t xi_t[ends, starts] summed over ends + gamma_0[starts] (88-95).
@@ -296,7 +671,10 @@ class BigramPhoneLoop(HMM):
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,
-               prior_strength=1.0):
+               prior_strength=1.0, train_transitions=False):
+        if train_transitions:
+            raise ValueError('learned transitions (train_transitions=True) are not supported '
+                             'on a bigram phone loop: its kernel does not count them')
         tensor = modelset.mean_field_factorization()[0][0].prior._tensors()[0]
         if categoricalset is None:
             weights = torch.ones(len(start_pdf), len(start_pdf), dtype=tensor.dtype,

@@ -607,6 +607,44 @@ int beer_hmm_posteriors_fused(int dtype, const beer_batch* batch_h, int S_total,
                               double* gamma0_sum, double* hub_flow, double* utt_llh,
                               void* frame_llh, void* stream);
 
+/* Transition counts for LEARNED transition probabilities (HMM / PhoneLoop created with
+ * train_transitions=True; an extension: the reference's transition probabilities are constants
+ * copied from conf/hmm.yml, beer/cli/subcommands/hmm/mkphones.py:12-43, and only the phone weights
+ * are re-estimated, beer/models/phoneloop.py:53-65).  Batches whose utterances all use ONE graph
+ * (n_graphs == 1) of the kind the one-wave kernels take (see above); the recursions, and every
+ * other output, are those of beer_hmm_posteriors_fused / beer_hmm_forward_backward, bit for bit,
+ * and the log-space twin gives the same counts for the utterances it takes over.
+ *   arc_counts  [n_arcs of the graph's lowdeg image] fp64, +=: sum over utterances and frames of
+ *               the transition posteriors xi_t(i, j) of every arc of the low-degree image, in its
+ *               out-CSR order (by source, destinations ascending; hub arcs are not in it):
+ *               graph.py:308-323 summed over t, restricted to those arcs.
+ *   src_flow    [S] fp64, +=: the expected exits of every state -- its transition posteriors
+ *               into the hub summed over the hub's destinations (phoneloop.py:88-95 counts the
+ *               same arcs by destination), plus its posterior at the last frame of every
+ *               utterance (the utterance ends by leaving it; 0 where the final weight is 0).
+ * EINVAL when the batch is not of that kind or an output is NULL. */
+int beer_hmm_posteriors_fused_counts(int dtype, const beer_batch* batch_h, int S_total,
+                                     const void* pc_all, double scale, double* alpha_ws,
+                                     double* hub_ws, void* state_resps, int atomic_out,
+                                     double* gamma0_sum, double* hub_flow, double* utt_llh,
+                                     void* frame_llh, double* arc_counts, double* src_flow,
+                                     void* stream);
+/* The same two outputs from beer_hmm_forward_backward's one-wave path (packed pc_llhs / gamma,
+ * graph.py:270-326): the dense xi_sum is replaced by `arc_counts` / `src_flow`. */
+int beer_hmm_forward_backward_counts(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                                     double* alpha_ws, double* hub_ws, void* gamma,
+                                     double* gamma0_sum, double* hub_flow, double* arc_counts,
+                                     double* src_flow, void* lognorm_mean, void* stream);
+
+/* The general path of the same counts, for every graph beer_hmm_forward_backward takes (more
+ * than 256 states, hubs of more than 64 phones): its dense xi_sum with the hub arcs in the matrix
+ * (the batch's lowdeg flag cleared) gives the arcs and, row by row, the exits; what it lacks is
+ * the end-of-utterance exit, the posteriors of every utterance's last frame:
+ * out [S] fp64 (+=) = sum_u gamma_u[T_u - 1, :] (gamma packed as beer_hmm_forward_backward
+ * leaves it; graph.py:304-307 at t = T - 1).  n_graphs must be 1. */
+int beer_hmm_last_frame_sum(int dtype, const beer_batch* batch_h, const void* gamma, double* out,
+                            void* stream);
+
 /* A phone loop with a BIGRAM language model (beer/models/phoneloop.py:104-191):
  * its end -> start block trans[src[i], dst[j]] = ln(1 - loop_i) + E[ln w][i, j] is a
  * full P x P matrix, kept apart from the rest of the graph (a low-degree CSR: the
