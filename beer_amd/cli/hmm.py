@@ -6,6 +6,7 @@ utterances as ONE ragged batch on the GPU instead of a Python loop."""
 import os
 import pickle
 import sys
+import warnings
 
 import numpy as np
 import torch
@@ -90,6 +91,19 @@ def build_units(groups_conf, grouped_names, mean, var):
             units[name] = topo.graph(next_pdf)
             next_pdf += topo.n_emitting
         n_states = topo.n_emitting * len(names)
+        pool = conf.get('shared_normal_pool')
+        if pool:
+            # (not in the reference) the group's states share ONE pool of `pool` Gaussians and
+            # differ in their mixture weights only: a tied-mixture group
+            if 'n_normal_per_state' in conf:
+                warnings.warn(f'group {group!r}: n_normal_per_state is ignored, its states share '
+                              f'a pool of {int(pool)} Gaussians (shared_normal_pool)', stacklevel=2)
+            normals = beer.NormalSet.create(
+                mean=mean, cov=var, size=int(pool), prior_strength=conf['prior_strength'],
+                noise_std=conf['noise_std'], cov_type=conf['cov_type'])
+            sets.append(beer.TiedMixtureSet.create(n_states, normals,
+                                                   prior_strength=conf['prior_strength']))
+            continue
         normals = beer.NormalSet.create(
             mean=mean, cov=var, size=n_states * conf['n_normal_per_state'],
             prior_strength=conf['prior_strength'], noise_std=conf['noise_std'],

@@ -422,6 +422,21 @@ class Dirichlet(ExponentialFamily):
         stats @ E[T]` of Mixture._log_weights (mixture.py:45-48) in one call.'''
         return self._memoised('logw', lambda: self._launch('beer_dirichlet_log_weights'))
 
+    def log_weights64(self):
+        '''`log_weights` in float64 whatever the distribution's dtype, from the concentrations
+        as they are: E[ln pi] of a category nobody uses is about -1 / concentration, and
+        float32 holds -130 to 8e-6 only (tied mixtures: the responsibilities inherit it).'''
+        c = self.params.concentrations
+        if c.dtype == torch.float64:
+            return self.log_weights()
+
+        def compute():
+            c2 = c.double().reshape(1, -1) if c.dim() <= 1 else c.double()
+            out = _empty(tuple(c2.shape), c2, torch.float64)
+            _run('beer_dirichlet_log_weights', torch.float64, tuple(c2.shape), (c2,), (out,))
+            return out.to(c.device).view(c.shape)
+        return self._memoised('logw64', compute)
+
     def expected_value(self):
         c = self.params.concentrations
         return c / c.sum(dim=-1, keepdim=True)

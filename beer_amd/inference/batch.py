@@ -24,7 +24,7 @@ import torch
 
 from .. import _hip, hmm_kernels as hk, kernels
 from ..models.gaussians import NormalSet
-from ..models.mixtures import Mixture, MixtureSet
+from ..models.mixtures import Mixture, MixtureSet, TiedMixtureSet
 from ..models.modelset import JointModelSet
 from ..models.sequence import HMM, BigramPhoneLoop, PhoneLoop
 from ..models.vae import VAE
@@ -109,8 +109,10 @@ def pack_utterances(utterances):
 
 
 def _groups(emissions):
-    '''Flatten an emission model into [(MixtureSet | NormalSet, S, G)].  A nested
-    MixtureSet is one group of S mixtures of its G leaves (`MixtureSet.leaf_log_weights`).'''
+    '''Flatten an emission model into [(MixtureSet | TiedMixtureSet | NormalSet, S, G)].  A
+    nested MixtureSet is one group of S mixtures of its G leaves
+    (`MixtureSet.leaf_log_weights`); a TiedMixtureSet one of S mixtures of the G = K Gaussians
+    of its pool, which it does not own S times: `_n_gaussians`.'''
     if isinstance(emissions, JointModelSet):
         out = []
         for m in emissions.modelsets:
@@ -118,13 +120,20 @@ def _groups(emissions):
         return out
     if isinstance(emissions, MixtureSet):
         return [(emissions, len(emissions), emissions.n_leaves_per_mixture)]
+    if isinstance(emissions, TiedMixtureSet):
+        return [(emissions, len(emissions), len(emissions.modelset))]
     if isinstance(emissions, NormalSet):
         return [(emissions, len(emissions), 1)]
     raise NotImplementedError(f'unsupported emission model {type(emissions).__name__}')
 
 
 def _normalset(group):
-    return group.normalset if isinstance(group, MixtureSet) else group
+    return group.normalset if isinstance(group, (MixtureSet, TiedMixtureSet)) else group
+
+
+def _n_gaussians(group, S, G):
+    'Rows of the group\'s Gaussian statistics: S x G, or the K of a tied group\'s one pool.'
+    return G if isinstance(group, TiedMixtureSet) else S * G
 
 
 def _sub_batches(lengths, bytes_per_frame, max_frames):
@@ -308,8 +317,14 @@ def _emission_estep(groups, stats, dtype, for_accumulate=False):
     cols, comps = [], []
     for grp, S, G in groups:
         ns = _normalset(grp)
-        lw = grp.leaf_log_weights() if isinstance(grp, MixtureSet) else None
         gstats = stats.as_cov(ns.cov_type)
+        if isinstance(grp, TiedMixtureSet):
+            # the pool's K log-likelihoods once, the S columns by `beer_tied_lognorm`
+            tied = grp.estep(gstats)
+            cols.append(tied[2])
+            comps.append(('tied',) + tied)
+            continue
+        lw = grp.leaf_log_weights() if isinstance(grp, MixtureSet) else None
         fused = for_accumulate and G > 1 and \
             kernels.fused_accumulate_ok(gstats, S, G, ns.cov_type)
         if for_accumulate and G > 1 and not fused and \
@@ -334,14 +349,16 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     emissions = model._emissions()
     groups = _groups(emissions)
     S_total = sum(S for _, S, _ in groups)
-    K_max = sum(S * G for _, S, G in groups)
     dev, dtype = X.device, X.dtype
     free_loop = graphs is None
-    accs = []
+    accs, tied_counts = [], []
     for grp, S, G in groups:
         ns = _normalset(grp)
         Q = FrameStats(X[:1], ns.cov_type).shape[1]
-        accs.append(torch.zeros(S * G, Q, dtype=torch.float64, device=dev))
+        accs.append(torch.zeros(_n_gaussians(grp, S, G), Q, dtype=torch.float64, device=dev))
+        # a tied group's weight statistics do not follow from its Gaussians': [S, K] of their own
+        tied_counts.append(torch.zeros(S, G, dtype=torch.float64, device=dev)
+                      if isinstance(grp, TiedMixtureSet) else None)
     nutt = len(lengths)
     utt_llh = torch.zeros(nutt, dtype=torch.float64, device=dev)
 
@@ -366,8 +383,11 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     max_S = model.graph.n_states if free_loop else max(g.n_states for g in graphs)
     # scratch per frame: the responsibilities of the groups whose accumulation does
     # not recompute them, per-state likelihoods / posteriors, the trellis
-    K_scratch = sum(S * G for grp, S, G in groups if G > 1 and not kernels.fused_accumulate_ok(
-        FrameStats(X, _normalset(grp).cov_type), S, G, _normalset(grp).cov_type))
+    # (a tied group: the pool's log-likelihoods and responsibilities, 2 K)
+    K_scratch = sum(2 * G if isinstance(grp, TiedMixtureSet) else S * G
+                    for grp, S, G in groups
+                    if isinstance(grp, TiedMixtureSet) or (G > 1 and not kernels.fused_accumulate_ok(
+                        FrameStats(X, _normalset(grp).cov_type), S, G, _normalset(grp).cov_type)))
     bpf = (K_scratch + 2 * S_total) * X.element_size() + max_S * (3 * X.element_size() + 8)
     if bigram:
         model.declare_block()
@@ -429,7 +449,7 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
             sr, counts = hk.posteriors_bigram(batch, pc_all, scale,
                                               utt_llh=utt_llh[run[0]:run[-1] + 1])
             counts_tot = counts if counts_tot is None else counts_tot + counts
-            _accumulate_emissions(groups, comps, accs, sr, stats)
+            _accumulate_emissions(groups, comps, accs, sr, stats, tied_counts)
             done.record()
             continue
         # phone counts come from the flows through the loop's hub (the eliminated
@@ -479,15 +499,17 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                 g0_tot = g0 if g0_tot is None else g0_tot + g0
             if flow is not None:
                 flow_tot = flow if flow_tot is None else flow_tot + flow
-        _accumulate_emissions(groups, comps, accs, sr, stats)
+        _accumulate_emissions(groups, comps, accs, sr, stats, tied_counts)
         done.record()
     value_terms = (scales * utt_llh).sum()
     out = {}
-    for (grp, S, G), acc in zip(groups, accs):
+    for (grp, S, G), acc, cnt in zip(groups, accs, tied_counts):
         ns = _normalset(grp)
         out[ns.means_precisions] = _like(ns.means_precisions, acc)
         if isinstance(grp, MixtureSet):
             out.update(grp.weights_accumulate(acc))
+        elif isinstance(grp, TiedMixtureSet):
+            out.update(grp.weights_accumulate(cnt))
     if learned:
         out.update(model.transitions.accumulate_counts(tcounts_tot))
     if isinstance(model, BigramPhoneLoop):
@@ -511,15 +533,20 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     return value_terms, out
 
 
-def _accumulate_emissions(groups, comps, accs, sr, stats):
-    'The emissions\' statistics of a sub-batch from its posteriors at the pdf ids.'
+def _accumulate_emissions(groups, comps, accs, sr, stats, counts=None):
+    '''The emissions' statistics of a sub-batch from its posteriors at the pdf ids (`counts`:
+    per group, the [S, K] weight counts of a tied one).'''
     first = 0
-    for (grp, S, G), comp, acc in zip(groups, comps, accs):
+    for n, ((grp, S, G), comp, acc) in enumerate(zip(groups, comps, accs)):
         ns = _normalset(grp)
         sr_g = sr if len(groups) == 1 else sr[:, first:first + S].contiguous()
         first += S
         gstats = stats.as_cov(ns.cov_type)
-        if G == 1:
+        if isinstance(grp, TiedMixtureSet):
+            # pool responsibilities [T, K] + weight counts, then the pool as K Gaussians
+            r, _ = kernels.tied_accumulate(*comp[1:], sr_g, counts=counts[n])
+            kernels.normal_accumulate(gstats, r, None, G, 1, ns.cov_type, acc=acc)
+        elif G == 1:
             kernels.normal_accumulate(gstats, sr_g, None, S, 1, ns.cov_type, acc=acc)
         elif isinstance(comp, tuple):
             # responsibilities recomputed inside the accumulation: no [T, K] matrix
@@ -607,7 +634,7 @@ def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=
     X, lengths = pack_utterances(utterances)
     groups = _groups(model._emissions())
     S_total = sum(S for _, S, _ in groups)
-    K_max = sum(S * G for _, S, G in groups)
+    K_max = sum(2 * G if isinstance(grp, TiedMixtureSet) else S * G for grp, S, G in groups)
     off = [0]
     for T in lengths:
         off.append(off[-1] + T)

@@ -12,6 +12,7 @@ from . import _hip
 from .stats import FrameStats
 
 __all__ = ['normal_llh', 'mixtureset_estep', 'normal_accumulate', 'weights_from_acc',
+           'tied_lognorm', 'tied_accumulate',
            'is_dense', 'dense_llh', 'dense_softmax', 'dense_accumulate', 'rowdot',
            'attach_stats_grad', 'differentiable_stats', 'sample_stats', 'attach_frame_grad',
            'frames_llh_backward', 'normal_llh_autograd']
@@ -422,6 +423,74 @@ def weights_from_acc(acc, S, G):
     out = torch.zeros(S, G, dtype=torch.float64, device=acc.device)
     _hip.call('beer_weights_from_acc', S, G, acc.shape[1], _hip.ptr(acc), _hip.ptr(out))
     return out
+
+
+# ---- tied mixtures: S sets of weights over one pool of K Gaussians --------------
+
+_tied_counters = {}
+
+
+def tied_log_counter(device):
+    '''The int64 device scalar the models' `tied_lognorm` calls count their log-space entries
+    in (one per device, for the life of the process; `tied_log_entries` reads it).'''
+    device = torch.device(device)
+    if device not in _tied_counters:
+        _tied_counters[device] = torch.zeros((), dtype=torch.int64, device=device)
+    return _tied_counters[device]
+
+
+def tied_log_entries(device=None):
+    '''How many (frame, state) entries of tied mixtures were redone in log space on `device`
+    so far (a host read-back: for tests and diagnostics, not for the training loop).'''
+    device = _hip.require_device() if device is None else torch.device(device)
+    return int(tied_log_counter(device))
+
+
+def tied_lognorm(pool_llh, log_weights, log_count=None):
+    '''(pc [T,S], m [T]): pc[t,s] = logsumexp_k(pool_llh[t,k] + log_weights[s,k]) and the row
+    maxima of `pool_llh` (`beer_tied_lognorm`).  The log-weights go to the kernels in fp64
+    whatever the dtype of `pool_llh` (`Dirichlet.log_weights64`).  `log_count`: optional int64 device scalar,
+    += the entries that were redone in log space (include/beer_hip.h).'''
+    l = _hip.on_device(pool_llh)
+    lw = _hip.on_device(log_weights, torch.float64)
+    T, K = l.shape
+    S = lw.shape[0]
+    if lw.dim() != 2 or lw.shape[1] != K:
+        raise ValueError(f'log-weights {tuple(lw.shape)} over a pool of {K} Gaussians')
+    if log_count is not None and (log_count.dtype != torch.int64 or not log_count.is_cuda):
+        raise TypeError('log_count: an int64 tensor on the GPU')
+    pc = torch.empty(T, S, dtype=l.dtype, device=l.device)
+    m = torch.empty(T, dtype=l.dtype, device=l.device)
+    _hip.call('beer_tied_lognorm', _hip.dtype_code(l.dtype), T, K, S, _hip.ptr(l), _hip.ptr(lw),
+              _hip.ptr(pc), _hip.ptr(m), _hip.ptr(log_count))
+    return pc, m
+
+
+def tied_accumulate(pool_llh, m, pc, log_weights, state_resps, counts=None):
+    '''(r [T,K], counts [S,K] fp64): with j[t,s,k] = state_resps[t,s] * exp(pool_llh[t,k] +
+    log_weights[s,k] - pc[t,s]), r = sum_s j (the pool's responsibilities) and
+    counts += sum_t j (`beer_tied_accumulate`); `m`, `pc` as `tied_lognorm` returned them.'''
+    l = _hip.on_device(pool_llh)
+    lw = _hip.on_device(log_weights, torch.float64)
+    T, K = l.shape
+    S = lw.shape[0]
+    mm, norm = _hip.on_device(m, l.dtype), _hip.on_device(pc, l.dtype)
+    g = _hip.on_device(state_resps, l.dtype)
+    if tuple(lw.shape) != (S, K) or tuple(mm.shape) != (T,) or tuple(norm.shape) != (T, S) or \
+            tuple(g.shape) != (T, S):
+        raise ValueError(f'tied accumulation over {T} frames, {S} states, {K} Gaussians: got '
+                         f'lw {tuple(lw.shape)}, m {tuple(mm.shape)}, pc {tuple(norm.shape)}, '
+                         f'state_resps {tuple(g.shape)}')
+    if counts is None:
+        counts = torch.zeros(S, K, dtype=torch.float64, device=l.device)
+    elif counts.dtype != torch.float64 or tuple(counts.shape) != (S, K) or \
+            not counts.is_contiguous():
+        raise ValueError(f'counts: contiguous fp64 [{S}, {K}]')
+    r = torch.empty(T, K, dtype=l.dtype, device=l.device)
+    _hip.call('beer_tied_accumulate', _hip.dtype_code(l.dtype), T, K, S, _hip.ptr(l),
+              _hip.ptr(mm), _hip.ptr(norm), _hip.ptr(lw), _hip.ptr(g), _hip.ptr(r),
+              _hip.ptr(counts))
+    return r, counts
 
 
 # ---- dense ("stats-in") statistics: the prior of a VAE ------------------------

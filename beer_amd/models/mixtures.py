@@ -13,6 +13,11 @@ as the flat mixture over their leaves: a leaf's log-weight is the sum of its
 ancestors' E[ln pi], the softmax over all leaves gives the value and the joint
 responsibilities, and every level's weight statistics are sums of the leaf counts
 over its subtrees ("Nested mixtures").  The same kernels run.
+
+`TiedMixtureSet` (no reference counterpart): S mixtures that share ONE pool of K Gaussians
+and differ in their weights only -- the pool is evaluated once per frame, and what is
+state-specific are three [T, K] x [K, S]-shaped products (`beer_tied_lognorm`,
+`beer_tied_accumulate`; DESIGN.md, "Tied mixtures").
 """
 
 import torch
@@ -23,7 +28,7 @@ from .gaussians import NormalSet
 from .modelset import ModelSet
 from .weights import Categorical, CategoricalSet, SBCategorical, SBCategoricalSet
 
-__all__ = ['Mixture', 'MixtureSet']
+__all__ = ['Mixture', 'MixtureSet', 'TiedMixtureSet']
 
 
 def _merge_groups(l1, l2):
@@ -357,4 +362,86 @@ class MixtureSet(ModelSet):
             step = 1 if key.step is None else key.step * ncpm
             return self.__class__(self.categoricalset[key],
                                   self.modelset[slice(start, stop, step)])
+        raise IndexError(f'Unsupported index: {key}')
+
+
+class TiedMixtureSet(ModelSet):
+    '''Set of S mixtures over the SAME K Gaussians (a tied-mixture / semi-continuous
+    emission model): `modelset` is one `NormalSet`, the pool, and `categoricalset` holds a
+    Dirichlet row of K weights per mixture.'''
+
+    @classmethod
+    def create(cls, size, modelset, prior_strength=1.):
+        if not isinstance(modelset, NormalSet):
+            raise NotImplementedError('the pool of a TiedMixtureSet must be a NormalSet, got '
+                                      f'{type(modelset).__name__}')
+        tensor = modelset.mean_field_factorization()[0][0].prior._tensors()[0]
+        K = len(modelset)
+        weights = torch.full((size, K), 1. / K, dtype=tensor.dtype, device=tensor.device)
+        return cls(CategoricalSet.create(weights, prior_strength), modelset)
+
+    def __init__(self, categoricalset, modelset):
+        super().__init__()
+        if categoricalset.weights.posterior.params.concentrations.shape[-1] != len(modelset):
+            raise ValueError('a TiedMixtureSet needs one weight per Gaussian of the pool')
+        self.categoricalset = categoricalset
+        self.modelset = modelset
+
+    @property
+    def normalset(self):
+        'The shared pool.'
+        return self.modelset
+
+    def _log_weights(self, tensorconf=None):
+        'E[ln pi] [S, K] in float64 whatever the model\'s dtype (`Dirichlet.log_weights64`).'
+        return self.categoricalset.weights.posterior.log_weights64()
+
+    def mean_field_factorization(self):
+        return _merge_groups(self.modelset.mean_field_factorization(),
+                             self.categoricalset.mean_field_factorization())
+
+    def sufficient_statistics(self, data):
+        return self.modelset.sufficient_statistics(data)
+
+    def estep(self, stats):
+        '''(l [T, K], m [T], pc [T, S], lw [S, K]): the pool's expected log-likelihoods, their
+        row maxima, the mixtures' log-normalisers and the E[ln pi] they were computed with --
+        what `kernels.tied_accumulate` takes.'''
+        if kernels.is_dense(stats):
+            raise NotImplementedError('TiedMixtureSet takes frames, not dense statistics (the '
+                                      'prior of a VAE): not supported')
+        ns = self.modelset
+        pool = kernels.normal_llh(stats, ns.means_precisions.natural_form(), ns.cov_type)
+        lw = self._log_weights()
+        pc, m = kernels.tied_lognorm(pool, lw, kernels.tied_log_counter(pool.device))
+        return pool, m, pc, lw
+
+    def expected_log_likelihood(self, stats):
+        'Per-state mixture log-normaliser [T, S]; caches what `accumulate` needs.'
+        tied = self.estep(stats)
+        self.cache['tied'] = tied
+        return tied[2]
+
+    def weights_accumulate(self, counts):
+        '{weights parameter: statistics} from the counts C [S, K] (last column <- row sum).'
+        return _weight_stats(self.categoricalset, counts)
+
+    def accumulate(self, stats, resps):
+        'State posteriors [T, S] -> statistics of the weights and of the pool.'
+        if kernels.is_dense(stats):
+            raise NotImplementedError('TiedMixtureSet takes frames, not dense statistics')
+        ns = self.modelset
+        r, counts = kernels.tied_accumulate(*self.cache['tied'], resps)
+        acc = kernels.normal_accumulate(stats, r, None, len(ns), 1, ns.cov_type)
+        return {**self.weights_accumulate(counts),
+                ns.means_precisions: _like(ns.means_precisions, acc)}
+
+    def __len__(self):
+        return len(self.categoricalset)
+
+    def __getitem__(self, key):
+        if isinstance(key, int):
+            return Mixture(self.categoricalset[key], self.modelset)
+        if isinstance(key, slice):
+            return self.__class__(self.categoricalset[key], self.modelset)
         raise IndexError(f'Unsupported index: {key}')

@@ -431,6 +431,38 @@ int beer_frame_image(int cov, int64_t T, int D, const float* X, void* image,
 int beer_weights_from_acc(int S, int G, int Q, const double* acc,
                           double* out /*[S,G] +=*/, void* stream);
 
+/* Tied-mixture (semi-continuous) emissions: S mixtures over ONE pool of K Gaussians that
+ * differ in their weights only (no reference counterpart: the reference's MixtureSet,
+ * beer/models/mixtureset.py:22-133, gives every mixture its own components; what is
+ * replaced is its cat / logsumexp / exp sequence, mixtureset.py:84-103, for weights of
+ * shape [S, K] over shared components).  `l` [T,K] are the pool's expected
+ * log-likelihoods (beer_mixtureset_estep with S = K, G = 1), `lw` [S,K] the E[ln pi] in
+ * fp64 whatever `dtype` is (float32 holds the -130 of an unused component to 8e-6 only, an
+ * error the responsibilities would inherit).
+ *   pc [T,S]   = logsumexp_k(l[t,k] + lw[s,k])
+ *   m  [T]     = max_k l[t,k] (0 for a row without a finite entry)
+ * computed as m + ln(E W^T), e = exp(l - m), w = exp(lw), on the matrix cores (exact fp32
+ * / fp64 MFMA).  An entry whose linear-domain sum p = sum_k e w is below 2^-94 (float32) /
+ * 2^-970 (float64) -- where terms lost to underflow could cost more than 2^-20 / 2^-40 of
+ * it; derivation in csrc/tied.hip -- is redone in log space; `log_count` (nullable,
+ * device, +=) receives the number of such entries.  K <= 4096, else BEER_EINVAL. */
+int beer_tied_lognorm(int dtype, int64_t T, int K, int S, const void* l, const double* lw,
+                      void* pc, void* m, int64_t* log_count, void* stream);
+/* The statistics of the same model from the state posteriors `g` [T,S] (times the
+ * acoustic scale, as MixtureSet.accumulate receives them, mixtureset.py:105-117), with
+ * j[t,s,k] = g[t,s] exp(l[t,k] + lw[s,k] - pc[t,s]) never stored:
+ *   r [T,K] (of dtype, stored)  = sum_s j   responsibilities of the pool, for
+ *                                 beer_normal_accumulate
+ *   C [S,K] (fp64, +=)          = sum_t j   counts of the weights' Dirichlet rows
+ * as E o (Q W) and W o (Q^T E), q = g / p, p = exp(pc - m); E is recomputed from `l` and
+ * `m` (beer_tied_lognorm's outputs).  q of an entry with g = 0 is 0; an entry below the
+ * threshold above has q = 0 in the products and its j added in log space afterwards
+ * (normalised by its own fp64 logsumexp, not by the stored pc).
+ * Workgroups sum at most 4096 frames in dtype before their partial C meet in fp64. */
+int beer_tied_accumulate(int dtype, int64_t T, int K, int S, const void* l, const void* m,
+                         const void* pc, const double* lw, const void* g, void* r, double* C,
+                         void* stream);
+
 /* ------------------------------------------------------------------------
  * HMM inference over a ragged batch of utterances
  * ---------------------------------------------------------------------- */
