@@ -33,32 +33,6 @@
 #include "estep_mfma.h"
 #include "estep_tiles.h"
 
-// Timing experiments (tools/ab_build.sh; all but 0 give wrong results):
-#ifndef BEER_K1_ABL
-#define BEER_K1_ABL 0      // K1: 1 = no fragment arithmetic, 2 = and no parameter loads, 3 = and no epilogue
-#endif
-#ifndef BEER_K2_ABL
-#define BEER_K2_ABL 0      // K2: 1 = no B fragments, 2 = and no A loads, 3 = and no atomics
-#endif
-#ifndef BEER_AF_ABL
-#define BEER_AF_ABL 0      // fused accumulation, bits: 1 no flush, 8 no exp / split, 16 no statistics B fragments,
-#endif                     // 32 no logit A fragments, 64 no tile skipping
-#ifndef BEER_AFI_ABL
-#define BEER_AFI_ABL 0     // accfi_kernel, bits: 1 one B fragment load per tile, 2 no flush, 4 one A fragment load per tile
-#endif
-#ifndef BEER_LNFI_ABL
-#define BEER_LNFI_ABL 0     // lnfi_kernel, bits: 1 no epilogue, 2 no MFMAs, 4 no LDS reads of B, 8 no A loads
-#endif
-#ifndef BEER_LNFI_SLEEP
-#define BEER_LNFI_SLEEP 0   // lnfi_kernel: s_sleep count (x 64 cycles) of the second wave of every SIMD at its start
-#endif
-#ifndef BEER_ACCFI_SLEEP
-#define BEER_ACCFI_SLEEP 0  // accfi_kernel: the same
-#endif
-#ifndef BEER_K1_FENCE
-#define BEER_K1_FENCE 0    // K1: scheduling fence every n MFMAs of the hand-placed stream (0 = none)
-#endif
-
 namespace beer_mfma {
 
 namespace {
@@ -88,13 +62,12 @@ __device__ __forceinline__ bf8 as_bf8(const u4& w) { return __builtin_bit_cast(b
 __device__ __forceinline__ f32x4 mfma_bf16(const u4& a, const u4& b, const f32x4& c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf8(a), as_bf8(b), c, 0, 0, 0);
 }
-// The same MFMA with its accumulator tied IN PLACE to an AGPR quad.  A kernel with 256
-// accumulators (64 x 256 or 128 x 128 per wave, one wave per SIMD) fills the AGPR half
-// of the register file exactly; given the builtin, hipcc's allocator treats
-// accumulators and fragments as one "any vector register" class and shuffles them
-// between the two halves -- 0.55 v_accvgpr_* per MFMA and, in K2, 110 scratch accesses
-// per tile pair (tools/isa_stats.py).  With "+a" / "v" constraints nothing moves.  What
-// hipcc then no longer does is pad hazards around the instruction
+// The same MFMA with its accumulator tied IN PLACE to an AGPR quad.  K2's 256
+// accumulators (128 x 128 per wave, one wave per SIMD) fill the AGPR half of the register
+// file exactly; given the builtin, hipcc's allocator treats accumulators and fragments as
+// one "any vector register" class and shuffles them between the two halves -- 110 scratch
+// accesses per tile pair (tools/isa_stats.py).  With "+a" / "v" constraints nothing moves.
+// What hipcc then no longer does is pad hazards around the instruction
 // (cdna_hip_programming.md section 5.7): FIRST = the fragment operands may have been
 // written by the VALU instruction just before (2 wait states), and the accumulators
 // must not be read before mfma_drain().  Dependent MFMAs of an accumulation chain need
@@ -105,14 +78,6 @@ __device__ __forceinline__ void mfma_bf16_pinned(f32x4& acc, const u4& a, const 
         asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
     else
         asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-// ... and with the accumulator in a VGPR quad (accumulators that VALU code reads next)
-template <bool FIRST>
-__device__ __forceinline__ void mfma_bf16_pinned_v(f32x4& acc, const u4& a, const u4& b) {
-    if (FIRST)
-        asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-    else
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 // after the last pinned MFMA, before anything reads an accumulator
 __device__ __forceinline__ void mfma_drain() {
@@ -355,11 +320,8 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ X, int64_t 
 
 // ---------------------------------------------------------------------------
 // K1 on the bf16 pipes: one wave owns 16 MT frames x 16 NT components (a chunk of
-// the K components: blockIdx via xcd_block when there are several).  The large
-// form (MT = 4, NT = 16: 64 frames x 256 components, 256 accumulators, one wave per
-// SIMD) builds every A fragment once for 256 components: the fragment arithmetic
-// (4 products + 4.5 VALU per element for the three-way split) is what the fp16
-// two-piece kernel of round 2 was bound by, with half the MFMAs per element.
+// the K components: blockIdx via xcd_block when there are several), at most 128
+// accumulators, two waves per SIMD.
 // A fragments are built one k-step ahead, in slices between the MFMA batches; B
 // fragments (three 16-byte loads per tile from the packed image) one batch of BT
 // tiles ahead.
@@ -378,12 +340,13 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ X, int64_t 
 // for the own DMA, barrier, refill the buffer that has just been read out.  A wave that waits
 // at the barrier leaves the matrix pipe to the wave of the other workgroup on its SIMD.
 template <int NT, int MT, int GQ, bool PACKED, bool SQ, bool LNO, bool IMG = false, bool BL = false>
-__global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
+__global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
     int64_t nframes, int D, int K, int S, int G, int gl, int jw, int nk,
     const float* __restrict__ X, const u4* __restrict__ Pall, const int* __restrict__ tab,
     float* __restrict__ resps, float* __restrict__ log_norm, double* __restrict__ llh_sum,
     float* __restrict__ xt_out, int xt_floats, int nku, int cg, const float* __restrict__ c0,
     const u4* __restrict__ img = nullptr) {
+    static_assert(MT * NT <= 32, "128 accumulators: two waves per SIMD (launch bounds)");
     static_assert(!IMG || (MT == 2 && !PACKED && LNO), "the image holds 32-frame tiles");
     static_assert(!BL || (NT == 16 && MT == 2 && !IMG), "half k-steps of 8 tiles, hipcc-scheduled form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -393,7 +356,6 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
     constexpr int FW = 16 * MT, NW = kThreads / 64;
-    constexpr bool PIN = MT * NT > 32;                        // 256 accumulators: see mfma_bf16_pinned
     float* xw = reinterpret_cast<float*>(smem) + wave * (FW * LD);
     int* tabs = reinterpret_cast<int*>(reinterpret_cast<float*>(smem) + NW * FW * LD);
     // (BL) the ring of two half-k-step buffers behind the slab table, 1 KiB aligned
@@ -521,68 +483,6 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
         __builtin_amdgcn_s_barrier();
     };
     auto batch = [&](int s, int bi, const AFrag& cur, AFrag& nxt, const BFrag& b, BFrag& bn) {
-        if constexpr (PIN) {
-            // Hand-placed stream: one wave per SIMD issues in order, so whatever is not
-            // interleaved with the MFMAs runs while the matrix pipe idles (the block form
-            // below measured 52 % MFMA busy).  48 pinned MFMAs, each followed by at most
-            // one filler: the 6 loads of the next B batch, then ONE half A fragment of the
-            // next k-step -- table entry, 2 LDS reads, 4 products, 2 x 7 steps of the
-            // three-way split -- and a scheduling fence, so that hipcc keeps the order.
-            static_assert(!PIN || (MT * 2 == NBATCH && 6 * BT * MT == 48), "one half fragment per batch");
-            const int hm = bi % MT, hh = bi / MT;             // the half built in this batch
-            const int64_t blk = (int64_t)s * NT + (bi + 1) * BT;
-            int t = 0;
-            f32x4 bb = {0.f, 0.f, 0.f, 0.f}, p = {0.f, 0.f, 0.f, 0.f}, yy = {0.f, 0.f, 0.f, 0.f};
-            float xx = 0.f;
-            Split3Steps st[2];
-#pragma unroll
-            for (int n = 0; n < 48; ++n) {
-                const int pr = n / (BT * MT), c = (n / MT) % BT, m = n % MT;
-                mfma_bf16_pinned<false>(acc[m][bi * BT + c], cur.w[kProdA[pr]][m],
-                                        b.p[c][kProdB[pr]]);
-                if (BEER_K1_ABL >= 1 && n >= NP * BT) {
-                } else if (BEER_K1_ABL >= 2) {
-                } else if (n < NP * BT) {
-#ifdef BEER_K1_FAKEB
-                    // (timing experiment: every load hits the same 12 KB -- wrong results)
-                    bn.p[n / NP][n % NP] = Pl[(size_t)((blk + n / NP) & 3) * kBlockU4 + 64 * (n % NP)];
-#else
-                    bn.p[n / NP][n % NP] = Pl[(size_t)(blk + n / NP) * kBlockU4 + 64 * (n % NP)];
-#endif
-                } else if (n == 8) {
-                    t = tl[8 * (s + 1) + hh];                 // (the table is padded by one k-step)
-                } else if (n == 12) {
-                    bb = *reinterpret_cast<const f32x4*>(xrow[hm] + (SQ ? (t >> 8) & 0xff : t & 0xff));
-                    if (SQ) xx = xrow[hm][t & 0xff];
-                } else if (!SQ && n >= 13 && n < 17) {
-                    yy[n - 13] = xrow[hm][band_col(t, n - 13, Dp)];
-                } else if (n >= 18 && n < 22) {
-                    const bool sq = SQ && (t >> 16) != 0;
-                    float v = bb[n - 18] * (SQ ? (sq ? bb[n - 18] : xx) : yy[n - 18]);
-                    pin(v);
-                    p[n - 18] = v;
-                } else if (n >= 22 && n < 29) {
-                    split3_step(n - 22, p[0], p[1], st[0]);
-                } else if (n >= 29 && n < 36) {
-                    split3_step(n - 29, p[2], p[3], st[1]);
-                }
-                if (BEER_K1_FENCE > 0 && n % BEER_K1_FENCE == BEER_K1_FENCE - 1)
-                    __builtin_amdgcn_sched_barrier(0);
-            }
-            if (BEER_K1_ABL >= 1) {
-#pragma unroll
-                for (int q = 0; q < NP; ++q) nxt.w[q][hm] = cur.w[q][hm];
-                if (BEER_K1_ABL >= 2) bn = b;
-                return;
-            }
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                nxt.w[0][hm][2 * hh + e] = st[e].w0;
-                nxt.w[1][hm][2 * hh + e] = st[e].w1;
-                nxt.w[2][hm][2 * hh + e] = st[e].w2;
-            }
-            return;
-        }
         if constexpr (BL) {
             // in front of the batches whose look-ahead read crosses into the other buffer:
             // batch 3 (reads tile 8 of this k-step; buffer 0 has been read out: refill it with
@@ -658,11 +558,6 @@ __global__ __launch_bounds__(kThreads, MT * NT <= 32 ? 2 : 1) void llhx_kernel(
     for (int s = 0; s < nku; s += 2) {
         kstep(s, f0, f1, b0, b1);
         if (s + 1 < nku) kstep(s + 1, f1, f0, b0, b1);
-    }
-    if constexpr (PIN) mfma_drain();
-    if (PIN && BEER_K1_ABL >= 3) {
-        if (acc[0][0][0] == 1.2345f) log_norm[0] = 1.f;
-        return;
     }
     if constexpr (LNO) {
         // (jw == 4 by construction of the dispatch; gl = lanes per group, uniform; 0: the
@@ -923,7 +818,6 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
     // chunk position pos holds frames 8 (pos ^ (c & 7)) ..), all three planes, times
     // the state's gamma
     auto fold = [&](int buf) {
-        if (BEER_K2_ABL == 4) return;                       // (timing experiment: no fold)
 #pragma unroll 1
         for (int n = 0; n < 16 * MC * 8 / (64 * WAVES); ++n) {
             const int p = tid + 64 * WAVES * n, c = p >> 3, pos = p & 7, ch = pos ^ (c & 7);
@@ -1012,7 +906,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
         if (active) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                if (BEER_K2_ABL < 2 || (tile == 0 && ks == 0)) load_a(buf, ks);
+                load_a(buf, ks);
 #pragma unroll
                 for (int uu = 0; uu < NQ; ++uu) {
                     // (the two B buffers alternate along the tile's 2 NQ steps, which
@@ -1022,9 +916,9 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
                     // The B fragment of the next statistic tile (of tile 0 of the next
                     // k-step; the one of the next TILE comes from the other buffer, after
                     // the barrier), built behind this tile's 48 MFMAs, one filler each, every
-                    // result pinned where it is computed (see K1): 4 LDS reads, 8 products,
+                    // result pinned where it is computed (split3_step): 4 LDS reads, 8 products,
                     // 4 x 7 steps of the three-way split.
-                    const bool build = BEER_K2_ABL < 1 && (uu + 1 < NQ || ks == 0);
+                    const bool build = uu + 1 < NQ || ks == 0;
                     const int nks = uu + 1 < NQ ? ks : 1, nuu = uu + 1 < NQ ? uu + 1 : 0;
                     const char* pa = smem + xa_off[nuu] + (buf * xstride + 128 * nks);
                     const char* pb = smem + xb_off[nuu] + (buf * xstride + 128 * nks);
@@ -1042,22 +936,14 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
                         else if (n == 4) xb[1] = *reinterpret_cast<const f32x4*>(pb + 16);
                         else if (n >= 12 && n < 20) {
                             const int e = n - 12;
-                            if (BEER_ASM_STEPS) {
-                                asm volatile("v_mul_f32 %0, %1, %2" : "=v"(pp[e])
-                                             : "v"(xa[e >> 2][e & 3]), "v"(xb[e >> 2][e & 3]));
-                            } else {
-                                pp[e] = xa[e >> 2][e & 3] * xb[e >> 2][e & 3];
-                                pin(pp[e]);
-                            }
+                            asm volatile("v_mul_f32 %0, %1, %2" : "=v"(pp[e])
+                                         : "v"(xa[e >> 2][e & 3]), "v"(xb[e >> 2][e & 3]));
                         } else if (n >= 20) {
                             // two pairs at a time, their seven steps alternating: a step and the
                             // one that consumes its result are two MFMAs apart (back to back --
                             // one MFMA apart -- hipcc pads the dependence with an s_nop: 612 of
                             // them per tile pair)
-#ifndef BEER_K2_CHAINS
-#define BEER_K2_CHAINS 2
-#endif
-                            constexpr int NCH = BEER_K2_CHAINS;
+                            constexpr int NCH = 2;
                             const int m = n - 20, grp = m / (7 * NCH), mm = m % (7 * NCH);
                             const int e = NCH * grp + mm % NCH;
                             split3_step(mm / NCH, pp[2 * e], pp[2 * e + 1], st[e]);
@@ -1070,9 +956,6 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
                             bf[cur ^ 1][1][e] = st[e].w1;
                             bf[cur ^ 1][2][e] = st[e].w2;
                         }
-                    } else if (BEER_K2_ABL >= 1) {
-#pragma unroll
-                        for (int q = 0; q < NP; ++q) bf[cur ^ 1][q] = bf[cur][q];
                     }
                 }
             }
@@ -1093,10 +976,6 @@ __global__ __launch_bounds__(64 * kAxWaves, 1) void accx_kernel(
         if (tile + 1 < ntiles) iteration(tile + 1, 1);
     }
     mfma_drain();
-    if (BEER_K2_ABL >= 3) {
-        if (acc[0][0][0] == 1.2345f) Sp[0] = 1.0;
-        return;
-    }
 #pragma unroll
     for (int uu = 0; uu < NQ; ++uu) {
         const int q = (tile0 + uu) * 16 + i;
@@ -1221,10 +1100,7 @@ __global__ __launch_bounds__(256) void pack_resps_kernel(int64_t nframes, int K,
 // frame tiles it walks (fp32, <= 4096 frames), then adds it to the fp64 image.
 // ---------------------------------------------------------------------------
 constexpr int kAfXS = 36;                 // row stride (floats) of the transposed frame tile
-#ifndef BEER_AF_MAXFRAMES
-#define BEER_AF_MAXFRAMES 2048
-#endif
-constexpr int kAfMaxFramesPerWave = BEER_AF_MAXFRAMES; // MFMA accumulations per sum: 64 (half of
+constexpr int kAfMaxFramesPerWave = 2048; // MFMA accumulations per sum: 64 (half of
 // the packed accumulation's 128, BEER_OPT_AX_MAXFRAMES; 1024 -> 2048 frames: fewer flushes, 29.8 -> 29.35 ms
 // per 10 M frames at config 3, count conservation unchanged at 3.6e-8)
 
@@ -1425,7 +1301,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void accf_kernel(
             // A tile none of whose frames gives the chunk's states any posterior
             // contributes exactly nothing: skip it (alignment graphs: most of the model's
             // states are absent from an utterance, their posteriors are exact zeros)
-            if (sr && !(BEER_AF_ABL & 64)) {
+            if (sr) {
                 float any = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) any = __builtin_fmaxf(any, __builtin_fabsf(lsv[j]));
@@ -1454,7 +1330,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void accf_kernel(
                         }
                     }
             if (fb + WAVES * FW < te) issue(fb + WAVES * FW);
-            if (sr && !(BEER_AF_ABL & 64)) {
+            if (sr) {
                 float any = 0.f;
 #pragma unroll
                 for (int q = 0; q < QT; ++q)
@@ -1540,18 +1416,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void accf_kernel(
                     // l - log_norm first (one rounding of a small difference), THEN the change
                     // of base: scaling l (|l| ~ 100) and log_norm separately by a rounded
                     // log2(e) left a systematic 4e-6 in r
-                    v[r] = (BEER_AF_ABL & 8) ? acc[m][nt][r] + nl2[q][m][r][jj] + wg[q][m][r][jj] :
-                           __builtin_amdgcn_exp2f((acc[m][nt][r] + nl2[q][m][r][jj]) *
+                    v[r] = __builtin_amdgcn_exp2f((acc[m][nt][r] + nl2[q][m][r][jj]) *
                                                   1.44269504088896340736f) *
                            wg[q][m][r][jj];
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     unsigned w3[3];
-                    if (BEER_AF_ABL & 8) {
-                        w3[0] = __builtin_bit_cast(unsigned, v[2 * e]);
-                        w3[1] = __builtin_bit_cast(unsigned, v[2 * e + 1]);
-                        w3[2] = w3[0] ^ w3[1];
-                    } else
                     split3(v[2 * e], v[2 * e + 1], w3);
 #pragma unroll
                     for (int pq = 0; pq < NP; ++pq) ar[nt][pq][2 * m + e] = w3[pq];
@@ -1581,13 +1451,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void accf_kernel(
 #pragma unroll
         for (int uu = 0; uu < NQT; ++uu) {
             const int cur = uu & 1;
-            if (uu + 1 < NQT) {
-                if (BEER_AF_ABL & 16) {
-#pragma unroll
-                    for (int pq = 0; pq < NP; ++pq) bq[cur ^ 1][pq] = bq[cur][pq];
-                } else
-                gen_b(uu + 1, bq[cur ^ 1]);
-            }
+            if (uu + 1 < NQT) gen_b(uu + 1, bq[cur ^ 1]);
 #pragma unroll
             for (int pr = 0; pr < 6; ++pr)
 #pragma unroll
@@ -1597,15 +1461,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void accf_kernel(
     }
 
     // ---- flush: rows = components kbase + 64 (c / 4) + 4 (4 g + r) + c % 4 ----
-    if (BEER_AF_ABL & 1) {
-        float t = 0.f;
-#pragma unroll
-        for (int uu = 0; uu < NQT; ++uu)
-#pragma unroll
-            for (int c = 0; c < NTC; ++c) t += sacc[c][uu][0] + sacc[c][uu][1] + sacc[c][uu][2] + sacc[c][uu][3];
-        if (t == 1.2345f) Sp[0] = 1.0;
-        return;
-    }
     // The WAVES waves of the workgroup hold sums over different frames of the same 64
     // components: added up through LDS (the parameters' region, no longer needed; fp64)
     // one statistic tile at a time, so that the fp64 image sees one atomic per
@@ -1780,11 +1635,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void accfi_kernel(
         for (int idx = tid; idx < p_u4; idx += NTHREADS) Ps[idx] = src[idx];
     }
     __syncthreads();
-    if (BEER_ACCFI_SLEEP > 0 && (WAVES == 8 ? wave >= 4 : (blockIdx.x >> 3) & 1)) {
-#pragma unroll
-        for (int n = 0; n < (BEER_ACCFI_SLEEP + 126) / 127; ++n)
-            __builtin_amdgcn_s_sleep(BEER_ACCFI_SLEEP < 127 ? BEER_ACCFI_SLEEP : 127);
-    }
     const int kbase = by * (16 * NTC);
     const float c0 = c0p[0];
     const int64_t tb = bx * frames_per_block;
@@ -1883,8 +1733,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void accfi_kernel(
                 for (int q = 0; q < NP; ++q)
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
-                        af[(s + 1) & 1][q][m] = (BEER_AFI_ABL & 4) ? af[s & 1][q][m] :
-                                                ti[(((s + 1) * NP + q) * MT + m) * 64];
+                        af[(s + 1) & 1][q][m] = ti[(((s + 1) * NP + q) * MT + m) * 64];
             }
             // the loads of this k-step first (the counts must match what is issued here, or
             // hipcc moves other loads in to fill the group)
@@ -1925,7 +1774,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void accfi_kernel(
                 const float wg = (sr ? lsw[(FW + row) * NS + sidx] : 1.f) * (ok ? 1.f : 0.f);
 #pragma unroll
                 for (int nt = 0; nt < NTC; ++nt)
-                    acc[m][nt][r] = exp2_valu((acc[m][nt][r] + nl2) * 1.44269504088896340736f) * wg;
+                    acc[m][nt][r] = __builtin_amdgcn_exp2f((acc[m][nt][r] + nl2) * 1.44269504088896340736f) * wg;
             }
 #pragma unroll
         for (int nt = 0; nt < NTC; ++nt)
@@ -1949,8 +1798,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void accfi_kernel(
             if (uu + NBQ - 1 < NQT) {
 #pragma unroll
                 for (int q = 0; q < NP; ++q)
-                    bq[(uu + NBQ - 1) % NBQ][q] = (BEER_AFI_ABL & 1) ? bq[uu % NBQ][q] :
-                                                  ti[(NKU * NP * MT + (uu + NBQ - 1) * NP + q) * 64];
+                    bq[(uu + NBQ - 1) % NBQ][q] = ti[(NKU * NP * MT + (uu + NBQ - 1) * NP + q) * 64];
             }
             if (uu == NQT - 3) {
                 // (no next tile: this one again, harmlessly)
@@ -1972,15 +1820,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void accfi_kernel(
     }
 
     // ---- flush: the waves' partial sums through LDS (fp64), one atomic per element ----
-    if (BEER_AFI_ABL & 2) {
-        float t = 0.f;
-#pragma unroll
-        for (int uu = 0; uu < NQT; ++uu)
-#pragma unroll
-            for (int c = 0; c < NTC; ++c) t += sacc[c][uu][0] + sacc[c][uu][1] + sacc[c][uu][2] + sacc[c][uu][3];
-        if (t == 1.2345f) Sp[0] = 1.0;
-        return;
-    }
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);          // [WAVES][16 = c * 4 + r][64 lanes]
     const int ndata = nslab - 1 - (nslab - 1) / 8;         // squares and linear terms (no constants)
@@ -2078,11 +1917,6 @@ __global__ __launch_bounds__(512, 2) void lnfi_kernel(
         for (int idx = tid; idx < p_u4; idx += NTHREADS) Ps[idx] = src[idx];
     }
     __syncthreads();
-    if (BEER_LNFI_SLEEP > 0 && wave >= WAVES / 2) {
-#pragma unroll
-        for (int n = 0; n < (BEER_LNFI_SLEEP + 126) / 127; ++n)
-            __builtin_amdgcn_s_sleep(BEER_LNFI_SLEEP < 127 ? BEER_LNFI_SLEEP : 127);
-    }
     const int kbase = by * (16 * NT);
     const float c0 = c0p[0];
     const int64_t tb = bx * frames_per_block;
@@ -2123,44 +1957,27 @@ __global__ __launch_bounds__(512, 2) void lnfi_kernel(
                 for (int q = 0; q < NP; ++q)
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
-                        af[(s + 1) & 1][q][m] = (BEER_LNFI_ABL & 8) ? af[s & 1][q][m] : src[(q * MT + m) * 64];
+                        af[(s + 1) & 1][q][m] = src[(q * MT + m) * 64];
             }
-            if (!(BEER_LNFI_ABL & 8)) __builtin_amdgcn_sched_group_barrier(0x020, NP * MT, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, NP * MT, 0);
 #pragma unroll
             for (int c = 0; c < NT; ++c) {
                 constexpr int kLast = NKU * NT - 1;
                 const int gi = s * NT + c, gn = gi < kLast ? gi + 1 : kLast;
 #pragma unroll
                 for (int pq = 0; pq < NP; ++pq)
-                    bp[(gi + 1) & 1][pq] = (BEER_LNFI_ABL & 4) ? bp[gi & 1][pq] : Pl[gn * kBlockU4 + 64 * pq];
-                if (BEER_LNFI_ABL & 2) continue;
+                    bp[(gi + 1) & 1][pq] = Pl[gn * kBlockU4 + 64 * pq];
 #pragma unroll
                 for (int pr = 0; pr < 6; ++pr)
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
                         acc[m][c] = mfma_bf16(af[s & 1][kProdA[pr]][m], bp[gi & 1][kProdB[pr]], acc[m][c]);
-                if (!(BEER_LNFI_ABL & 4)) __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 6 * MT, 0);
             }
         }
-        if (BEER_LNFI_ABL & 1) {
-            float t = 0.f;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int c = 0; c < NT; ++c) t += acc[m][c][0] + acc[m][c][1] + acc[m][c][2] + acc[m][c][3];
-            if (t == 1.2345f) log_norm[0] = t;
-        } else {
-            if (BEER_LNFI_ABL & 2) {
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-#pragma unroll
-                    for (int c = 0; c < NT; ++c)
-                        acc[m][c] = f32x4{(float)(c + lane), (float)(m - c), (float)lane, bp[0][0][0] * 1e-30f};
-            }
-            lognorm_epilogue_lane_major<NT, MT, G>(acc, fb, nframes, kbase, S, i, g, lane, log_norm,
-                                                   llh_sum, c0);
-        }
+        lognorm_epilogue_lane_major<NT, MT, G>(acc, fb, nframes, kbase, S, i, g, lane, log_norm,
+                                               llh_sum, c0);
         if constexpr (NKU % 2 == 0) {
             // (even number of k-steps: the prefetched fragments sit in af[0] already)
         } else {
@@ -2221,9 +2038,6 @@ inline size_t p_image_bytes(int nchunks, int nk, int NT) {
 #ifdef BEER_KERNEL_PROBE
 // ISA experiments (tools/isa_stats.py): only the hot kernels, no host code
 namespace {
-template __global__ void llhx_kernel<16, 4, 4, true, false, false>(
-    int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
-    double*, float*, int, int, int, const float*, const u4*);
 template __global__ void llhx_kernel<16, 2, 4, true, false, false, false, true>(
     int64_t, int, int, int, int, int, int, int, const float*, const u4*, const int*, float*, float*,
     double*, float*, int, int, int, const float*, const u4*);
@@ -2380,11 +2194,9 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
             // 32 frames x 256 components per wave, two waves per SIMD: the epilogue of one
             // wave (its 48 KB of packed tiles leave at the CU's store-issue rate) runs under
             // the other's MFMAs.  Measured at K = 256, D = 40, 1 M frames: 2.0 ms against
-            // 2.3 ms for 64 x 256 per wave with one wave per SIMD (BEER_K1_WIDE=1), whose
-            // hand-placed main loop runs at 90 % of the MFMA rate but whose epilogue, 0.4 ms,
-            // nothing covers.
-            const bool wide = beer::option(BEER_OPT_K1_WIDE) != 0;
-            if (wide) BEER_LLHX(16, 4, 4, true, false, xt, xtf);
+            // 2.3 ms for 64 x 256 per wave with one wave per SIMD (a retired variant), whose
+            // hand-placed main loop ran at 90 % of the MFMA rate but whose epilogue, 0.4 ms,
+            // nothing covered.
             if (full && k1_lds_fits(D, nk) && beer::option(BEER_OPT_K1_LDS))
                 return launch_llhx<16, 2, 4, true, false, false, false, true>(
                     nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm,
@@ -2404,13 +2216,6 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
     }
     if (packed) {
         // the responsibilities within each state's mixture as the accumulation's LDS tiles
-        const bool wide = beer::option(BEER_OPT_K1_WIDE) != 0;
-        if (wide) {
-            switch (gq) {
-                case 1: BEER_LLHX(16, 4, 1, true, false);
-                default: BEER_LLHX(16, 4, 2, true, false);
-            }
-        }
         if (full && k1_lds_fits(D, nk) && beer::option(BEER_OPT_K1_LDS)) {
             if (gq == 1)
                 return launch_llhx<16, 2, 1, true, false, false, false, true>(

@@ -16,39 +16,6 @@ using namespace beer;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-// 2^y, y <~ 0, on the plain vector ALU.  v_exp_f32 runs at a quarter of the vector rate AND
-// keeps the matrix pipe of its SIMD from issuing meanwhile -- measured
-// (tools/probes/coissue.hip): a wave of fma + add + exp triples beside a wave of MFMAs on the
-// same SIMD takes the SUM of their times (65.6 k cycles against 35.4 k + 35 k), where plain
-// fmas vanish behind the MFMAs (37 k); in the epilogues below that was 16 cycles of matrix
-// pipe per exponential.  y = n + f, n = rint(y) by the 1.5 * 2^23 trick, 2^f on [-1/2, 1/2] by a
-// degree-6 polynomial (max relative error 7.9e-8 evaluated in float32: a float32 ulp, like
-// v_exp_f32), 2^n added into the exponent field.  Arguments below -125 (padded components,
-// rows past the end) give 2^-125; NaN arguments give 2^-125 too (the log-normaliser of the
-// frame is NaN regardless: its maximum is).  11 full-rate instructions.
-#ifndef BEER_EXP_VALU
-#define BEER_EXP_VALU 0
-#endif
-#ifndef BEER_LNFI_TRANS_EVERY
-#define BEER_LNFI_TRANS_EVERY 0     // lane-major log-normaliser epilogue: every n-th exponential on v_exp_f32 (0: none)
-#endif
-__device__ __forceinline__ float exp2_valu(float y) {
-    if (!BEER_EXP_VALU) return __builtin_amdgcn_exp2f(y);
-    y = __builtin_fmaxf(y, -125.f);
-    const float magic = 12582912.f;
-    const float t = y + magic;
-    const float f = y - (t - magic);
-    float p = 0.00015345810970757157f;
-    p = __builtin_fmaf(p, f, 0.0013399930903688073f);
-    p = __builtin_fmaf(p, f, 0.009618489071726799f);
-    p = __builtin_fmaf(p, f, 0.05550328642129898f);
-    p = __builtin_fmaf(p, f, 0.24022646248340607f);
-    p = __builtin_fmaf(p, f, 0.6931471824645996f);
-    p = __builtin_fmaf(p, f, 1.0f);
-    return __builtin_bit_cast(float, __builtin_bit_cast(int, p) +
-                                         (int)((unsigned)__builtin_bit_cast(int, t) << 23));
-}
-
 template <typename T> struct Mma;
 template <> struct Mma<float> {
     using acc_t = f32x4;
@@ -428,52 +395,28 @@ __device__ __forceinline__ void split3(float a, float b, unsigned (&p)[3]) {
     p[2] = cvt_pk_bf16(ra, rb);
 }
 // split3 one instruction group at a time (k = 0 .. 6), for kernels that place the
-// fragment arithmetic by hand between their MFMAs
-// (`pin`: an empty volatile asm that redefines the value.  Volatile asms keep their
-// order, so a value pinned between two pinned MFMAs is computed between them --
-// hipcc's IR passes otherwise sink the whole computation to its first use, a k-step
-// later, and keep its inputs alive until then.)
-template <typename V>
-__device__ __forceinline__ void pin(V& v) { asm volatile("" : "+v"(v)); }
+// fragment arithmetic by hand between their MFMAs.  Every step is a volatile asm statement
+// (one or two instructions): volatile asms keep their program order among themselves, so a
+// step written between two pinned MFMAs stays there.  C++ steps with only their RESULTS
+// pinned were slid along the stream by the machine scheduler into runs of four or five
+// behind every second MFMA -- and an in-order wave that meets `M M v v v v` waits for the
+// matrix pipe in front of the second M with nothing to issue (21.5 cycles per MFMA against
+// 17.3 for `M v v M v v`, tools/probes/coissue.hip).
 struct Split3Steps { unsigned w0, w1, w2; float r0, r1; };
-// BEER_ASM_STEPS: every step is a volatile asm statement (one or two instructions).  Pinning
-// the RESULT of a C++ step (pin()) keeps it from sinking to its first use, but the machine
-// scheduler still slides the instruction itself along the stream and gathers the steps into
-// runs of four or five behind every second MFMA -- and an in-order wave that meets
-// `M M v v v v` waits for the matrix pipe in front of the second M with nothing to issue
-// (21.5 cycles per MFMA against 17.3 for `M v v M v v`, tools/probes/coissue.hip).  Volatile asm
-// statements keep their program order among themselves: the steps stay where they are written.
-#ifndef BEER_ASM_STEPS
-#define BEER_ASM_STEPS 1
-#endif
 __device__ __forceinline__ void split3_step(int k, float a, float b, Split3Steps& t) {
-#pragma clang fp contract(off)
-    if (BEER_ASM_STEPS) {
-        unsigned tmp;
-        switch (k) {
-            case 0: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w0) : "v"(a), "v"(b)); break;
-            case 1: asm volatile("v_lshlrev_b32 %0, 16, %1\n\tv_sub_f32 %0, %2, %0"
-                                 : "=&v"(t.r0) : "v"(t.w0), "v"(a)); break;
-            case 2: asm volatile("v_and_b32 %0, 0xffff0000, %1\n\tv_sub_f32 %0, %2, %0"
-                                 : "=&v"(t.r1) : "v"(t.w0), "v"(b)); break;
-            case 3: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w1) : "v"(t.r0), "v"(t.r1)); break;
-            case 4: asm volatile("v_lshlrev_b32 %0, 16, %2\n\tv_sub_f32 %1, %1, %0"
-                                 : "=&v"(tmp), "+v"(t.r0) : "v"(t.w1)); break;
-            case 5: asm volatile("v_and_b32 %0, 0xffff0000, %2\n\tv_sub_f32 %1, %1, %0"
-                                 : "=&v"(tmp), "+v"(t.r1) : "v"(t.w1)); break;
-            case 6: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w2) : "v"(t.r0), "v"(t.r1)); break;
-            default: break;
-        }
-        return;
-    }
+    unsigned tmp;
     switch (k) {
-        case 0: t.w0 = cvt_pk_bf16(a, b); pin(t.w0); break;
-        case 1: t.r0 = a - __builtin_bit_cast(float, t.w0 << 16); pin(t.r0); break;
-        case 2: t.r1 = b - __builtin_bit_cast(float, t.w0 & 0xffff0000u); pin(t.r1); break;
-        case 3: t.w1 = cvt_pk_bf16(t.r0, t.r1); pin(t.w1); break;
-        case 4: t.r0 -= __builtin_bit_cast(float, t.w1 << 16); pin(t.r0); break;
-        case 5: t.r1 -= __builtin_bit_cast(float, t.w1 & 0xffff0000u); pin(t.r1); break;
-        case 6: t.w2 = cvt_pk_bf16(t.r0, t.r1); pin(t.w2); break;
+        case 0: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w0) : "v"(a), "v"(b)); break;
+        case 1: asm volatile("v_lshlrev_b32 %0, 16, %1\n\tv_sub_f32 %0, %2, %0"
+                             : "=&v"(t.r0) : "v"(t.w0), "v"(a)); break;
+        case 2: asm volatile("v_and_b32 %0, 0xffff0000, %1\n\tv_sub_f32 %0, %2, %0"
+                             : "=&v"(t.r1) : "v"(t.w0), "v"(b)); break;
+        case 3: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w1) : "v"(t.r0), "v"(t.r1)); break;
+        case 4: asm volatile("v_lshlrev_b32 %0, 16, %2\n\tv_sub_f32 %1, %1, %0"
+                             : "=&v"(tmp), "+v"(t.r0) : "v"(t.w1)); break;
+        case 5: asm volatile("v_and_b32 %0, 0xffff0000, %2\n\tv_sub_f32 %1, %1, %0"
+                             : "=&v"(tmp), "+v"(t.r1) : "v"(t.w1)); break;
+        case 6: asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(t.w2) : "v"(t.r0), "v"(t.r1)); break;
         default: break;
     }
 }
@@ -783,11 +726,13 @@ __device__ __forceinline__ void lognorm_epilogue_lane_major(
                 const float nm = -mx * L2E;
                 const float d = __builtin_fmaf(mx, L2E, nm);
                 float sum = 0.f;
+                // v_exp_f32 keeps the matrix pipe of its SIMD from issuing meanwhile
+                // (tools/probes/coissue.hip), but an 11-instruction polynomial on the plain
+                // vector ALU lost to it: these kernels are bound by vector issue (lnfi 5.5 ->
+                // 6.2 ms, accfi 10.7 -> 11.8 ms; DESIGN.md, "Tried and measured, not kept")
 #pragma unroll
                 for (int c = 0; c < G; ++c)
-                    sum += (BEER_LNFI_TRANS_EVERY > 0 && c % (BEER_LNFI_TRANS_EVERY > 0 ? BEER_LNFI_TRANS_EVERY : 1) == 0)
-                               ? __builtin_amdgcn_exp2f(__builtin_fmaf(acc[m][q * G + c][r], L2E, nm))
-                               : exp2_valu(__builtin_fmaf(acc[m][q * G + c][r], L2E, nm));
+                    sum += __builtin_amdgcn_exp2f(__builtin_fmaf(acc[m][q * G + c][r], L2E, nm));
                 const float lse = __builtin_fmaf(__builtin_amdgcn_logf(sum) - d, LN2, mx) + shift;
                 if (ok && s0 + q < S) {
                     if (log_norm) row[q] = lse;

@@ -761,22 +761,11 @@ __global__ __launch_bounds__(kLdThreads) void fb_lowdeg_kernel(
 // back to pdf ids (modelset.py:148-154, hmm.py:95) and the utterance's
 // sum_t sum_s gamma * pc (hmm.py:87) when gamma is written: three launches and
 // two round trips of the [frames, states] arrays less.
-#ifndef BEER_FB_WAVES
-#define BEER_FB_WAVES 4
-#endif
-constexpr int kWvWaves = BEER_FB_WAVES; // utterances (waves) per workgroup
-#ifndef BEER_FB_PF
-#define BEER_FB_PF 4
-#endif
-constexpr int kWvPF = BEER_FB_PF;      // steps of look-ahead of the global loads
-#ifndef BEER_FB_RESCALE
-#define BEER_FB_RESCALE 2
-#endif
-constexpr int kWvRescale = BEER_FB_RESCALE;   // a column is rescaled every kWvRescale-th frame (divides kWvPF)
+constexpr int kWvWaves = 4;            // utterances (waves) per workgroup
+constexpr int kWvPF = 4;               // steps of look-ahead of the global loads
+constexpr int kWvRescale = 2;          // a column is rescaled every kWvRescale-th frame (divides kWvPF)
 static_assert(kWvPF % kWvRescale == 0, "the rescaled frames are fixed positions of the unrolled loop");
-#ifndef BEER_FB_OCC
-#define BEER_FB_OCC 4                  // waves per SIMD the linear-domain kernel is compiled for
-#endif
+constexpr int kWvOcc = 4;              // waves per SIMD the linear-domain kernel is compiled for
 
 typedef unsigned v2u_t __attribute__((ext_vector_type(2)));     // a 64-bit buffer word
 
@@ -871,7 +860,7 @@ constexpr int kWvRowMax = 512;
 // (CNT is compiled for one wave per SIMD less: the per-arc sums and the source flows take the
 // registers that kept the recipe's shape, 120 states on two slots a lane, from spilling)
 template <typename T, int SPL, int DEG, bool FUSED, bool XI, int OUTM, bool CNT>
-__global__ __launch_bounds__(64 * kWvWaves, (BEER_FB_OCC - (CNT ? 1 : 0)) * 4 / kWvWaves) void fb_wave_kernel(
+__global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWaves) void fb_wave_kernel(
     beer_batch b, const T* __restrict__ pc, int S_total, T scale, double* __restrict__ alpha_ws,
     double* __restrict__ hubf_ws, T* __restrict__ out, T resp_scale,
     double* __restrict__ xi_sum, double* __restrict__ gamma0_sum, double* __restrict__ hub_flow,

@@ -12,7 +12,6 @@ struct OptSpec { int def, lo, hi; };
 constexpr OptSpec kOptSpec[BEER_OPT_COUNT] = {
     {kAxMaxFramesDefault, 64, 1 << 20},      // BEER_OPT_AX_MAXFRAMES
     {6, 1, 64},               // BEER_OPT_ACCF_ROUNDS
-    {0, 0, 1},                // BEER_OPT_K1_WIDE
     {4, 4, 8},                // BEER_OPT_ACCFI_WAVES (4 or 8)
     {1, 0, 1},                // BEER_OPT_LNFI
     {0, 0, 1},                // BEER_OPT_FB_LOG

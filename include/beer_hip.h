@@ -62,25 +62,23 @@ int beer_hip_device_count(void);
                                   * chain on same-sign sums).  Default 4096, range 64 .. 2^20. */
 #define BEER_OPT_ACCF_ROUNDS 1   /* workgroup rounds per CU of beer_mixtureset_accumulate_fused.
                                   * Default 6, range 1 .. 64. */
-#define BEER_OPT_K1_WIDE 2       /* 1: the packed E-step runs its 64 x 256-per-wave form.
-                                  * Default 0. */
-#define BEER_OPT_ACCFI_WAVES 3   /* waves per workgroup of the fused accumulation over a frame
+#define BEER_OPT_ACCFI_WAVES 2   /* waves per workgroup of the fused accumulation over a frame
                                   * image: 4 (two workgroups per CU: one flushes its partial
                                   * sums while the other multiplies) or 8.  Default 4. */
-#define BEER_OPT_LNFI 4          /* 1: beer_mixtureset_lognorm_image keeps a chunk's packed
+#define BEER_OPT_LNFI 3          /* 1: beer_mixtureset_lognorm_image keeps a chunk's packed
                                   * parameters in LDS and walks blocks of frames (lnfi_kernel);
                                   * 0: one tile per wave, parameters streamed from L2.  Default 1. */
-#define BEER_OPT_FB_LOG 5        /* 1: the one-wave-per-utterance forward-backward runs EVERY
+#define BEER_OPT_FB_LOG 4        /* 1: the one-wave-per-utterance forward-backward runs EVERY
                                   * utterance in log space (the kernel that otherwise only
                                   * redoes utterances whose dynamic range exceeds the
                                   * scaled-probability recursion; beer/graph.py:270-326 is
                                   * log-space throughout).  Default 0. */
-#define BEER_OPT_K1_LDS 6        /* 1: the packed full-covariance E-step stages the packed
+#define BEER_OPT_K1_LDS 5        /* 1: the packed full-covariance E-step stages the packed
                                   * parameters of a k-step through LDS once per workgroup (DMA,
                                   * ring of two half k-steps) instead of streaming them from L2
                                   * per wave; 0: per wave.  Same products in the same order:
                                   * bit-identical results.  Default 1. */
-#define BEER_OPT_COUNT 7
+#define BEER_OPT_COUNT 6
 int beer_hip_set_option(int option, int value);
 int beer_hip_get_option(int option);   /* the value, or BEER_EINVAL for an unknown option */
 
