@@ -128,6 +128,11 @@ class Batch(ctypes.Structure):
                 ('order', c_p)]
 
 
+class CatMap(ctypes.Structure):
+    'beer_cat_map of include/beer_hip.h.'
+    _fields_ = [('arc_cat', c_p), ('last_cat', c_p), ('arc_off', c_p), ('state_off', c_p)]
+
+
 class Bigram(ctypes.Structure):
     'beer_bigram of include/beer_hip.h.'
     _fields_ = [('n_states', ctypes.c_int32), ('n_phones', ctypes.c_int32),
@@ -217,6 +222,11 @@ SIGNATURES = {
     'beer_hmm_forward_backward_counts': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                          c_p],
     'beer_hmm_last_frame_sum': [c_i, c_p, c_p, c_p, c_p],
+    'beer_hmm_refresh_weights': [c_i, c_l, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_posteriors_fused_cat': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p, c_p,
+                                      c_p, c_p, c_p],
+    'beer_hmm_forward_backward_cat': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_path_counts_cat': [c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_fb_log_count': [c_p, c_p, c_p, c_p],
     'beer_hmm_posteriors_bigram': [c_i, c_p, ctypes.c_int32, c_l, c_p, c_p, c_i, c_p, c_d, c_p,
                                    c_p, c_p, c_i, c_p, c_p],
@@ -251,6 +261,7 @@ HOST_SIGNATURES = {
                            ctypes.c_int32, c_pp],
     'beer_aligraphs_compile': [ctypes.c_int32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l,
                                c_p, c_p, c_pp],
+    'beer_graphset_from_csr': [c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_pp],
     'beer_graphset_free': [c_p],
     'beer_graphset_sizes': [c_p, c_p, c_p, c_p],
     'beer_graphset_export': [c_p, c_p, c_p, c_p, c_p, c_p, c_p],

@@ -423,6 +423,27 @@ def _shard(model, dataset, uttids, alis, logger):
     return feats, graphs, kept
 
 
+def _shard_elbo(model, feats, graphs, datasize, scale):
+    '''ELBO of a shard whose utterances may have an alignment graph (`graphs[i]`, or None).
+    Utterances with one train the emissions -- and learned transitions, whose categories the
+    graphs are bound to here -- but give the phone weights no counts (phoneloop.py:98-100);
+    those without one go through the free phone loop and DO count phones, as the reference's
+    per-utterance `inference_graph=None` does (accumulate.py:45-54): two batches, one sum.'''
+    elbo = beer.evidence_lower_bound(datasize=datasize)
+    aligned = [i for i, g in enumerate(graphs) if g is not None]
+    free = [i for i, g in enumerate(graphs) if g is None]
+    if aligned:
+        use = [graphs[i] for i in aligned]
+        if getattr(model, 'transitions', None) is not None:
+            use = model.bind_alignment_graphs(use)
+        elbo = elbo + beer.accumulate_elbo(model, [feats[i] for i in aligned], datasize=datasize,
+                                           inference_graphs=use, scale=scale)
+    if free:
+        elbo = elbo + beer.accumulate_elbo(model, [feats[i] for i in free], datasize=datasize,
+                                           scale=scale)
+    return elbo
+
+
 def _load_alis(path):
     '''alis.npz: one `.npy` object array [CompiledGraph] per utterance
     (mkaligraph.py:60-63, accumulate.py:35,50).  Loaded eagerly; archives
@@ -450,21 +471,8 @@ class accumulate:
         alis = _load_alis(args.alis)
         uttids = [line.strip().split()[0] for line in sys.stdin if line.strip()]
         feats, graphs, kept = _shard(model, dataset, uttids, alis, logger)
-        elbo = beer.evidence_lower_bound(datasize=dataset.size)
         count = len(kept)
-        # Utterances with an alignment graph train the emissions only (the phone
-        # weights get no counts: phoneloop.py:98-100); those without one go through
-        # the free phone loop and DO count phones, as the reference's per-utterance
-        # `inference_graph=None` does (accumulate.py:45-54): two batches, one sum.
-        aligned = [i for i, g in enumerate(graphs) if g is not None]
-        free = [i for i, g in enumerate(graphs) if g is None]
-        if aligned:
-            elbo = elbo + beer.accumulate_elbo(
-                model, [feats[i] for i in aligned], datasize=dataset.size,
-                inference_graphs=[graphs[i] for i in aligned], scale=args.acoustic_scale)
-        if free:
-            elbo = elbo + beer.accumulate_elbo(model, [feats[i] for i in free],
-                                               datasize=dataset.size, scale=args.acoustic_scale)
+        elbo = _shard_elbo(model, feats, graphs, dataset.size, args.acoustic_scale)
         _dump((_cpu_elbo(elbo), count), args.out)
         norm = max(count, 1) * dataset.size
         logger.info(f'accumulated ELBO over {count} utterances: {float(elbo) / norm :.3f}.')
@@ -509,6 +517,7 @@ class train:
 
     @staticmethod
     def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
         parser.add_argument('-b', '--batch-size', type=int, default=-1,
                             help='utterances per update (-1: all)')
         parser.add_argument('-e', '--epochs', type=int, default=1)
@@ -524,14 +533,19 @@ class train:
         model = _load(args.model).to(_device())
         dataset = _load(args.dataset)
         optim = beer.VBConjugateOptimizer(model.mean_field_factorization(), lrate=args.lrate)
+        alis = _load_alis(args.alis)
         for epoch in range(1, args.epochs + 1):
             utts = list(dataset.utterances())
             bsize = len(utts) if args.batch_size <= 0 else args.batch_size
             for b in range(0, len(utts), bsize):
                 batch = utts[b:b + bsize]
                 optim.init_step()
-                elbo = beer.accumulate_elbo(model, [u.features for u in batch],
-                                            datasize=dataset.size)
+                if alis is None:
+                    elbo = beer.accumulate_elbo(model, [u.features for u in batch],
+                                                datasize=dataset.size)
+                else:
+                    feats, graphs, _ = _shard(model, dataset, [u.id for u in batch], alis, logger)
+                    elbo = _shard_elbo(model, feats, graphs, dataset.size, 1.)
                 elbo.backward()
                 optim.step()
                 logger.info(f'epoch={epoch} batch={b // bsize + 1} '

@@ -332,6 +332,45 @@ int beer_aligraphs_compile(int32_t n_units, const int32_t* unit_state_off,
     return BEER_OK;
 }
 
+int beer_graphset_from_csr(int64_t n_graphs, const int64_t* state_off, const int64_t* arc_off,
+                           const float* init, const float* fin, const int32_t* pdf_ids,
+                           const int32_t* arc_src, const int32_t* arc_dst,
+                           const float* arc_prob, beer_graphset** out) {
+    if (n_graphs < 0 || !state_off || !arc_off || !out) return BEER_EINVAL;
+    if (n_graphs > 0 && (!init || !fin || !pdf_ids)) return BEER_EINVAL;
+    beer_graphset* set = new (std::nothrow) beer_graphset;
+    if (!set) return BEER_EINVAL;
+    set->graphs.resize((size_t)n_graphs);
+    for (int64_t i = 0; i < n_graphs; ++i) {
+        const int64_t s0 = state_off[i], S = state_off[i + 1] - s0;
+        const int64_t a0 = arc_off[i], A = arc_off[i + 1] - a0;
+        bool ok = S >= 1 && S <= INT32_MAX && A >= 0 && A <= INT32_MAX &&
+                  (A == 0 || (arc_src && arc_dst && arc_prob));
+        for (int64_t a = 0; ok && a < A; ++a) {
+            const int32_t s = arc_src[a0 + a], d = arc_dst[a0 + a];
+            ok = s >= 0 && s < S && d >= 0 && d < S &&
+                 (a == 0 || arc_src[a0 + a - 1] < s ||
+                  (arc_src[a0 + a - 1] == s && arc_dst[a0 + a - 1] < d));
+        }
+        if (!ok) {
+            delete set;
+            return BEER_EINVAL;
+        }
+        CGraph& g = set->graphs[(size_t)i];
+        g.S = (int32_t)S;
+        g.init.assign(init + s0, init + s0 + S);
+        g.fin.assign(fin + s0, fin + s0 + S);
+        g.pdf.assign(pdf_ids + s0, pdf_ids + s0 + S);
+        if (A) {
+            g.asrc.assign(arc_src + a0, arc_src + a0 + A);
+            g.adst.assign(arc_dst + a0, arc_dst + a0 + A);
+            g.aprob.assign(arc_prob + a0, arc_prob + a0 + A);
+        }
+    }
+    *out = set;
+    return BEER_OK;
+}
+
 int beer_graphset_free(beer_graphset* set) {
     delete set;
     return BEER_OK;

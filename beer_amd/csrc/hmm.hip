@@ -179,11 +179,15 @@ template <bool BIG> struct FbIdx { typedef int16_t type; };
 template <> struct FbIdx<true> { typedef int32_t type; };
 constexpr int kFbBigBlocks = 512;
 
-template <typename T, bool BIG>
+// MAP: `xi_sum` is the [n_categories] counts of learned transitions and every arc's sum goes to
+// its category (beer_cat_map) instead of its cell of a dense [S, S] matrix -- any graph per
+// utterance; the instantiations without it are the code they were.
+template <typename T, bool BIG, bool MAP = false>
 __device__ __forceinline__ void fb_utterance(
     const beer_batch& b, int u, const T* __restrict__ pc_llhs, double* __restrict__ alpha_ws,
     T* __restrict__ gamma, double* __restrict__ xi_sum, double* __restrict__ gamma0_sum,
-    T* __restrict__ lognorm_mean, double* __restrict__ arc_ws, char* smem) {
+    T* __restrict__ lognorm_mean, double* __restrict__ arc_ws, char* smem,
+    const beer_cat_map* cm = nullptr) {
     typedef typename FbIdx<BIG>::type idx_t;
     const int tid = threadIdx.x, nt_ = blockDim.x;
     const beer_graph g = b.graphs[b.graph_id[u]];
@@ -382,8 +386,14 @@ __device__ __forceinline__ void fb_utterance(
     if (lognorm_mean && tid == 0) lognorm_mean[u] = (T)(ln_acc / (double)T_);
     if (xi_sum) {
         __syncthreads();
-        for (int e = tid; e < nnz; e += nt_)
-            atomicAdd(xi_sum + (size_t)src_out[e] * S + dst_out[e], xi[e]);
+        if constexpr (MAP) {
+            const int32_t* ac = cm->arc_cat + cm->arc_off[b.graph_id[u]];
+            for (int e = tid; e < nnz; e += nt_)
+                if (xi[e] != 0.0) atomicAdd(xi_sum + ac[e], xi[e]);
+        } else {
+            for (int e = tid; e < nnz; e += nt_)
+                atomicAdd(xi_sum + (size_t)src_out[e] * S + dst_out[e], xi[e]);
+        }
     }
 }
 
@@ -397,6 +407,20 @@ __global__ __launch_bounds__(kFbThreads) void fb_kernel(
         fb_utterance<T, BIG>(b, u, pc_llhs, alpha_ws, gamma, xi_sum, gamma0_sum, lognorm_mean,
                              arc_ws, smem);
         __syncthreads();                                         // LDS reused by the next one
+    }
+}
+
+// ... with the arcs' sums by category (`cat_counts`): a batch of different graphs
+template <typename T, bool BIG>
+__global__ __launch_bounds__(kFbThreads) void fb_cat_kernel(
+    beer_batch b, const T* __restrict__ pc_llhs, double* __restrict__ alpha_ws,
+    T* __restrict__ gamma, double* __restrict__ cat_counts, double* __restrict__ gamma0_sum,
+    T* __restrict__ lognorm_mean, double* __restrict__ arc_ws, beer_cat_map cm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    for (int u = blockIdx.x; u < b.nutt; u += gridDim.x) {
+        fb_utterance<T, BIG, true>(b, u, pc_llhs, alpha_ws, gamma, cat_counts, gamma0_sum,
+                                   lognorm_mean, arc_ws, smem, &cm);
+        __syncthreads();
     }
 }
 
@@ -419,11 +443,12 @@ __device__ __forceinline__ double logaddexp2(double a, double b) {
     return m + flog<T>(fexp<T>(a - m) + fexp<T>(b - m));
 }
 
-template <typename T>
+// (MAP: as fb_utterance's -- `xi_sum` is the counts by category, `cm` the maps)
+template <typename T, bool MAP = false>
 __global__ __launch_bounds__(kLdThreads) void fb_lowdeg_kernel(
     beer_batch b, const T* __restrict__ pc_llhs, double* __restrict__ alpha_ws,
     T* __restrict__ gamma, double* __restrict__ xi_sum, double* __restrict__ gamma0_sum,
-    double* __restrict__ hub_flow, T* __restrict__ lognorm_mean) {
+    double* __restrict__ hub_flow, T* __restrict__ lognorm_mean, beer_cat_map cm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -714,7 +739,12 @@ __global__ __launch_bounds__(kLdThreads) void fb_lowdeg_kernel(
     if (xi_sum && st) {
 #pragma unroll
         for (int k = 0; k < BEER_SEG; ++k)
-            if (ow[k] > NINF && xi_r[k] != 0.0) atomicAdd(xi_sum + (size_t)j * S + odst[k], xi_r[k]);
+            if (ow[k] > NINF && xi_r[k] != 0.0) {
+                if constexpr (MAP)
+                    atomicAdd(xi_sum + cm.arc_cat[cm.arc_off[b.graph_id[u]] + out_beg + k], xi_r[k]);
+                else
+                    atomicAdd(xi_sum + (size_t)j * S + odst[k], xi_r[k]);
+            }
         if (hd >= 0 && hub_flow) atomicAdd(hub_flow + j, flow_r);
     }
 }
@@ -859,13 +889,17 @@ constexpr int kWvRowMax = 512;
 // last frame (the utterance ends by leaving j; 0 where the final weight is 0).
 // (CNT is compiled for one wave per SIMD less: the per-arc sums and the source flows take the
 // registers that kept the recipe's shape, 120 states on two slots a lane, from spilling)
-template <typename T, int SPL, int DEG, bool FUSED, bool XI, int OUTM, bool CNT>
+// CNT == 2 (alignment graphs, any graph per utterance): the same sums BY CATEGORY -- `arc_counts`
+// is the [n_categories] array, an arc's sum goes to arc_cat, the last frame's posterior to last_cat
+// (beer_cat_map `cm`; these graphs have no hub, so that posterior is all of the source flow).
+// Instantiations of their own: CNT == 0 / 1 are the code they were.
+template <typename T, int SPL, int DEG, bool FUSED, bool XI, int OUTM, int CNT>
 __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWaves) void fb_wave_kernel(
     beer_batch b, const T* __restrict__ pc, int S_total, T scale, double* __restrict__ alpha_ws,
     double* __restrict__ hubf_ws, T* __restrict__ out, T resp_scale,
     double* __restrict__ xi_sum, double* __restrict__ gamma0_sum, double* __restrict__ hub_flow,
     double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh,
-    double* __restrict__ arc_counts, double* __restrict__ src_flow) {
+    double* __restrict__ arc_counts, double* __restrict__ src_flow, beer_cat_map cm) {
     static_assert(!CNT || XI, "the counts are the per-arc sums of xi");
     typedef Lin<T> R;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1339,7 +1373,14 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
                 if (ow[p][k] > 0.0 && xi_r[p][k] != 0.0)
                     atomicAdd(xi_sum + (size_t)j * S + (odst[p][k] - lb0) / 8, xi_r[p][k]);
         }
-        if constexpr (CNT) {
+        if constexpr (CNT == 2) {
+            const int32_t* ac = cm.arc_cat + cm.arc_off[gid] + L.out_ptr[j];
+#pragma unroll
+            for (int k = 0; k < DEG; ++k)
+                if (ow[p][k] > 0.0 && xi_r[p][k] != 0.0) atomicAdd(arc_counts + ac[k], xi_r[p][k]);
+            const int lc = cm.last_cat[cm.state_off[gid] + j];
+            if (lc >= 0 && sf_r[p] != 0.0) atomicAdd(arc_counts + lc, sf_r[p]);
+        } else if constexpr (CNT == 1) {
             const int ob = L.out_ptr[j];
 #pragma unroll
             for (int k = 0; k < DEG; ++k)
@@ -1394,13 +1435,13 @@ __device__ __forceinline__ double rel_base(R m) {
     return m > (R)-INFINITY ? (double)m : 0.0;
 }
 
-template <typename T, int SPL, int DEG, bool FUSED, bool XI, bool CNT>
+template <typename T, int SPL, int DEG, bool FUSED, bool XI, int CNT>
 __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
     beer_batch b, const T* __restrict__ pc, int S_total, T scale, double* __restrict__ alpha_ws,
     double* __restrict__ hubf_ws, T* __restrict__ out, T resp_scale, int atomic_out,
     double* __restrict__ xi_sum, double* __restrict__ gamma0_sum, double* __restrict__ hub_flow,
     double* __restrict__ utt_llh, T* __restrict__ lognorm_mean, T* __restrict__ frame_llh,
-    double* __restrict__ arc_counts, double* __restrict__ src_flow) {
+    double* __restrict__ arc_counts, double* __restrict__ src_flow, beer_cat_map cm) {
     static_assert(!CNT || XI, "the counts are the per-arc sums of xi");
     typedef Rel<T> R;
     typedef typename R::r_t r_t;
@@ -1748,7 +1789,14 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
                 if (ow[p][k] > ninf<T>() && xi_r[p][k] != 0.0)
                     atomicAdd(xi_sum + (size_t)j * S + (odst[p][k] - lb0) / 8, xi_r[p][k]);
         }
-        if constexpr (CNT) {
+        if constexpr (CNT == 2) {
+            const int32_t* ac = cm.arc_cat + cm.arc_off[gid] + L.out_ptr[j];
+#pragma unroll
+            for (int k = 0; k < DEG; ++k)
+                if (ow[p][k] > ninf<T>() && xi_r[p][k] != 0.0) atomicAdd(arc_counts + ac[k], xi_r[p][k]);
+            const int lc = cm.last_cat[cm.state_off[gid] + j];
+            if (lc >= 0 && sf_r[p] != 0.0) atomicAdd(arc_counts + lc, sf_r[p]);
+        } else if constexpr (CNT == 1) {
             const int ob = L.out_ptr[j];
 #pragma unroll
             for (int k = 0; k < DEG; ++k)
@@ -1976,6 +2024,66 @@ __global__ __launch_bounds__(256) void last_frame_kernel(beer_batch b, const T* 
     for (int s = threadIdx.x; s < S; s += blockDim.x) atomicAdd(out + s, (double)g[s]);
 }
 
+// ... by category, for a batch of different graphs (`cm`): cat[last_cat of the state] += its
+// posterior at the utterance's last frame
+template <typename T>
+__global__ __launch_bounds__(256) void last_frame_cat_kernel(beer_batch b, const T* __restrict__ gamma,
+                                                             beer_cat_map cm,
+                                                             double* __restrict__ cat_counts) {
+    const int u = blockIdx.x;
+    const int64_t T_ = b.frame_off[u + 1] - b.frame_off[u];
+    if (T_ <= 0) return;
+    const int gid = b.graph_id[u];
+    const int S = b.graphs[gid].n_states;
+    const T* g = gamma + b.llh_off[u] + (T_ - 1) * S;
+    const int32_t* lc = cm.last_cat + cm.state_off[gid];
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {
+        const double gv = (double)g[s];
+        if (lc[s] >= 0 && gv == gv && gv != 0.0) atomicAdd(cat_counts + lc[s], gv);
+    }
+}
+
+// The hard counts of a state path by category: one workgroup per utterance; the arc
+// (p_t, p_t+1) is looked up in the out-row of p_t (at most BEER_SEG arcs for the graphs the
+// one-wave kernels take, a short search otherwise)
+__global__ __launch_bounds__(256) void path_cat_kernel(beer_batch b, const int64_t* __restrict__ path,
+                                                       beer_cat_map cm,
+                                                       double* __restrict__ cat_counts) {
+    const int u = blockIdx.x;
+    const int gid = b.graph_id[u];
+    const beer_graph g = b.graphs[gid];
+    const int64_t f0 = b.frame_off[u], nt = b.frame_off[u + 1] - f0;
+    if (nt <= 0) return;
+    const int64_t* p = path + f0;
+    const int32_t* ac = cm.arc_cat + cm.arc_off[gid];
+    for (int64_t t = threadIdx.x; t < nt - 1; t += blockDim.x) {
+        const int64_t i = p[t], j = p[t + 1];
+        if (i < 0 || i >= g.n_states) continue;
+        for (int e = g.out_ptr[i]; e < g.out_ptr[i + 1]; ++e)
+            if (g.out_dst[e] == j) {
+                atomicAdd(cat_counts + ac[e], 1.0);
+                break;
+            }
+    }
+    if (threadIdx.x == 0) {
+        const int64_t e = p[nt - 1];
+        if (e >= 0 && e < g.n_states) {
+            const int lc = cm.last_cat[cm.state_off[gid] + e];
+            if (lc >= 0) atomicAdd(cat_counts + lc, 1.0);
+        }
+    }
+}
+
+// w[pos[i]] = log_a[cat[i]]: the weight arrays of a bound image rewritten by category
+template <typename T>
+__global__ __launch_bounds__(256) void refresh_weights_kernel(int64_t n, const int64_t* __restrict__ pos,
+                                                              const int32_t* __restrict__ cat,
+                                                              const T* __restrict__ log_a,
+                                                              T* __restrict__ image) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) image[pos[i]] = log_a[cat[i]];
+}
+
 // ---- launchers -------------------------------------------------------------
 
 template <typename T>
@@ -2045,10 +2153,11 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
                    double* hub_ws, T* out, T resp_scale, int atomic_out, double* xi_sum,
                    double* gamma0_sum, double* hub_flow, double* utt_llh, T* lognorm_mean,
                    T* frame_llh, hipStream_t s, double* arc_counts = nullptr,
-                   double* src_flow = nullptr) {
+                   double* src_flow = nullptr, const beer_cat_map* map = nullptr) {
     const dim3 grid((unsigned)((b->nutt + kWvWaves - 1) / kWvWaves)), block(64 * kWvWaves);
     const bool xi = !FUSED && xi_sum != nullptr;
     const bool cnt = arc_counts != nullptr;
+    const beer_cat_map cm = map ? *map : beer_cat_map{};
     const int spl = b->max_states <= 64 ? 1 : (b->max_states <= 128 ? 2 : 4);
     const int deg = b->max_degree <= 2 ? 2 : (b->max_degree <= 4 ? 4 : 8);
     const bool rows = FUSED && atomic_out == 2;
@@ -2066,21 +2175,21 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
             hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 2 : 0, CNT_>), \
                                grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
                                out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
-                               lognorm_mean, frame_llh, arc_counts, src_flow);                  \
+                               lognorm_mean, frame_llh, arc_counts, src_flow, cm);              \
         else if (FUSED && atomic_out)                                                           \
             hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 1 : 0, CNT_>), \
                                grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
                                out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
-                               lognorm_mean, frame_llh, arc_counts, src_flow);                  \
+                               lognorm_mean, frame_llh, arc_counts, src_flow, cm);              \
         else                                                                                    \
             hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, 0, CNT_>), grid,      \
                                block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out,    \
                                resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean, \
-                               frame_llh, arc_counts, src_flow);                                \
+                               frame_llh, arc_counts, src_flow, cm);                            \
         hipLaunchKernelGGL((fb_wave_log_kernel<T, SPL_, DEG_, FUSED, XI_, CNT_>), grid, block,  \
                            lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out, resp_scale,  \
                            atomic_out, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean,    \
-                           frame_llh, arc_counts, src_flow);                                   \
+                           frame_llh, arc_counts, src_flow, cm);                               \
     } while (0)
 #define BEER_WV_DEG(SPL_, XI_, CNT_)                                                            \
     do {                                                                                        \
@@ -2096,13 +2205,15 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
     } while (0)
     // (CNT: the transition counts of learned transition probabilities, new instantiations;
     //  the others are the kernels as they were)
-    if (cnt) {
-        BEER_WV_SPL(true, true);
+    if (cnt && map) {
+        BEER_WV_SPL(true, 2);
+    } else if (cnt) {
+        BEER_WV_SPL(true, 1);
     } else if constexpr (FUSED) {
-        BEER_WV_SPL(false, false);
+        BEER_WV_SPL(false, 0);
     } else {
-        if (xi) BEER_WV_SPL(true, false);
-        else BEER_WV_SPL(false, false);
+        if (xi) BEER_WV_SPL(true, 0);
+        else BEER_WV_SPL(false, 0);
     }
 #undef BEER_WV_SPL
 #undef BEER_WV_DEG
@@ -2179,6 +2290,127 @@ int beer_hmm_forward_backward_counts(int dtype, const beer_batch* b, const void*
                                          nullptr, s, arc_counts, src_flow);
 }
 
+static bool cat_map_ok(const beer_cat_map* m) {
+    return m && m->arc_cat && m->last_cat && m->arc_off && m->state_off;
+}
+
+int beer_hmm_refresh_weights(int dtype, int64_t n, const int64_t* pos, const int32_t* cat,
+                             const void* log_a, void* image, void* stream) {
+    BEER_REQUIRE(n >= 0 && (dtype == BEER_F32 || dtype == BEER_F64));
+    if (n == 0) return BEER_OK;
+    BEER_REQUIRE(pos && cat && log_a && image);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (dtype == BEER_F32)
+        hipLaunchKernelGGL(refresh_weights_kernel<float>, grid, dim3(256), 0, as_stream(stream), n,
+                           pos, cat, (const float*)log_a, (float*)image);
+    else
+        hipLaunchKernelGGL(refresh_weights_kernel<double>, grid, dim3(256), 0, as_stream(stream), n,
+                           pos, cat, (const double*)log_a, (double*)image);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+int beer_hmm_posteriors_fused_cat(int dtype, const beer_batch* b, int S_total, const void* pc_all,
+                                  double scale, double* alpha_ws, double* hub_ws,
+                                  void* state_resps, int atomic_out, double* gamma0_sum,
+                                  double* utt_llh, void* frame_llh, const beer_cat_map* map,
+                                  double* cat_counts, void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && S_total >= 1);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(wave_fb_ok(b) && b->max_hubs == 0);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_all && alpha_ws && hub_ws && state_resps && cat_counts && cat_map_ok(map));
+    hipStream_t s = as_stream(stream);
+    if (dtype == BEER_F32)
+        return wave_fb_launch<float, true>(b, (const float*)pc_all, S_total, (float)scale,
+                                           alpha_ws, hub_ws, (float*)state_resps, (float)scale,
+                                           atomic_out, nullptr, gamma0_sum, nullptr, utt_llh,
+                                           nullptr, (float*)frame_llh, s, cat_counts, nullptr, map);
+    return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
+                                        hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
+                                        gamma0_sum, nullptr, utt_llh, nullptr, (double*)frame_llh,
+                                        s, cat_counts, nullptr, map);
+}
+
+int beer_hmm_forward_backward_cat(int dtype, const beer_batch* b, const void* pc_llhs,
+                                  double* alpha_ws, double* hub_ws, void* gamma,
+                                  double* gamma0_sum, const beer_cat_map* map,
+                                  double* cat_counts, void* lognorm_mean, void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && b->max_states <= 32767);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(b->max_hubs == 0);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_llhs && alpha_ws && gamma && cat_counts && cat_map_ok(map));
+    hipStream_t s = as_stream(stream);
+    if (wave_fb_ok(b) && hub_ws) {
+        if (dtype == BEER_F32)
+            return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
+                                                alpha_ws, hub_ws, (float*)gamma, 1.f, 0, nullptr,
+                                                gamma0_sum, nullptr, nullptr, (float*)lognorm_mean,
+                                                nullptr, s, cat_counts, nullptr, map);
+        return wave_fb_launch<double, false>(b, (const double*)pc_llhs, b->max_states, 1.0,
+                                             alpha_ws, hub_ws, (double*)gamma, 1.0, 0, nullptr,
+                                             gamma0_sum, nullptr, nullptr, (double*)lognorm_mean,
+                                             nullptr, s, cat_counts, nullptr, map);
+    }
+    // beyond the one-wave kernels: the workgroup kernels' per-arc sums by category, then the
+    // last frames' posteriors
+    if (b->all_lowdeg && b->max_states <= kLdThreads) {
+        const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
+        const int threads = b->max_states <= 128 ? 128 : (b->max_states <= 256 ? 256 : 512);
+        if (dtype == BEER_F32)
+            hipLaunchKernelGGL((fb_lowdeg_kernel<float, true>), dim3(b->nutt), dim3(threads), lds,
+                               s, *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, cat_counts,
+                               gamma0_sum, nullptr, (float*)lognorm_mean, *map);
+        else
+            hipLaunchKernelGGL((fb_lowdeg_kernel<double, true>), dim3(b->nutt), dim3(threads), lds,
+                               s, *b, (const double*)pc_llhs, alpha_ws, (double*)gamma, cat_counts,
+                               gamma0_sum, nullptr, (double*)lognorm_mean, *map);
+    } else {
+        const size_t lds = fb_lds_bytes(b, dtype, true, false);
+        const bool big = lds > kLdsBytes;
+#define BEER_FBC(T_, BIG_, LDS_, GRID_)                                                          \
+    do {                                                                                         \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fb_cat_kernel<T_, BIG_>),        \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
+        hipLaunchKernelGGL((fb_cat_kernel<T_, BIG_>), dim3(GRID_), dim3(kFbThreads), LDS_, s,    \
+                           *b, (const T_*)pc_llhs, alpha_ws, (T_*)gamma, cat_counts, gamma0_sum, \
+                           (T_*)lognorm_mean, hub_ws, *map);                                     \
+    } while (0)
+        if (!big) {
+            if (dtype == BEER_F32) BEER_FBC(float, false, lds, b->nutt);
+            else BEER_FBC(double, false, lds, b->nutt);
+        } else {
+            const size_t lds_big = fb_lds_bytes(b, dtype, true, true);
+            BEER_REQUIRE(lds_big <= kLdsBytes && hub_ws);
+            const int grid = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
+            if (dtype == BEER_F32) BEER_FBC(float, true, lds_big, grid);
+            else BEER_FBC(double, true, lds_big, grid);
+        }
+#undef BEER_FBC
+    }
+    BEER_LAUNCH_CHECK();
+    if (dtype == BEER_F32)
+        hipLaunchKernelGGL(last_frame_cat_kernel<float>, dim3(b->nutt), dim3(256), 0, s, *b,
+                           (const float*)gamma, *map, cat_counts);
+    else
+        hipLaunchKernelGGL(last_frame_cat_kernel<double>, dim3(b->nutt), dim3(256), 0, s, *b,
+                           (const double*)gamma, *map, cat_counts);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+int beer_hmm_path_counts_cat(const beer_batch* b, const int64_t* path, const beer_cat_map* map,
+                             double* cat_counts, void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(path && cat_counts && cat_map_ok(map));
+    hipLaunchKernelGGL(path_cat_kernel, dim3(b->nutt), dim3(256), 0, as_stream(stream), *b, path,
+                       *map, cat_counts);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
 int beer_hmm_last_frame_sum(int dtype, const beer_batch* b, const void* gamma, double* out,
                             void* stream) {
     BEER_REQUIRE(b && b->nutt >= 0 && b->n_graphs == 1);
@@ -2235,11 +2467,11 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llh
         if (dtype == BEER_F32)
             hipLaunchKernelGGL(fb_lowdeg_kernel<float>, dim3(b->nutt), dim3(threads), lds, s,
                                *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, xi_sum,
-                               gamma0_sum, hub_flow, (float*)lognorm_mean);
+                               gamma0_sum, hub_flow, (float*)lognorm_mean, beer_cat_map{});
         else
             hipLaunchKernelGGL(fb_lowdeg_kernel<double>, dim3(b->nutt), dim3(threads), lds, s,
                                *b, (const double*)pc_llhs, alpha_ws, (double*)gamma, xi_sum,
-                               gamma0_sum, hub_flow, (double*)lognorm_mean);
+                               gamma0_sum, hub_flow, (double*)lognorm_mean, beer_cat_map{});
         BEER_LAUNCH_CHECK();
         return BEER_OK;
     }

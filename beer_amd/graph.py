@@ -14,7 +14,8 @@ import torch
 
 from . import _hip
 
-__all__ = ['Graph', 'CompiledGraph', 'GraphSet', 'SparseGraph', 'compile_alignments']
+__all__ = ['Graph', 'CompiledGraph', 'GraphSet', 'SparseGraph', 'compile_alignments',
+           'BoundGraphSet', 'BoundGraph']
 
 
 class State:
@@ -287,6 +288,160 @@ class SparseGraph:
 
     def best_path(self, llhs):
         return CompiledGraph.best_path(self, llhs)
+
+
+class BoundGraph(SparseGraph):
+    '''One graph of a `BoundGraphSet`: an inference graph whose arcs are bound to the
+    categories of a model's learned transitions.  `arc_categories` / `final_categories` are
+    host arrays (no device needed): the category of every arc in (source, destination) order,
+    and per state the category its posterior at the last frame counts for, -1 for none.'''
+
+    @property
+    def arcs(self):
+        '(sources, destinations) of the arcs, sorted by (source, destination).'
+        src, dst, _ = self._arcs()
+        return src, dst
+
+    @property
+    def arc_categories(self):
+        o = self._set
+        return o.arc_cat[o.arc_off[self._i]:o.arc_off[self._i + 1]]
+
+    @property
+    def final_categories(self):
+        o = self._set
+        return o.last_cat[o.state_off[self._i]:o.state_off[self._i + 1]]
+
+
+def _csr_tables(graphs):
+    '''The tables of `beer_graphset_export` for a `GraphSet`, a list of `SparseGraph` or a
+    list of dense `CompiledGraph` (arcs sorted by (source, destination), float32
+    probabilities).'''
+    if isinstance(graphs, GraphSet):
+        o = graphs
+        return (o.state_off.copy(), o.arc_off.copy(), o.init, o.final, o.pdf_ids, o.arc_src,
+                o.arc_dst, o.arc_prob)
+    state_off, arc_off = [0], [0]
+    init, fin, pdf, src, dst, prob = [], [], [], [], [], []
+    for n, g in enumerate(graphs):
+        if isinstance(g, SparseGraph):
+            o, i = g._set, g._i
+            s0, s1 = o.state_off[i], o.state_off[i + 1]
+            gi, gf, gp = o.init[s0:s1], o.final[s0:s1], o.pdf_ids[s0:s1]
+            gs, gd, gw = g._arcs()
+        elif isinstance(g, CompiledGraph):
+            trans = g.trans_log_probs.detach().to('cpu', torch.float32)
+            if g.pdf_id_mapping is None:
+                raise ValueError(f'alignment graph {n} has no pdf ids')
+            gp = np.asarray([int(i) for i in g.pdf_id_mapping], dtype=np.int32)
+            gi = g.init_log_probs.detach().to('cpu', torch.float32).exp().numpy()
+            gf = g.final_log_probs.detach().to('cpu', torch.float32).exp().numpy()
+            rows, cols = torch.nonzero(trans > -float('inf'), as_tuple=True)   # (row-major: sorted)
+            gs, gd = rows.numpy().astype(np.int32), cols.numpy().astype(np.int32)
+            gw = trans[rows, cols].exp().numpy()
+        else:
+            raise TypeError(f'alignment graph {n}: a SparseGraph or a CompiledGraph, not '
+                            f'{type(g).__name__}')
+        init.append(gi), fin.append(gf), pdf.append(gp)
+        src.append(gs), dst.append(gd), prob.append(gw)
+        state_off.append(state_off[-1] + len(gp))
+        arc_off.append(arc_off[-1] + len(gs))
+    cat = lambda parts, dt: np.ascontiguousarray(                                # noqa: E731
+        np.concatenate(parts) if parts else np.zeros(0), dtype=dt)
+    return (np.asarray(state_off, dtype=np.int64), np.asarray(arc_off, dtype=np.int64),
+            cat(init, np.float32), cat(fin, np.float32), cat(pdf, np.int32), cat(src, np.int32),
+            cat(dst, np.int32), cat(prob, np.float32))
+
+
+class BoundGraphSet(GraphSet):
+    '''Alignment graphs bound to the learned transitions of ONE model
+    (`HMM.bind_alignment_graphs`): a `GraphSet` of its own -- a native copy of the graphs'
+    tables with an arena image that no other set shares -- plus, per arc and per final state,
+    the category of the model's `HMMTransitions` it counts for.  Every weight of the image is
+    E[ln a] of its arc's category, rewritten on the device when the transitions have changed
+    (`refresh`, `beer_hmm_refresh_weights`); initial / final log-probabilities stay as
+    compiled.  A sequence: items are `BoundGraph`s, the same objects at every access.'''
+
+    is_bound = True
+
+    def __init__(self, tables, arc_cat, last_cat, transitions):
+        handle = ctypes.c_void_p()
+        state_off, arc_off = tables[0], tables[1]
+        keep = [np.ascontiguousarray(t) for t in tables]
+        _hip.call_host('beer_graphset_from_csr', len(state_off) - 1, *[_np_ptr(t) for t in keep],
+                       ctypes.byref(handle))
+        super().__init__(handle)
+        self.arc_cat = np.ascontiguousarray(arc_cat, dtype=np.int32)
+        self.last_cat = np.ascontiguousarray(last_cat, dtype=np.int32)
+        self.transitions = transitions
+        self.n_categories = len(transitions.cat_src)
+        self._items = [BoundGraph(self, i) for i in range(self.n)]
+        self._maps = {}                     # dtype -> device tensors of `refresh`
+        self._cat_dev = None
+
+    def __getitem__(self, i):
+        return self._items[i]               # (a slice: the list of those graphs)
+
+    def __iter__(self):
+        return iter(self._items)
+
+    def in_order(self):
+        '''Positions, in the (source, destination) arc order, of the arcs as the images' in-CSR
+        holds them (by destination, sources ascending), all graphs concatenated.'''
+        gidx = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.arc_off))
+        top = int(np.diff(self.state_off).max()) if self.n else 1
+        return np.argsort(gidx * top + self.arc_dst, kind='stable')
+
+    def cat_maps(self):
+        '(arc_cat, last_cat) int32 device tensors of the whole set (beer_cat_map).'
+        if self._cat_dev is None:
+            up = _hip.upload({'arc_cat': torch.from_numpy(self.arc_cat if len(self.arc_cat)
+                                                           else np.zeros(1, np.int32)),
+                              'last_cat': torch.from_numpy(self.last_cat)}, _hip.require_device())
+            self._cat_dev = (up['arc_cat'], up['last_cat'], up)
+        return self._cat_dev[:2]
+
+    def weight_positions(self, dtype):
+        '''(element positions in the image's blob [2 A] int64, categories [2 A] int32) of every
+        weight of the image in `dtype`: in_w of every graph, then out_w -- host arrays.'''
+        blob, structs = self.device_image(dtype)
+        size = ctypes.sizeof(_hip.Graph)
+        raw = np.frombuffer(structs, dtype=np.uint8).reshape(-1, size)[:self.n]
+        field = lambda f: np.ascontiguousarray(                                  # noqa: E731
+            raw[:, f.offset:f.offset + 8]).view(np.int64).reshape(-1)
+        isz = torch.empty(0, dtype=dtype).element_size()
+        counts = np.diff(self.arc_off)
+        local = np.arange(int(self.arc_off[-1]), dtype=np.int64) - np.repeat(self.arc_off[:-1], counts)
+        pos = [np.repeat((field(f) - blob.data_ptr()) // isz, counts) + local
+               for f in (_hip.Graph.in_w, _hip.Graph.out_w)]
+        return np.concatenate(pos), np.concatenate([self.arc_cat[self.in_order()], self.arc_cat])
+
+    def refresh(self, dtype):
+        '''The image in `dtype` with E[ln a] of the transitions as they are now, on the current
+        stream.  Nothing happens while the posteriors are the ones of the last refresh (the
+        token lives in their memos, which every update and every replayed recording drops).'''
+        self.cat_maps()
+        if dtype not in self._maps:
+            pos, cat = self.weight_positions(dtype)
+            up = _hip.upload({'pos': torch.from_numpy(pos), 'cat': torch.from_numpy(cat)},
+                             _hip.require_device())
+            self._maps[dtype] = (up['pos'], up['cat'], up)
+            stale = True
+        else:
+            stale = torch.cuda.is_current_stream_capturing()
+        key = ('bound_image', id(self), dtype)
+        for p in self.transitions.parameters_of_groups():
+            hit = []
+            p.posterior._memoised(key, lambda: hit.append(1) or True)
+            stale = stale or bool(hit)
+        if not stale:
+            return
+        pos, cat, _ = self._maps[dtype]
+        blob, _ = self.device_image(dtype)
+        log_a = self.transitions.log_probs().detach()
+        log_a = _hip.on_device(log_a, dtype)
+        _hip.call('beer_hmm_refresh_weights', _hip.dtype_code(dtype), pos.numel(), _hip.ptr(pos),
+                  _hip.ptr(cat), _hip.ptr(log_a), _hip.ptr(blob))
 
 
 def compile_alignments(sequences, units):

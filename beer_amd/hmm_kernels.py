@@ -89,12 +89,22 @@ class HmmBatch:
         # finish together, and a launch ends with its shortest utterances
         order = torch.argsort(lengths_t, descending=True, stable=True).to(torch.int32) \
             if self.nutt else torch.zeros(0, dtype=torch.int32)
+        # graphs bound to a model's learned transitions (`BoundGraphSet`): the category maps of
+        # beer_cat_map, every graph of the batch at its offsets in the set's arrays
+        owner = getattr(graphs[0], '_set', None) if len(graphs) else None
+        self.bound_set = owner if getattr(owner, 'is_bound', False) and \
+            all(getattr(g, '_set', None) is owner for g in graphs) else None
+        extra = {}
+        if self.bound_set is not None:
+            at = np.fromiter((g._i for g in graphs), dtype=np.int64, count=len(graphs))
+            extra = dict(cat_arc_off=torch.from_numpy(np.ascontiguousarray(owner.arc_off[at])),
+                         cat_state_off=torch.from_numpy(np.ascontiguousarray(owner.state_off[at])))
         self.bufs = _hip.upload(dict(
             frame_off=frame_off, llh_off=llh_off[:-1], graph_id=gid_t.to(torch.int32),
             order=order,
             graphs=graph_bytes,
             pdf_off=torch.as_tensor(np.asarray(pdf_off), dtype=torch.int32),
-            pdf_ids=torch.as_tensor(pdf_ids, dtype=torch.int32)), dev)
+            pdf_ids=torch.as_tensor(pdf_ids, dtype=torch.int32), **extra), dev)
         b = self.bufs
         self.struct = _hip.Batch(
             self.nutt, max(n_states) if n_states else 1, max(max_arcs, 1), max(max_segs, 1),
@@ -103,6 +113,10 @@ class HmmBatch:
             b['graphs'].data_ptr(), b['pdf_off'].data_ptr(), b['pdf_ids'].data_ptr(),
             *(ld_info if all_lowdeg else (0, 0, 0)), 0, b['order'].data_ptr())
         self.shared_graph = len(graphs) == 1
+        if self.bound_set is not None:
+            arc_cat, last_cat = owner.cat_maps()
+            self.cat_map = _hip.CatMap(arc_cat.data_ptr(), last_cat.data_ptr(),
+                                       b['cat_arc_off'].data_ptr(), b['cat_state_off'].data_ptr())
         self._pdf_ids_h, self._pdf_off_h = np.asarray(pdf_ids), np.asarray(pdf_off)
         self._profile = {}
 
@@ -256,7 +270,7 @@ FUSED_ROW_MAX = 512          # kWvRowMax of hmm.hip: pdf ids of a set that fit a
 
 
 def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, frame_llh=None,
-                     want_transitions=False):
+                     want_transitions=False, gamma0_sum=None):
     '''Gather + forward-backward + scatter of a shard in one launch
     (`beer_hmm_posteriors_fused`): (state_resps [n_frames, S_total] = scale *
     gamma at the pdf ids, gamma0_sum [S] or None, hub_flow [S] or None);
@@ -267,7 +281,10 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
     `want_transitions` (one graph): the same launch also counts the transitions of learned
     transition probabilities (`beer_hmm_posteriors_fused_counts`, every other output bit for
     bit the same) and a fourth value is returned: ('arcs', arc_counts, src_flow) -- see
-    `transition_counts`.'''
+    `transition_counts`.  A batch of graphs bound to the model (`HMM.bind_alignment_graphs`,
+    any graph per utterance) gives ('cat', counts by category, None) instead
+    (`beer_hmm_posteriors_fused_cat`).  `gamma0_sum` ([max states] fp64, +=): the first-frame
+    posteriors by state index into the caller's buffer, for batches of several graphs too.'''
     dt, dev = batch.dtype, batch.device
     pc_all = _hip.on_device(pc_all, dt)
     S_total = pc_all.shape[1]
@@ -287,12 +304,23 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
         S = batch.n_states[0]
         g0 = torch.zeros(S, dtype=torch.float64, device=dev)
         flow = torch.zeros(S, dtype=torch.float64, device=dev)
+    elif gamma0_sum is not None:
+        if gamma0_sum.dtype != torch.float64 or gamma0_sum.numel() < max(batch.n_states):
+            raise ValueError('gamma0_sum: an fp64 buffer of at least the largest graph\'s states')
+        g0 = gamma0_sum
     if frame_llh is not None and (frame_llh.dtype != dt or frame_llh.numel() != batch.n_frames or
                                   not frame_llh.is_contiguous() or frame_llh.device != sr.device):
         raise ValueError('frame_llh: a contiguous [n_frames] tensor of the batch\'s dtype and device')
     args = (_hip.dtype_code(dt), batch.ref(), S_total, _hip.ptr(pc_all), float(scale),
             _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(sr), out_mode, _hip.ptr(g0),
             _hip.ptr(flow), _hip.ptr(utt_llh), _hip.ptr(frame_llh))
+    if want_transitions and batch.bound_set is not None:
+        # alignment graphs bound to the model: the counts by category, any graph per utterance
+        cat_counts = _cat_buffer(batch)
+        _hip.call('beer_hmm_posteriors_fused_cat', *args[:9], _hip.ptr(g0), *args[11:],
+                  ctypes.byref(batch.cat_map), _hip.ptr(cat_counts))
+        counting_log_space.note(batch, hub_ws)
+        return sr, g0, flow, ('cat', cat_counts, None)
     if want_transitions:
         arc_counts, src_flow = _count_buffers(batch)
         _hip.call('beer_hmm_posteriors_fused_counts', *args, _hip.ptr(arc_counts),
@@ -312,6 +340,10 @@ def lowdeg_arcs(batch):
     if not batch.shared_graph or getattr(batch.dgraphs[0], 'lowdeg', None) is None:
         raise ValueError('transition counts need one graph with a low-degree image for the batch')
     return batch.dgraphs[0].lowdeg_arcs()
+
+
+def _cat_buffer(batch):
+    return torch.zeros(batch.bound_set.n_categories, dtype=torch.float64, device=batch.device)
 
 
 def _count_buffers(batch):
@@ -347,6 +379,22 @@ def forward_backward_counts(batch, pc_llhs):
     than 64 phones) the general kernel's dense xi_sum -- hub arcs in the matrix -- and the
     posteriors of the last frames: counts = ('dense', xi_sum, last).  See `transition_counts`.'''
     dt, dev = batch.dtype, batch.device
+    if batch.bound_set is not None:
+        # alignment graphs bound to the model (`beer_hmm_forward_backward_cat`): any graph per
+        # utterance, the one-wave kernels or -- beyond 256 states -- the workgroup kernels
+        cat_counts = _cat_buffer(batch)
+        gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
+        alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
+        n_ws = max(_hip.MAX_HUBS * batch.n_frames,
+                   _hip.lib().beer_hmm_fb_scratch_doubles(_hip.dtype_code(dt), batch.ref(), 1))
+        hub_ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+        _hip.call('beer_hmm_forward_backward_cat', _hip.dtype_code(dt), batch.ref(),
+                  _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma), None,
+                  ctypes.byref(batch.cat_map), _hip.ptr(cat_counts), None)
+        batch.last_alpha = alpha
+        batch.last_alpha_is_log = not fused_ok(batch)
+        counting_log_space.note(batch, hub_ws)
+        return gamma, None, None, None, ('cat', cat_counts, None)
     if not batch.shared_graph:
         raise ValueError('transition counts need one graph for the whole batch')
     if not fused_ok(batch):
@@ -372,6 +420,12 @@ def path_counts(batch, path, xi):
     '''The hard counts of a state path, ('dense', xi, last): the dense xi_sum of
     `path_posteriors(want_xi=True)` and how often each state ends an utterance.'''
     path = _hip.on_device(torch.as_tensor(path)).to(torch.int64).reshape(-1)
+    if batch.bound_set is not None:
+        # alignment graphs bound to the model: +1 at the category of every arc of the path
+        cat_counts = _cat_buffer(batch)
+        _hip.call('beer_hmm_path_counts_cat', batch.ref(), _hip.ptr(path.contiguous()),
+                  ctypes.byref(batch.cat_map), _hip.ptr(cat_counts))
+        return ('cat', cat_counts, None)
     last_states = path[batch.bufs['frame_off'][1:] - 1]
     last = torch.zeros(xi.shape[0], dtype=torch.float64, device=xi.device)
     last.index_add_(0, last_states, torch.ones(len(last_states), dtype=torch.float64,

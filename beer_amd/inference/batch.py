@@ -376,7 +376,9 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     # forward-backward launches, summed over the sub-batches in arc / state order
     learned = model.transitions is not None
     if learned and not free_loop:
-        model._refuse_transitions('alignment graphs (inference_graphs)')
+        # bound alignment graphs only (`HMM.bind_alignment_graphs`): E[ln a] on every arc of
+        # their image before the first recursion, counts by category out of the launches
+        model._bound_set(graphs).refresh(dtype)
     tcounts_tot = None
     bigram = free_loop and isinstance(model, BigramPhoneLoop)
     counts_tot = None
@@ -641,6 +643,10 @@ def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=
     paths = []
     max_S = model.graph.n_states if inference_graphs is None \
         else max(g.n_states for g in inference_graphs)
+    if inference_graphs is not None and len(inference_graphs) and \
+            getattr(getattr(inference_graphs[0], '_set', None), 'is_bound', False):
+        # graphs bound to learned transitions: E[ln a] on their arcs before the search
+        model._bound_set(inference_graphs).refresh(X.dtype)
     bpf = (K_max + S_total) * X.element_size() + max_S * (X.element_size() + 4)
     for run in _sub_batches(lengths, bpf, max_frames):
         f0, f1 = off[run[0]], off[run[-1] + 1]

@@ -307,6 +307,8 @@ class HMM(DiscreteLatentModel):
         `forward_backward_counts`, `path_counts`): ('arcs', arc_counts, src_flow) on the
         device image `dgraph` of the model's graph, or ('dense', xi_sum, last).'''
         kind, a, b = counts
+        if kind == 'cat':                   # (bound alignment graphs: by category already)
+            return a
         if kind == 'dense':
             return self.transitions.counts_from_dense(a, b)
         _, src, dst = self.transitions.intra()
@@ -317,7 +319,88 @@ class HMM(DiscreteLatentModel):
     def _refuse_transitions(what):
         raise ValueError(f'learned transitions (train_transitions=True) with {what} are not '
                          'supported: per-utterance graphs would need a category map per '
-                         'compiled arc')
+                         'compiled arc -- bind them to the model first '
+                         '(bound = model.bind_alignment_graphs(graphs), then pass bound / bound[u])')
+
+    def bind_alignment_graphs(self, graphs):
+        '''Alignment graphs bound to this model's learned transitions: a `BoundGraphSet`, a
+        sequence whose items stand wherever an inference graph is taken (`inference_graph=`,
+        `inference_graphs=`).  `graphs`: a `GraphSet`, a list of `SparseGraph` or a list of
+        dense `CompiledGraph`.  With s(p) the state of `self.graph` whose pdf id is p, an arc
+        with the pdf ids (p, q) counts for the category of the arc s(p) -> s(q) inside a unit,
+        else for the exit of s(p); a state with a final probability counts its last-frame
+        posterior for the exit of s(p) when it owns one.  ValueError: fixed transitions, a
+        pdf id that two states of the model share, an arc without a category, two arcs of one
+        state with the same category (an exit that branches: its compile-time branch
+        probabilities would be lost).  The set owns its device image; it is not pickled with
+        the model.'''
+        from ..graph import BoundGraphSet, _csr_tables
+        if self.transitions is None:
+            raise ValueError('bind_alignment_graphs: the transition probabilities of this model '
+                             'are not learned (create it with train_transitions=True)')
+        tables = _csr_tables(graphs)
+        arc_cat, last_cat = self._alignment_categories(*tables)
+        return BoundGraphSet(tables, arc_cat, last_cat, self.transitions)
+
+    def _alignment_categories(self, state_off, arc_off, init, fin, pdf, src, dst, prob):
+        'Host arrays: the category of every arc, and of every state\'s last-frame posterior.'
+        import numpy as np
+        own = self.graph.pdf_id_mapping
+        own = np.arange(self.graph.n_states) if own is None else \
+            np.asarray([int(i) for i in own], dtype=np.int64)
+        if len(np.unique(own)) != len(own):
+            raise ValueError('bind_alignment_graphs: the pdf_id_mapping of the model\'s graph '
+                             'repeats a pdf id; the states of an alignment graph cannot be told apart')
+        S = self.graph.n_states
+        state_of = np.full(max(int(own.max()), int(pdf.max()) if len(pdf) else 0) + 2, -1, np.int64)
+        state_of[own] = np.arange(S)
+        tr = self.transitions
+        intra = np.full((S, S), -1, dtype=np.int32)
+        exits = np.full(S + 1, -1, dtype=np.int32)          # (slot S: a pdf id the model lacks)
+        for c, (i, j) in enumerate(zip(tr.cat_src, tr.cat_dst)):
+            if j >= 0:
+                intra[i, j] = c
+            else:
+                exits[i] = c
+        n = len(state_off) - 1
+        gidx = np.repeat(np.arange(n, dtype=np.int64), np.diff(arc_off))
+        gsrc, gdst = state_off[gidx] + src, state_off[gidx] + dst
+        sp, sq = state_of[pdf[gsrc]], state_of[pdf[gdst]]
+        cat = np.where((sp >= 0) & (sq >= 0), intra[sp, sq], -1)
+        cat = np.where(cat < 0, exits[np.where(sp >= 0, sp, S)], cat).astype(np.int32)
+        bad = np.nonzero(cat < 0)[0]
+        if len(bad):
+            a = int(bad[0])
+            raise ValueError(f'bind_alignment_graphs: graph {int(gidx[a])}, arc {int(src[a])} -> '
+                             f'{int(dst[a])} (pdf ids {int(pdf[gsrc[a]])} -> {int(pdf[gdst[a]])}) '
+                             'is neither an arc inside a unit of the model nor leaves a unit\'s '
+                             'end state')
+        # (arcs are sorted by source: two arcs of one state with one category sort together)
+        order = np.lexsort((cat, gsrc))
+        same = (gsrc[order][1:] == gsrc[order][:-1]) & (cat[order][1:] == cat[order][:-1])
+        if same.any():
+            a = int(order[1:][same][0])
+            raise ValueError(f'bind_alignment_graphs: graph {int(gidx[a])}, state {int(src[a])} '
+                             f'(pdf id {int(pdf[gsrc[a]])}) has two arcs of one category (an exit '
+                             'that branches to two successors): the branch probabilities the '
+                             'graph was compiled with would be lost')
+        sl = state_of[pdf]
+        last = np.where(fin > 0, exits[np.where(sl >= 0, sl, S)], -1).astype(np.int32)
+        return cat, last
+
+    def _bound_set(self, graphs):
+        '''The `BoundGraphSet` every graph of `graphs` (one graph, a list, the set itself)
+        belongs to; ValueError unless they are bound to this model's transitions.'''
+        items = [graphs] if hasattr(graphs, 'n_states') else graphs
+        owner = graphs if getattr(graphs, 'is_bound', False) else \
+            (getattr(items[0], '_set', None) if len(items) else None)
+        if not getattr(owner, 'is_bound', False) or owner.transitions is not self.transitions:
+            self._refuse_transitions('alignment graphs (inference_graph) that are not bound to '
+                                     'this model')
+        if owner is not graphs and any(getattr(g, '_set', None) is not owner for g in items):
+            raise ValueError('learned transitions: the alignment graphs of one call must come '
+                             'from one bound set')
+        return owner
 
     # -- helpers ---------------------------------------------------------------
     def _emissions(self):
@@ -365,8 +448,9 @@ class HMM(DiscreteLatentModel):
         each decoded with the same graph, in one ragged batch.'''
         trans_posts = inference_graph is None
         learned = self.transitions is not None
-        if learned and inference_graph is not None:
-            self._refuse_transitions('alignment graphs (inference_graph)')
+        # (alignment graphs of a learned model: bound ones only -- checked before any device work)
+        bound = self._bound_set(inference_graph) if learned and inference_graph is not None \
+            else None
         self.cache.pop('trans_counts', None)
         graph = self.graph if inference_graph is None else inference_graph
         dense = kernels.is_dense(stats)
@@ -375,6 +459,9 @@ class HMM(DiscreteLatentModel):
         pc_all = emissions.expected_log_likelihood(stats.detach())
         self.modelset.cache['order'] = graph.pdf_id_mapping
         T, S_total = pc_all.shape
+        if bound is not None:
+            # (E[ln a] on every arc of the image before the recursion)
+            bound.refresh(pc_all.dtype)
         if utt_lengths is None:
             batch = self._batch_of_one(graph, T, pc_all.dtype)
         else:
@@ -477,6 +564,8 @@ class HMM(DiscreteLatentModel):
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
         pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
         pc_llhs = hk.gather(batch, pc_all, scale)
         return hk.viterbi(batch, pc_llhs, map_pdf=True).cpu()
@@ -486,6 +575,8 @@ class HMM(DiscreteLatentModel):
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.modelset.sufficient_statistics(data) * scale
         pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
         gamma = hk.forward_backward(batch, hk.gather(batch, pc_all, 1.))[0]
         return gamma.view(len(stats), -1)

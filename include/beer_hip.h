@@ -675,6 +675,53 @@ int beer_hmm_forward_backward_counts(int dtype, const beer_batch* batch_h, const
 int beer_hmm_last_frame_sum(int dtype, const beer_batch* batch_h, const void* gamma, double* out,
                             void* stream);
 
+/* Learned transition probabilities trained against ALIGNMENT GRAPHS (accumulate.py:39-59 with
+ * --alis; an extension like the counts above): every utterance has a graph of its own, and every
+ * arc of every graph is bound to a category of the model's transitions.  The maps are device
+ * arrays over the graphs of the batch, graph g of `beer_batch.graphs` at its own offsets:
+ *   arc_cat   category of every arc, in the graph's out-CSR order (by source, destinations
+ *             ascending: `out_ptr` / `out_dst`, which for these graphs is the low-degree
+ *             image's order too): arc a of graph g at arc_cat[arc_off[g] + a]
+ *   last_cat  per state, the category that receives its posterior at the LAST frame of an
+ *             utterance (the exit of the unit the state ends; the convention of `src_flow`
+ *             above), or -1: state j of graph g at last_cat[state_off[g] + j] */
+typedef struct {
+    const int32_t* arc_cat;
+    const int32_t* last_cat;
+    const int64_t* arc_off;    /* [n_graphs] */
+    const int64_t* state_off;  /* [n_graphs] */
+} beer_cat_map;
+
+/* w[pos[i]] = log_a[cat[i]] for i < n: every weight array of a bound image (in_w, out_w -- the
+ * low-degree image of an alignment graph reads the same two arrays) rewritten with E[ln a] of its
+ * arcs' categories.  `image` is the image's blob seen as an array of dtype, `pos` element
+ * positions in it, `log_a` [n_categories] of dtype.  Reads nothing on the host. */
+int beer_hmm_refresh_weights(int dtype, int64_t n, const int64_t* pos, const int32_t* cat,
+                             const void* log_a, void* image, void* stream);
+
+/* beer_hmm_posteriors_fused / beer_hmm_forward_backward with the transition counts BY CATEGORY
+ * of a batch of different graphs: cat_counts [n_categories] fp64, += the transition posteriors
+ * of every arc summed over frames and utterances, at the arc's category, and the last-frame
+ * posteriors at `last_cat`.  The recursions and every other output are those of the un-mapped
+ * calls on the same image, bit for bit.  beer_hmm_posteriors_fused_cat takes what
+ * beer_hmm_posteriors_fused takes (one-wave kernels); beer_hmm_forward_backward_cat every batch
+ * beer_hmm_forward_backward takes (beyond 256 states: the workgroup kernels).  `hub_ws` as for
+ * beer_hmm_forward_backward with transition posteriors (beer_hmm_fb_scratch_doubles). */
+int beer_hmm_posteriors_fused_cat(int dtype, const beer_batch* batch_h, int S_total,
+                                  const void* pc_all, double scale, double* alpha_ws,
+                                  double* hub_ws, void* state_resps, int atomic_out,
+                                  double* gamma0_sum, double* utt_llh, void* frame_llh,
+                                  const beer_cat_map* map, double* cat_counts, void* stream);
+int beer_hmm_forward_backward_cat(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                                  double* alpha_ws, double* hub_ws, void* gamma,
+                                  double* gamma0_sum, const beer_cat_map* map,
+                                  double* cat_counts, void* lognorm_mean, void* stream);
+/* The hard counts of a state path (viterbi=True / state_path=): cat_counts += 1 at the category
+ * of every arc (p_t, p_t+1) and at last_cat of every utterance's last state.  An arc is looked
+ * up in its source's out-row.  A pair of states that is not an arc counts nothing. */
+int beer_hmm_path_counts_cat(const beer_batch* batch_h, const int64_t* path,
+                             const beer_cat_map* map, double* cat_counts, void* stream);
+
 /* A phone loop with a BIGRAM language model (beer/models/phoneloop.py:104-191):
  * its end -> start block trans[src[i], dst[j]] = ln(1 - loop_i) + E[ln w][i, j] is a
  * full P x P matrix, kept apart from the rest of the graph (a low-degree CSR: the
@@ -968,6 +1015,15 @@ int beer_aligraphs_compile(int32_t n_units, const int32_t* unit_state_off,
                            beer_graphset** out);
 
 int beer_graphset_free(beer_graphset* set);
+
+/* A set from the tables beer_graphset_export gives (host arrays; offsets [n_graphs + 1]):
+ * how graphs that were compiled elsewhere -- dense CompiledGraph objects of an `alis.npz` --
+ * get an arena image, and how a set is copied so that the copy owns its image.  EINVAL
+ * unless every graph's arcs are sorted by (source, destination), distinct and in range. */
+int beer_graphset_from_csr(int64_t n_graphs, const int64_t* state_off, const int64_t* arc_off,
+                           const float* init, const float* fin, const int32_t* pdf_ids,
+                           const int32_t* arc_src, const int32_t* arc_dst,
+                           const float* arc_prob, beer_graphset** out);
 
 /* Number of graphs and (nullable) cumulative state / arc offsets [n+1]. */
 int beer_graphset_sizes(const beer_graphset* set, int64_t* n_graphs,
