@@ -79,6 +79,10 @@ __device__ __forceinline__ void mfma_bf16_pinned(f32x4& acc, const u4& a, const 
     else
         asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
+// (K1: 128 accumulators beside the fragments in one file of 256, two waves per SIMD)
+__device__ __forceinline__ void mfma_bf16_pinned_v(f32x4& acc, const u4& a, const u4& b) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+}
 // after the last pinned MFMA, before anything reads an accumulator
 __device__ __forceinline__ void mfma_drain() {
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -318,6 +322,17 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ X, int64_t 
     }
 }
 
+// A band table entry as the staged form of K1 (BL, below) keeps it in LDS: the five columns
+// its reads start at, ready-made, 6 bits each -- the aligned four at j, then w(b + step e),
+// e = 0 .. 3.  Rows of at most 64 floats (k1_lds_fits).  The arithmetic of band_col happens
+// once per workgroup instead of once per read.
+__device__ __forceinline__ int k1_slab_word(int t, int Dp) {
+    int w = t & 0xff;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w |= band_col(t, e, Dp) << (6 + 6 * e);
+    return w;
+}
+
 // ---------------------------------------------------------------------------
 // K1 on the bf16 pipes: one wave owns 16 MT frames x 16 NT components (a chunk of
 // the K components: blockIdx via xcd_block when there are several), at most 128
@@ -348,7 +363,7 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
     const u4* __restrict__ img = nullptr) {
     static_assert(MT * NT <= 32, "128 accumulators: two waves per SIMD (launch bounds)");
     static_assert(!IMG || (MT == 2 && !PACKED && LNO), "the image holds 32-frame tiles");
-    static_assert(!BL || (NT == 16 && MT == 2 && !IMG), "half k-steps of 8 tiles, hipcc-scheduled form");
+    static_assert(!BL || (NT == 16 && MT == 2 && !IMG && !SQ), "half k-steps of 8 tiles, band slabs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int LD = ld16_of(D);                                // 16-byte aligned rows
     const int Dp = 4 * d4_of(D);
@@ -370,7 +385,9 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
         if (nch > 1 && !xcd_block((nframes + FBK - 1) / FBK, nch, cg, bx, by)) return;
     }
     const int64_t fb = (bx * NW + wave) * FW;
-    for (int idx = tid; idx < (nk + 1) * 8; idx += kThreads) tabs[idx] = tab[idx];
+    // (BL: every column of a slab ready-made, k1_slab_word)
+    for (int idx = tid; idx < (nk + 1) * 8; idx += kThreads)
+        tabs[idx] = BL ? k1_slab_word(tab[idx], Dp) : tab[idx];
     if (!IMG) stage_rows<FW>(X, fb, nframes, D, LD, lane, xw);
     __syncthreads();
     if (IMG && fb >= nframes) return;
@@ -431,9 +448,10 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e) p[e] = bb[e] * (sq ? bb[e] : xx);     // v_cndmask, no branch
         } else {
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(xrow[m] + (t & 0xff));
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(xrow[m] + (t & (BL ? 0x3f : 0xff)));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) p[e] = bb[e] * xrow[m][band_col(t, e, Dp)];
+            for (int e = 0; e < 4; ++e)
+                p[e] = bb[e] * xrow[m][BL ? (t >> (6 + 6 * e)) & 0x3f : band_col(t, e, Dp)];
         }
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -482,17 +500,106 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     };
+    // (BL) The staged form issues its fragment work BETWEEN the MFMAs, by hand: an in-order wave
+    // gets two vector instructions per MFMA for free, but only there (`M v v M v v` 17.3 cycles
+    // per MFMA, `M M v v v v` 21.5: tools/probes/coissue.hip), and hipcc's scheduler gathers
+    // them into a few runs of 20 .. 90 (section 5.1b of DESIGN.md).  The MFMAs, the address
+    // arithmetic and the steps of the fragment arithmetic are volatile asm statements, which
+    // keep their order; the LDS reads are plain loads, which do not cross them.  A batch is
+    // 24 MFMAs; behind MFMA n of batch bi stands
+    //   n = 2k, bi even   k = 0: a table word (th[1] in batch 2; th[0], of the k-step after the
+    //                     next, in batch 6); k = 1 .. 6: the B fragments of the next batch;
+    //                     k = 7 .. 11: the address of read k - 7 of the slab the next batch loads;
+    //   n = 2k, bi odd    k = 0 .. 4: the reads of a slab of A -- the aligned four and the four
+    //                     wrapped columns of half hh = (h, m), raw[hh & 1] -- one batch ahead of
+    //                     its two units (half 0 in the last batch of the k-step before);
+    //                     k = 5 .. 10: the B fragments of the next batch;
+    //   n = 2k + 1        k = 0 .. 7: a step of the batch's unit = two products and their split,
+    //                     words 2h + e of tile m (4 MT units = NBATCH batches); a step and the
+    //                     one that uses its result are two MFMAs apart.
+    // Same products, same split, same order per accumulator: the bits of make_half + batch.
+    // Hazards (hipcc pads nothing inside asm): a fragment word is written at least 8 MFMAs
+    // before the first MFMA that reads it; the accumulators are read after mfma_drain().
+    static_assert(!BL || 4 * MT == NBATCH, "one unit of fragment arithmetic per batch");
+    struct ARaw { f32x4 bb; float xc[4]; };
+    typedef __attribute__((address_space(3))) const float* lds_cf;
+    typedef __attribute__((address_space(3))) const f32x4* lds_cf4;
+    ARaw raw[2];
+    int th[2];
+    unsigned ad[5], rowb[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) rowb[m] = (unsigned)(size_t)(lds_cf)xrow[m];
+    // LDS byte address of read k of a slab of tile m (k = 0: field 0, the aligned four)
+    auto addr_step = [&](int k, int m, int h) {
+#define BEER_AD(K_, LO_)                                                                     \
+    case K_:                                                                                 \
+        asm volatile("v_bfe_u32 %0, %1, " #LO_ ", 6\n\tv_lshl_add_u32 %0, %0, 2, %2"         \
+                     : "=&v"(ad[K_]) : "v"(th[h]), "v"(rowb[m]));                            \
+        break;
+        switch (k) {
+            BEER_AD(0, 0) BEER_AD(1, 6) BEER_AD(2, 12) BEER_AD(3, 18) BEER_AD(4, 24)
+            default: break;
+        }
+#undef BEER_AD
+    };
+    auto load_raw = [&](int k, ARaw& r) {
+        if (k == 0) r.bb = *(lds_cf4)ad[0];
+        else r.xc[k - 1] = *(lds_cf)ad[k];
+    };
+    auto batch_stream = [&](int s, int bi, const AFrag& cur, AFrag& nxt, const BFrag& b, BFrag& bn) {
+        // in front of the batches whose look-ahead read crosses into the other buffer:
+        // batch 3 (reads tile 8 of this k-step; buffer 0 has been read out: refill it with
+        // the first half of the next k-step), batch 7 (reads tile 0 of the next k-step;
+        // buffer 1 is free for its second half)
+        if (bi == NBATCH / 2 - 1 || bi == NBATCH - 1) {
+            publish();
+            const int hs = 2 * (s + 1) + (bi == NBATCH - 1 ? 1 : 0);
+            if (hs < 2 * nku) stage_half(hs);
+        }
+        const int bb0 = s * NT + (bi + 1) * BT;      // P is padded by one batch
+        const int hu = bi / 2, mu = hu % MT, wu = 2 * (hu / MT) + bi % 2, eu = bi % 2;
+        const ARaw& ru = raw[hu & 1];
+        const int hl = (bi / 2 + 1) % (MT * 2);      // the half that batch bi | 1 loads
+        float pp[2];
+        Split3Steps st;
+#pragma unroll
+        for (int n = 0; n < 6 * MT * BT; ++n) {
+            const int pr = n / (MT * BT), c = n / MT % BT, m = n % MT, k = n / 2;
+            mfma_bf16_pinned_v(acc[m][bi * BT + c], cur.w[kProdA[pr]][m], b.p[c][kProdB[pr]]);
+            if (n % 2 == 0) {
+                const int kb = bi % 2 ? k - 5 : k - 1;   // B fragments: piece-major, as they are used
+                if (kb >= 0 && kb < NP * BT) {
+                    const int blk = bb0 + kb % BT;
+                    bn.p[kb % BT][kb / BT] = *reinterpret_cast<const u4*>(
+                        ring + ((blk >> 3) & 1) * kHalfBytes + (blk & 7) * (kBlockU4 * 16) +
+                        (kb / BT) * 1024 + lane * 16);
+                } else if (bi % 2) {
+                    if (k < 5) load_raw(k, raw[hl & 1]);
+                } else if (k >= 7) {
+                    addr_step(k - 7, hl % MT, hl / MT);
+                } else if (bi == NBATCH / 2 - 2) {
+                    th[1] = tl[8 * (s + 1) + 1];
+                } else if (bi == NBATCH - 2) {
+                    // (the table is padded by ONE k-step: nothing is built from the last look-ahead)
+                    th[0] = tl[8 * min(s + 2, nk)];
+                }
+            } else if (k == 0) {
+                asm volatile("v_mul_f32 %0, %2, %3\n\tv_mul_f32 %1, %4, %5"
+                             : "=&v"(pp[0]), "=&v"(pp[1])
+                             : "v"(ru.bb[2 * eu]), "v"(ru.xc[2 * eu]), "v"(ru.bb[2 * eu + 1]),
+                               "v"(ru.xc[2 * eu + 1]));
+            } else if (k < 8) {
+                split3_step(k - 1, pp[0], pp[1], st);
+            }
+        }
+        nxt.w[0][mu][wu] = st.w0;
+        nxt.w[1][mu][wu] = st.w1;
+        nxt.w[2][mu][wu] = st.w2;
+    };
     auto batch = [&](int s, int bi, const AFrag& cur, AFrag& nxt, const BFrag& b, BFrag& bn) {
         if constexpr (BL) {
-            // in front of the batches whose look-ahead read crosses into the other buffer:
-            // batch 3 (reads tile 8 of this k-step; buffer 0 has been read out: refill it with
-            // the first half of the next k-step), batch 7 (reads tile 0 of the next k-step;
-            // buffer 1 is free for its second half)
-            if (bi == NBATCH / 2 - 1 || bi == NBATCH - 1) {
-                publish();
-                const int hs = 2 * (s + 1) + (bi == NBATCH - 1 ? 1 : 0);
-                if (hs < 2 * nku) stage_half(hs);
-            }
+            batch_stream(s, bi, cur, nxt, b, bn);
+            return;
         }
         // P is padded by one batch (bi + 1 = NBATCH: first batch of the next k-step)
         load_b((int64_t)s * NT + (bi + 1) * BT, bn);
@@ -511,10 +618,7 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
                 for (int m = 0; m < MT; ++m)
                     acc[m][bi * BT + c] = mfma_bf16(cur.w[kProdA[pr]][m], b.p[c][kProdB[pr]],
                                                     acc[m][bi * BT + c]);
-        if constexpr (BL)
-            __builtin_amdgcn_sched_group_barrier(0x100, NP * BT, 0);     // DS reads (B fragments)
-        else
-            __builtin_amdgcn_sched_group_barrier(0x020, NP * BT, 0);     // VMEM reads
+        __builtin_amdgcn_sched_group_barrier(0x020, NP * BT, 0);         // VMEM reads
         if constexpr (!IMG)
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * ((MT * 2 + NBATCH - 1) / NBATCH), 0);   // DS reads
         __builtin_amdgcn_sched_group_barrier(0x008, 6 * MT * BT, 0);     // MFMA
@@ -554,11 +658,24 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
         publish();
     }
     load_b(0, b0);
+    if constexpr (BL) {
+        // the look-ahead of k-step 0: half 0 of k-step 1; no compiler-placed write of a
+        // fragment or an accumulator next to the first pinned MFMA
+        th[0] = tl[8];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            addr_step(k, 0, 0);
+            load_raw(k, raw[0]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_nop 1");
+    }
     // (the image is padded to an even number of k-steps; only those that hold slabs run)
     for (int s = 0; s < nku; s += 2) {
         kstep(s, f0, f1, b0, b1);
         if (s + 1 < nku) kstep(s + 1, f1, f0, b0, b1);
     }
+    if constexpr (BL) mfma_drain();
     if constexpr (LNO) {
         // (jw == 4 by construction of the dispatch; gl = lanes per group, uniform; 0: the
         // image is lane-major, a group is G <= 16 registers of one lane)
@@ -591,7 +708,9 @@ __global__ __launch_bounds__(kThreads, 2) void llhx_kernel(
 }
 
 // Two workgroups of the LDS-staged form (BL) fit a CU: frame tiles + slab table + the ring
+// (rows of at most 64 floats: k1_slab_word; wider rows do not fit anyway)
 inline bool k1_lds_fits(int D, int nk) {
+    if (ld16_of(D) > 64) return false;
     size_t lds = (size_t)32 * (kThreads / 64) * ld16_of(D) * sizeof(float) + (size_t)(nk + 1) * 8 * sizeof(int);
     lds = ((lds + 1023) & ~(size_t)1023) + 2 * (size_t)(8 * kBlockU4 * 16);
     return 2 * lds <= (size_t)beer::kMaxDynLds;

@@ -6,7 +6,11 @@
 Compiles beer_amd/csrc/estep_bf16.hip with -DBEER_KERNEL_PROBE (only the hot kernels are
 instantiated) to assembly and prints, per kernel: registers, scratch, and for its
 MFMA-heaviest loop the instruction mix (MFMA, VALU, accvgpr moves, LDS, VMEM, scratch,
-waits, nops)."""
+waits, nops) and the histogram of run lengths: a run is the VALU and LDS instructions
+between two consecutive MFMAs (the loop taken as a cycle), `length:count`; an in-order wave
+issues up to two of them per MFMA for free, only there (tools/probes/coissue.hip).  Runs
+that hold an s_barrier are listed apart.  A first argument ending in .s is read as an
+assembly listing instead of compiling."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'beer_amd', 'csrc', 'estep_bf16.hip')
@@ -18,7 +22,10 @@ cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ml
        '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.dirname(SRC), '-S',
        '--cuda-device-only', SRC, '-o', OUT] + \
     (['-fno-slp-vectorize'] if SRC.endswith('estep_bf16.hip') else []) + sys.argv[1:]
-subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+if len(sys.argv) > 1 and sys.argv[1].endswith('.s'):        # a listing made earlier
+    OUT = sys.argv[1]
+else:
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 s = open(OUT).read()
 for f in re.split(r'\n\t\.globl\t', s)[1:]:
     name = f.split('\n', 1)[0].strip().split()[0]
@@ -51,3 +58,19 @@ for f in re.split(r'\n\t\.globl\t', s)[1:]:
               f"valu {c('v_') - n - c('v_accvgpr')} (pk {c('v_pk_')}) ds {c('ds_')} vmem {c('global_|buffer_')} "
               f"scratch {c('scratch_')} salu {c('s_') - c('s_waitcnt') - c('s_nop') - c('s_barrier')} "
               f"waitcnt {c('s_waitcnt')} nop {c('s_nop')} barrier {c('s_barrier')}")
+        runs, at_barrier, n_run, bar, first = {}, [], 0, False, None
+        for x in ins:
+            if x.startswith('v_mfma'):
+                if first is None:
+                    first = (n_run, bar)                     # closes the cycle with the tail
+                else:
+                    (at_barrier.append(n_run) if bar else runs.__setitem__(n_run, runs.get(n_run, 0) + 1))
+                n_run, bar = 0, False
+            elif x.startswith('s_barrier'):
+                bar = True
+            elif x.startswith(('v_', 'ds_')):
+                n_run += 1
+        n_run, bar = n_run + first[0], bar or first[1]
+        (at_barrier.append(n_run) if bar else runs.__setitem__(n_run, runs.get(n_run, 0) + 1))
+        print('   runs between MFMAs: ' + ' '.join(f'{k}:{v}' for k, v in sorted(runs.items())) +
+              (f' | at barriers: {sorted(at_barrier)}' if at_barrier else ''))
