@@ -144,6 +144,15 @@ class Bigram(ctypes.Structure):
                 ('src_slot', c_p), ('dst_slot', c_p), ('pdf_ids', c_p)]
 
 
+# BEER_FB_* of include/beer_hip.h: what `beer_hmm_fb_route` returns
+FB_WAVE, FB_LOWDEG, FB_GENERAL, FB_GENERAL_BIG = 0x1000, 0x2000, 0x3000, 0x4000
+
+
+def fb_family(route):
+    'BEER_FB_FAMILY: the kernel family of a `beer_hmm_fb_route` value.'
+    return route & 0xF000
+
+
 BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
 BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
 
@@ -228,6 +237,7 @@ SIGNATURES = {
     'beer_hmm_forward_backward_cat': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_counts_cat': [c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_fb_log_count': [c_p, c_p, c_p, c_p],
+    'beer_hmm_fb_route': [c_i, c_p, c_i, c_i],                     # (host only: no stream)
     'beer_hmm_posteriors_bigram': [c_i, c_p, ctypes.c_int32, c_l, c_p, c_p, c_i, c_p, c_d, c_p,
                                    c_p, c_p, c_i, c_p, c_p],
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],

@@ -2147,6 +2147,35 @@ inline bool wave_fb_ok(const beer_batch* b) {
     return b->all_lowdeg && b->max_states <= kWvMaxStates && b->max_degree >= 1 &&
            b->max_degree <= BEER_SEG && b->max_hubs <= 1 && b->max_hub_members <= 64;
 }
+// its template arguments: states per lane, and the arcs per state it unrolls
+inline int wave_fb_spl(const beer_batch* b) {
+    return b->max_states <= 64 ? 1 : (b->max_states <= 128 ? 2 : 4);
+}
+inline int wave_fb_deg(const beer_batch* b) {
+    return b->max_degree <= 2 ? 2 : (b->max_degree <= 4 ? 4 : 8);
+}
+// graphs the one-thread-per-state kernel takes, and its workgroup: at least two waves
+// (wave 1 recomputes the forward hub values)
+inline bool lowdeg_fb_ok(const beer_batch* b) {
+    return b->all_lowdeg && b->max_states <= kLdThreads;
+}
+inline int lowdeg_fb_threads(const beer_batch* b) {
+    return b->max_states <= 128 ? 128 : (b->max_states <= 256 ? 256 : 512);
+}
+// what beer_hmm_forward_backward accepts at all, and whether the factorised kernels can
+// report the transition posteriors it was asked for (through a hub they go to `hub_flow`)
+inline bool fb_batch_ok(int dtype, const beer_batch* b) {
+    return b && b->nutt >= 0 && b->max_states >= 1 && b->max_states <= 32767 &&
+           (dtype == BEER_F32 || dtype == BEER_F64);
+}
+inline bool fb_flow_ok(bool want_xi, bool have_hub_flow) { return !want_xi || have_hub_flow; }
+// the general kernel: the arc lists in LDS, or -- beyond it -- in global scratch
+inline bool fb_general_big(const beer_batch* b, int dtype, bool want_xi) {
+    return fb_lds_bytes(b, dtype, want_xi, false) > kLdsBytes;
+}
+inline bool fb_general_big_ok(const beer_batch* b, int dtype, bool want_xi) {
+    return fb_lds_bytes(b, dtype, want_xi, true) <= kLdsBytes;
+}
 
 template <typename T, bool FUSED>
 int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, double* alpha_ws,
@@ -2158,8 +2187,8 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
     const bool xi = !FUSED && xi_sum != nullptr;
     const bool cnt = arc_counts != nullptr;
     const beer_cat_map cm = map ? *map : beer_cat_map{};
-    const int spl = b->max_states <= 64 ? 1 : (b->max_states <= 128 ? 2 : 4);
-    const int deg = b->max_degree <= 2 ? 2 : (b->max_degree <= 4 ? 4 : 8);
+    const int spl = wave_fb_spl(b);
+    const int deg = wave_fb_deg(b);
     const bool rows = FUSED && atomic_out == 2;
     if (rows && S_total > kWvRowMax) return BEER_EINVAL;
     const size_t lds = (size_t)kWvWaves * 2 * 64 * spl * sizeof(double) +
@@ -2355,9 +2384,9 @@ int beer_hmm_forward_backward_cat(int dtype, const beer_batch* b, const void* pc
     }
     // beyond the one-wave kernels: the workgroup kernels' per-arc sums by category, then the
     // last frames' posteriors
-    if (b->all_lowdeg && b->max_states <= kLdThreads) {
+    if (lowdeg_fb_ok(b)) {
         const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
-        const int threads = b->max_states <= 128 ? 128 : (b->max_states <= 256 ? 256 : 512);
+        const int threads = lowdeg_fb_threads(b);
         if (dtype == BEER_F32)
             hipLaunchKernelGGL((fb_lowdeg_kernel<float, true>), dim3(b->nutt), dim3(threads), lds,
                                s, *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, cat_counts,
@@ -2368,7 +2397,7 @@ int beer_hmm_forward_backward_cat(int dtype, const beer_batch* b, const void* pc
                                gamma0_sum, nullptr, (double*)lognorm_mean, *map);
     } else {
         const size_t lds = fb_lds_bytes(b, dtype, true, false);
-        const bool big = lds > kLdsBytes;
+        const bool big = fb_general_big(b, dtype, true);
 #define BEER_FBC(T_, BIG_, LDS_, GRID_)                                                          \
     do {                                                                                         \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fb_cat_kernel<T_, BIG_>),        \
@@ -2382,7 +2411,7 @@ int beer_hmm_forward_backward_cat(int dtype, const beer_batch* b, const void* pc
             else BEER_FBC(double, false, lds, b->nutt);
         } else {
             const size_t lds_big = fb_lds_bytes(b, dtype, true, true);
-            BEER_REQUIRE(lds_big <= kLdsBytes && hub_ws);
+            BEER_REQUIRE(fb_general_big_ok(b, dtype, true) && hub_ws);
             const int grid = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
             if (dtype == BEER_F32) BEER_FBC(float, true, lds_big, grid);
             else BEER_FBC(double, true, lds_big, grid);
@@ -2443,11 +2472,12 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llh
                               double* alpha_ws, double* hub_ws, void* gamma, double* xi_sum,
                               double* gamma0_sum, double* hub_flow, void* lognorm_mean,
                               void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && b->max_states <= 32767);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(fb_batch_ok(dtype, b));
     if (b->nutt == 0) return BEER_OK;
     hipStream_t s = as_stream(stream);
-    if (wave_fb_ok(b) && hub_ws && (!xi_sum || hub_flow)) {
+    const bool want_xi = xi_sum != nullptr;
+    const bool flow_ok = fb_flow_ok(want_xi, hub_flow != nullptr);
+    if (wave_fb_ok(b) && hub_ws && flow_ok) {
         // one wave per utterance, no barriers
         if (dtype == BEER_F32)
             return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
@@ -2459,11 +2489,10 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llh
                                              gamma0_sum, hub_flow, nullptr,
                                              (double*)lognorm_mean, nullptr, s);
     }
-    if (b->all_lowdeg && b->max_states <= kLdThreads && (!xi_sum || hub_flow)) {
+    if (lowdeg_fb_ok(b) && flow_ok) {
         // factorised low-degree recursion: one thread per state
         const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
-        // at least two waves (wave 1 recomputes the forward hub values)
-        const int threads = b->max_states <= 128 ? 128 : (b->max_states <= 256 ? 256 : 512);
+        const int threads = lowdeg_fb_threads(b);
         if (dtype == BEER_F32)
             hipLaunchKernelGGL(fb_lowdeg_kernel<float>, dim3(b->nutt), dim3(threads), lds, s,
                                *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, xi_sum,
@@ -2475,8 +2504,8 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llh
         BEER_LAUNCH_CHECK();
         return BEER_OK;
     }
-    const size_t lds = fb_lds_bytes(b, dtype, xi_sum != nullptr, false);
-    const bool big = lds > kLdsBytes;
+    const size_t lds = fb_lds_bytes(b, dtype, want_xi, false);
+    const bool big = fb_general_big(b, dtype, want_xi);
 #define BEER_FB(T_, BIG_, LDS_, GRID_)                                                           \
     do {                                                                                         \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fb_kernel<T_, BIG_>),            \
@@ -2491,8 +2520,8 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llh
     } else {
         // arc lists beyond a CU's LDS: per-arc scratch in `hub_ws`
         // (beer_hmm_fb_scratch_doubles), the per-state arrays must still fit
-        const size_t lds_big = fb_lds_bytes(b, dtype, xi_sum != nullptr, true);
-        BEER_REQUIRE(lds_big <= kLdsBytes && hub_ws);
+        const size_t lds_big = fb_lds_bytes(b, dtype, want_xi, true);
+        BEER_REQUIRE(fb_general_big_ok(b, dtype, want_xi) && hub_ws);
         const int grid = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
         if (dtype == BEER_F32) BEER_FB(float, true, lds_big, grid);
         else BEER_FB(double, true, lds_big, grid);
@@ -2514,9 +2543,20 @@ int beer_hmm_fb_log_count(const beer_batch* b, const double* hub_ws, int64_t* co
     return BEER_OK;
 }
 
+int beer_hmm_fb_route(int dtype, const beer_batch* b, int want_xi, int have_hub_flow) {
+    BEER_REQUIRE(fb_batch_ok(dtype, b));
+    const bool flow_ok = fb_flow_ok(want_xi != 0, have_hub_flow != 0);
+    if (wave_fb_ok(b) && flow_ok)
+        return BEER_FB_WAVE | (wave_fb_spl(b) << 4) | wave_fb_deg(b);
+    if (lowdeg_fb_ok(b) && flow_ok) return BEER_FB_LOWDEG | lowdeg_fb_threads(b);
+    if (!fb_general_big(b, dtype, want_xi != 0)) return BEER_FB_GENERAL;
+    BEER_REQUIRE(fb_general_big_ok(b, dtype, want_xi != 0));
+    return BEER_FB_GENERAL_BIG;
+}
+
 size_t beer_hmm_fb_scratch_doubles(int dtype, const beer_batch* b, int want_xi) {
     if (!b || (dtype != BEER_F32 && dtype != BEER_F64) || b->nutt <= 0) return 0;
-    if (fb_lds_bytes(b, dtype, want_xi != 0, false) <= kLdsBytes) return 0;
+    if (!fb_general_big(b, dtype, want_xi != 0)) return 0;
     const size_t blocks = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
     return blocks * (2 * (size_t)b->max_arcs + (size_t)b->max_segs);
 }

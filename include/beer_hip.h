@@ -593,6 +593,27 @@ int beer_hmm_forward_backward(int dtype, const beer_batch* batch_h,
 int beer_hmm_fb_log_count(const beer_batch* batch_h, const double* hub_ws, int64_t* count,
                           void* stream);
 
+/* Which kernel family beer_hmm_forward_backward launches for this descriptor (host only: it
+ * reads the scalar fields of the batch and launches nothing), given a `hub_ws` workspace as
+ * above, transition posteriors asked for or not (`want_xi`: xi_sum != NULL) and, with them,
+ * `hub_flow` given or not.  The launcher decides with the same predicates.
+ *   BEER_FB_WAVE | SPL << 4 | DEG   one wave per utterance (linear domain, log-space twin):
+ *                                   SPL in {1, 2, 4} states per lane for at most 64 / 128 / 256
+ *                                   states, DEG in {2, 4, 8} arcs per state unrolled
+ *   BEER_FB_LOWDEG | threads        one thread per state, 128 / 256 / 512 threads: low-degree
+ *                                   images of up to 512 states, hubs of any size
+ *   BEER_FB_GENERAL                 the segment kernel, arc lists in LDS
+ *   BEER_FB_GENERAL_BIG             the segment kernel, per-arc scratch in `hub_ws`
+ *                                   (beer_hmm_fb_scratch_doubles > 0)
+ * BEER_EINVAL where beer_hmm_forward_backward refuses the batch.  BEER_FB_FAMILY(route) is
+ * the family alone.  The families other than BEER_FB_WAVE leave logarithms in `alpha_ws`. */
+#define BEER_FB_WAVE 0x1000
+#define BEER_FB_LOWDEG 0x2000
+#define BEER_FB_GENERAL 0x3000
+#define BEER_FB_GENERAL_BIG 0x4000
+#define BEER_FB_FAMILY(route) ((route) & 0xF000)
+int beer_hmm_fb_route(int dtype, const beer_batch* batch_h, int want_xi, int have_hub_flow);
+
 /* Doubles `hub_ws` of beer_hmm_forward_backward must hold BESIDES the hub values
  * (BEER_MAX_HUBS per frame) for this batch: 0 while the arc lists of its largest
  * graph fit a CU's LDS (about 4000 arcs with transition posteriors in float32);
