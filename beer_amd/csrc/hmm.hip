@@ -14,6 +14,8 @@
 // Reference restated: beer/graph.py:270-344, beer/models/hmm.py:40-121,
 // beer/models/modelset.py:140-154.
 
+#include <type_traits>
+
 #include "common.h"
 
 using namespace beer;
@@ -2177,49 +2179,67 @@ inline bool fb_general_big_ok(const beer_batch* b, int dtype, bool want_xi) {
     return fb_lds_bytes(b, dtype, want_xi, true) <= kLdsBytes;
 }
 
-template <typename T, bool FUSED>
-int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, double* alpha_ws,
-                   double* hub_ws, T* out, T resp_scale, int atomic_out, double* xi_sum,
-                   double* gamma0_sum, double* hub_flow, double* utt_llh, T* lognorm_mean,
-                   T* frame_llh, hipStream_t s, double* arc_counts = nullptr,
-                   double* src_flow = nullptr, const beer_cat_map* map = nullptr) {
+// The arguments of the forward-backward launchers by name, for the one-wave and the workgroup
+// kernels alike: an output the caller does not want stays null.
+struct FbArgs {
+    const void* pc = nullptr;           // pc_all [frames, S_total] (fused) or the packed pc_llhs
+    int S_total = 0;                    // (the packed calls: b->max_states)
+    double scale = 1., resp_scale = 1.;
+    double* alpha_ws = nullptr;
+    double* hub_ws = nullptr;
+    void* out = nullptr;                // state_resps (fused) or the packed gamma
+    int atomic_out = 0;
+    double* xi_sum = nullptr;
+    double* gamma0_sum = nullptr;
+    double* hub_flow = nullptr;
+    double* utt_llh = nullptr;
+    void* lognorm_mean = nullptr;
+    void* frame_llh = nullptr;
+    double* arc_counts = nullptr;       // (with `map`: the counts by category)
+    double* src_flow = nullptr;
+    const beer_cat_map* map = nullptr;
+    hipStream_t s = nullptr;
+};
+using Fused = std::true_type;           // gather + recursion + scatter in one launch
+using Packed = std::false_type;         // packed per-state likelihoods in, packed gamma out
+
+// the linear-domain kernel, then the log-space one for the utterances it flagged.  `outm`: how
+// a fused launch goes back to pdf ids (the packed launches exist with plain stores only: for
+// them the three names below are one instantiation)
+template <typename T, int SPL, int DEG, bool FUSED, bool XI, int CNT>
+void wave_fb_pair(const beer_batch* b, const FbArgs& a, const beer_cat_map& cm, size_t lds,
+                  int outm) {
     const dim3 grid((unsigned)((b->nutt + kWvWaves - 1) / kWvWaves)), block(64 * kWvWaves);
-    const bool xi = !FUSED && xi_sum != nullptr;
-    const bool cnt = arc_counts != nullptr;
-    const beer_cat_map cm = map ? *map : beer_cat_map{};
+    auto linear = fb_wave_kernel<T, SPL, DEG, FUSED, XI, FUSED ? 2 : 0, CNT>;
+    if (outm == 1) linear = fb_wave_kernel<T, SPL, DEG, FUSED, XI, FUSED ? 1 : 0, CNT>;
+    else if (outm == 0) linear = fb_wave_kernel<T, SPL, DEG, FUSED, XI, 0, CNT>;
+    if (beer::option(BEER_OPT_FB_LOG) != 0)
+        hipLaunchKernelGGL(fb_flag_all_kernel, dim3((unsigned)((b->nutt + 255) / 256)), dim3(256),
+                           0, a.s, *b, a.hub_ws);
+    else
+        hipLaunchKernelGGL(linear, grid, block, lds, a.s, *b, (const T*)a.pc, a.S_total,
+                           (T)a.scale, a.alpha_ws, a.hub_ws, (T*)a.out, (T)a.resp_scale, a.xi_sum,
+                           a.gamma0_sum, a.hub_flow, a.utt_llh, (T*)a.lognorm_mean,
+                           (T*)a.frame_llh, a.arc_counts, a.src_flow, cm);
+    hipLaunchKernelGGL((fb_wave_log_kernel<T, SPL, DEG, FUSED, XI, CNT>), grid, block, lds, a.s, *b,
+                       (const T*)a.pc, a.S_total, (T)a.scale, a.alpha_ws, a.hub_ws, (T*)a.out,
+                       (T)a.resp_scale, a.atomic_out, a.xi_sum, a.gamma0_sum, a.hub_flow,
+                       a.utt_llh, (T*)a.lognorm_mean, (T*)a.frame_llh, a.arc_counts, a.src_flow,
+                       cm);
+}
+
+template <typename T, bool FUSED>
+int wave_fb_launch(const beer_batch* b, const FbArgs& a, std::bool_constant<FUSED>) {
+    const bool xi = !FUSED && a.xi_sum != nullptr;
+    const bool cnt = a.arc_counts != nullptr;
+    const beer_cat_map cm = a.map ? *a.map : beer_cat_map{};
     const int spl = wave_fb_spl(b);
     const int deg = wave_fb_deg(b);
-    const bool rows = FUSED && atomic_out == 2;
-    if (rows && S_total > kWvRowMax) return BEER_EINVAL;
+    const int outm = !FUSED ? 0 : (a.atomic_out == 2 ? 2 : (a.atomic_out ? 1 : 0));
+    if (outm == 2 && a.S_total > kWvRowMax) return BEER_EINVAL;
     const size_t lds = (size_t)kWvWaves * 2 * 64 * spl * sizeof(double) +
-                       (rows ? (size_t)kWvWaves * kWvRowMax * sizeof(T) : 0);
-    const bool all_log = beer::option(BEER_OPT_FB_LOG) != 0;
-    // the linear-domain kernel, then the log-space one for the utterances it flagged
-#define BEER_WV(SPL_, DEG_, XI_, CNT_)                                                          \
-    do {                                                                                        \
-        if (all_log)                                                                            \
-            hipLaunchKernelGGL(fb_flag_all_kernel, dim3((unsigned)((b->nutt + 255) / 256)),     \
-                               dim3(256), 0, s, *b, hub_ws);                                    \
-        else if (rows)                                                                          \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 2 : 0, CNT_>), \
-                               grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
-                               out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
-                               lognorm_mean, frame_llh, arc_counts, src_flow, cm);              \
-        else if (FUSED && atomic_out)                                                           \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, FUSED ? 1 : 0, CNT_>), \
-                               grid, block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws,   \
-                               out, resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh,          \
-                               lognorm_mean, frame_llh, arc_counts, src_flow, cm);              \
-        else                                                                                    \
-            hipLaunchKernelGGL((fb_wave_kernel<T, SPL_, DEG_, FUSED, XI_, 0, CNT_>), grid,      \
-                               block, lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out,    \
-                               resp_scale, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean, \
-                               frame_llh, arc_counts, src_flow, cm);                            \
-        hipLaunchKernelGGL((fb_wave_log_kernel<T, SPL_, DEG_, FUSED, XI_, CNT_>), grid, block,  \
-                           lds, s, *b, pc, S_total, scale, alpha_ws, hub_ws, out, resp_scale,  \
-                           atomic_out, xi_sum, gamma0_sum, hub_flow, utt_llh, lognorm_mean,    \
-                           frame_llh, arc_counts, src_flow, cm);                               \
-    } while (0)
+                       (outm == 2 ? (size_t)kWvWaves * kWvRowMax * sizeof(T) : 0);
+#define BEER_WV(SPL_, DEG_, XI_, CNT_) wave_fb_pair<T, SPL_, DEG_, FUSED, XI_, CNT_>(b, a, cm, lds, outm)
 #define BEER_WV_DEG(SPL_, XI_, CNT_)                                                            \
     do {                                                                                        \
         if (deg == 2) BEER_WV(SPL_, 2, XI_, CNT_);                                              \
@@ -2234,7 +2254,7 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
     } while (0)
     // (CNT: the transition counts of learned transition probabilities, new instantiations;
     //  the others are the kernels as they were)
-    if (cnt && map) {
+    if (cnt && a.map) {
         BEER_WV_SPL(true, 2);
     } else if (cnt) {
         BEER_WV_SPL(true, 1);
@@ -2251,6 +2271,122 @@ int wave_fb_launch(const beer_batch* b, const T* pc, int S_total, T scale, doubl
     return BEER_OK;
 }
 
+// The workgroup kernels, beyond the one-wave ones: one thread per state (factorised low-degree
+// recursion), else the general kernel with its arc lists in LDS or -- beyond a CU's LDS -- in
+// the per-arc scratch of `hub_ws` (beer_hmm_fb_scratch_doubles; the per-state arrays must
+// still fit).  MAP: the per-arc sums go to `arc_counts` by category instead of `xi_sum`, then
+// the last frames' posteriors.
+template <typename T, bool MAP>
+int group_fb_launch(const beer_batch* b, const FbArgs& a, std::bool_constant<MAP>) {
+    constexpr int dtype = sizeof(T) == sizeof(float) ? BEER_F32 : BEER_F64;
+    const bool want_xi = MAP || a.xi_sum != nullptr;
+    double* sums = MAP ? a.arc_counts : a.xi_sum;
+    const beer_cat_map cm = MAP ? *a.map : beer_cat_map{};
+    if (lowdeg_fb_ok(b) && (MAP || fb_flow_ok(want_xi, a.hub_flow != nullptr))) {
+        const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
+        hipLaunchKernelGGL((fb_lowdeg_kernel<T, MAP>), dim3(b->nutt), dim3(lowdeg_fb_threads(b)),
+                           lds, a.s, *b, (const T*)a.pc, a.alpha_ws, (T*)a.out, sums,
+                           a.gamma0_sum, a.hub_flow, (T*)a.lognorm_mean, cm);
+    } else {
+        const bool big = fb_general_big(b, dtype, want_xi);
+        if (big) BEER_REQUIRE(fb_general_big_ok(b, dtype, want_xi) && a.hub_ws);
+        const size_t lds = fb_lds_bytes(b, dtype, want_xi, big);
+        const int grid = big && b->nutt > kFbBigBlocks ? kFbBigBlocks : b->nutt;
+        auto launch = [&](auto kernel, auto... map) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFbThreads), lds, a.s, *b, (const T*)a.pc,
+                               a.alpha_ws, (T*)a.out, sums, a.gamma0_sum, (T*)a.lognorm_mean,
+                               a.hub_ws, map...);
+        };
+        if constexpr (MAP) {
+            if (big) launch(fb_cat_kernel<T, true>, cm);
+            else launch(fb_cat_kernel<T, false>, cm);
+        } else {
+            if (big) launch(fb_kernel<T, true>);
+            else launch(fb_kernel<T, false>);
+        }
+    }
+    BEER_LAUNCH_CHECK();
+    if constexpr (MAP) {
+        hipLaunchKernelGGL(last_frame_cat_kernel<T>, dim3(b->nutt), dim3(256), 0, a.s, *b,
+                           (const T*)a.out, cm, a.arc_counts);
+        BEER_LAUNCH_CHECK();
+    }
+    return BEER_OK;
+}
+
+template <typename T>
+int refresh_weights_launch(int64_t n, const int64_t* pos, const int32_t* cat, const void* log_a,
+                           void* image, void* stream) {
+    BEER_REQUIRE(n >= 0);
+    if (n == 0) return BEER_OK;
+    BEER_REQUIRE(pos && cat && log_a && image);
+    hipLaunchKernelGGL(refresh_weights_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       as_stream(stream), n, pos, cat, (const T*)log_a, (T*)image);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T>
+int last_frame_launch(const beer_batch* b, const void* gamma, double* out, void* stream) {
+    BEER_REQUIRE(b && b->nutt >= 0 && b->n_graphs == 1);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(gamma && out);
+    hipLaunchKernelGGL(last_frame_kernel<T>, dim3(b->nutt), dim3(256), 0, as_stream(stream), *b,
+                       (const T*)gamma, out);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T>
+int xi_dense_launch(int64_t nframes, int S, const double* alpha, const void* llhs,
+                    const void* gamma, const void* trans, void* xi, void* stream) {
+    BEER_REQUIRE(nframes >= 0 && S >= 1);
+    if (nframes <= 1) return BEER_OK;
+    BEER_REQUIRE(alpha && llhs && gamma && trans && xi);
+    hipLaunchKernelGGL(xi_dense_kernel<T>, dim3((unsigned)(nframes - 1)), dim3(256), 0,
+                       as_stream(stream), nframes, S, alpha, (const T*)llhs, (const T*)gamma,
+                       (const T*)trans, (T*)xi);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+// (the caller has checked the batch and that it is not empty)
+template <typename T>
+int viterbi_launch(const beer_batch* b, const void* pc_llhs, int32_t* bt_ws, int64_t* path,
+                   int map_pdf, void* stream) {
+    // LDS: two trellis columns, a chunk of back-pointers and, when they fit, the arcs
+    const size_t base = (size_t)2 * b->max_states * sizeof(T) +
+                        (size_t)kViterbiChunk * b->max_states * sizeof(int32_t);
+    const size_t arcs = ((size_t)b->max_states + 2 + b->max_arcs) * sizeof(int32_t) +
+                        (size_t)b->max_arcs * sizeof(T);
+    BEER_REQUIRE(base <= 160 * 1024);
+    const int arcs_in_lds = base + arcs <= 64 * 1024;
+    const size_t lds = base + (arcs_in_lds ? arcs : 0);
+    // four lanes per state when 512 threads suffice for that, else 256 threads
+    const int vthreads = 4 * b->max_states <= kViterbiThreads ? kViterbiThreads : kHmmThreads;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(viterbi_kernel<T>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL(viterbi_kernel<T>, dim3(b->nutt), dim3(vthreads), lds, as_stream(stream),
+                       *b, (const T*)pc_llhs, bt_ws, path, map_pdf, arcs_in_lds);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T>
+int path_post_launch(const beer_batch* b, const int64_t* path, void* gamma, double* xi_sum,
+                     double* gamma0_sum, void* stream) {
+    hipLaunchKernelGGL(path_post_kernel<T>, dim3(b->nutt, 2), dim3(256), 0, as_stream(stream), *b,
+                       path, (T*)gamma, xi_sum, gamma0_sum);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+bool cat_map_ok(const beer_cat_map* m) {
+    return m && m->arc_cat && m->last_cat && m->arc_off && m->state_off;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2259,20 +2395,15 @@ int beer_hmm_posteriors_fused(int dtype, const beer_batch* b, int S_total, const
                               double scale, double* alpha_ws, double* hub_ws, void* state_resps,
                               int atomic_out, double* gamma0_sum, double* hub_flow,
                               double* utt_llh, void* frame_llh, void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && S_total >= 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(wave_fb_ok(b));
+    BEER_REQUIRE(fb_batch_ok(dtype, b) && S_total >= 1 && wave_fb_ok(b));
     if (b->nutt == 0) return BEER_OK;
     BEER_REQUIRE(pc_all && alpha_ws && hub_ws && state_resps);
-    hipStream_t s = as_stream(stream);
-    if (dtype == BEER_F32)
-        return wave_fb_launch<float, true>(b, (const float*)pc_all, S_total, (float)scale,
-                                           alpha_ws, hub_ws, (float*)state_resps, (float)scale,
-                                           atomic_out, nullptr, gamma0_sum, hub_flow, utt_llh,
-                                           nullptr, (float*)frame_llh, s);
-    return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
-                                        hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
-                                        gamma0_sum, hub_flow, utt_llh, nullptr, (double*)frame_llh, s);
+    FbArgs a;
+    a.pc = pc_all; a.S_total = S_total; a.scale = a.resp_scale = scale;
+    a.alpha_ws = alpha_ws; a.hub_ws = hub_ws; a.out = state_resps; a.atomic_out = atomic_out;
+    a.gamma0_sum = gamma0_sum; a.hub_flow = hub_flow; a.utt_llh = utt_llh;
+    a.frame_llh = frame_llh; a.s = as_stream(stream);
+    BEER_DISPATCH(dtype, wave_fb_launch, b, a, Fused{});
 }
 
 int beer_hmm_posteriors_fused_counts(int dtype, const beer_batch* b, int S_total,
@@ -2281,62 +2412,36 @@ int beer_hmm_posteriors_fused_counts(int dtype, const beer_batch* b, int S_total
                                      double* gamma0_sum, double* hub_flow, double* utt_llh,
                                      void* frame_llh, double* arc_counts, double* src_flow,
                                      void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && S_total >= 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(wave_fb_ok(b) && b->n_graphs == 1);
+    BEER_REQUIRE(fb_batch_ok(dtype, b) && S_total >= 1 && wave_fb_ok(b) && b->n_graphs == 1);
     if (b->nutt == 0) return BEER_OK;
     BEER_REQUIRE(pc_all && alpha_ws && hub_ws && state_resps && arc_counts && src_flow);
-    hipStream_t s = as_stream(stream);
-    if (dtype == BEER_F32)
-        return wave_fb_launch<float, true>(b, (const float*)pc_all, S_total, (float)scale,
-                                           alpha_ws, hub_ws, (float*)state_resps, (float)scale,
-                                           atomic_out, nullptr, gamma0_sum, hub_flow, utt_llh,
-                                           nullptr, (float*)frame_llh, s, arc_counts, src_flow);
-    return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
-                                        hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
-                                        gamma0_sum, hub_flow, utt_llh, nullptr, (double*)frame_llh,
-                                        s, arc_counts, src_flow);
+    FbArgs a;
+    a.pc = pc_all; a.S_total = S_total; a.scale = a.resp_scale = scale;
+    a.alpha_ws = alpha_ws; a.hub_ws = hub_ws; a.out = state_resps; a.atomic_out = atomic_out;
+    a.gamma0_sum = gamma0_sum; a.hub_flow = hub_flow; a.utt_llh = utt_llh;
+    a.frame_llh = frame_llh; a.arc_counts = arc_counts; a.src_flow = src_flow;
+    a.s = as_stream(stream);
+    BEER_DISPATCH(dtype, wave_fb_launch, b, a, Fused{});
 }
 
 int beer_hmm_forward_backward_counts(int dtype, const beer_batch* b, const void* pc_llhs,
                                      double* alpha_ws, double* hub_ws, void* gamma,
                                      double* gamma0_sum, double* hub_flow, double* arc_counts,
                                      double* src_flow, void* lognorm_mean, void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(wave_fb_ok(b) && b->n_graphs == 1);
+    BEER_REQUIRE(fb_batch_ok(dtype, b) && wave_fb_ok(b) && b->n_graphs == 1);
     if (b->nutt == 0) return BEER_OK;
     BEER_REQUIRE(pc_llhs && alpha_ws && hub_ws && gamma && arc_counts && src_flow);
-    hipStream_t s = as_stream(stream);
-    if (dtype == BEER_F32)
-        return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
-                                            alpha_ws, hub_ws, (float*)gamma, 1.f, 0, nullptr,
-                                            gamma0_sum, hub_flow, nullptr, (float*)lognorm_mean,
-                                            nullptr, s, arc_counts, src_flow);
-    return wave_fb_launch<double, false>(b, (const double*)pc_llhs, b->max_states, 1.0,
-                                         alpha_ws, hub_ws, (double*)gamma, 1.0, 0, nullptr,
-                                         gamma0_sum, hub_flow, nullptr, (double*)lognorm_mean,
-                                         nullptr, s, arc_counts, src_flow);
-}
-
-static bool cat_map_ok(const beer_cat_map* m) {
-    return m && m->arc_cat && m->last_cat && m->arc_off && m->state_off;
+    FbArgs a;
+    a.pc = pc_llhs; a.S_total = b->max_states; a.alpha_ws = alpha_ws; a.hub_ws = hub_ws;
+    a.out = gamma; a.gamma0_sum = gamma0_sum; a.hub_flow = hub_flow;
+    a.lognorm_mean = lognorm_mean; a.arc_counts = arc_counts; a.src_flow = src_flow;
+    a.s = as_stream(stream);
+    BEER_DISPATCH(dtype, wave_fb_launch, b, a, Packed{});
 }
 
 int beer_hmm_refresh_weights(int dtype, int64_t n, const int64_t* pos, const int32_t* cat,
                              const void* log_a, void* image, void* stream) {
-    BEER_REQUIRE(n >= 0 && (dtype == BEER_F32 || dtype == BEER_F64));
-    if (n == 0) return BEER_OK;
-    BEER_REQUIRE(pos && cat && log_a && image);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == BEER_F32)
-        hipLaunchKernelGGL(refresh_weights_kernel<float>, grid, dim3(256), 0, as_stream(stream), n,
-                           pos, cat, (const float*)log_a, (float*)image);
-    else
-        hipLaunchKernelGGL(refresh_weights_kernel<double>, grid, dim3(256), 0, as_stream(stream), n,
-                           pos, cat, (const double*)log_a, (double*)image);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    BEER_DISPATCH(dtype, refresh_weights_launch, n, pos, cat, log_a, image, stream);
 }
 
 int beer_hmm_posteriors_fused_cat(int dtype, const beer_batch* b, int S_total, const void* pc_all,
@@ -2344,89 +2449,37 @@ int beer_hmm_posteriors_fused_cat(int dtype, const beer_batch* b, int S_total, c
                                   void* state_resps, int atomic_out, double* gamma0_sum,
                                   double* utt_llh, void* frame_llh, const beer_cat_map* map,
                                   double* cat_counts, void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && S_total >= 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(wave_fb_ok(b) && b->max_hubs == 0);
+    BEER_REQUIRE(fb_batch_ok(dtype, b) && S_total >= 1 && wave_fb_ok(b) && b->max_hubs == 0);
     if (b->nutt == 0) return BEER_OK;
     BEER_REQUIRE(pc_all && alpha_ws && hub_ws && state_resps && cat_counts && cat_map_ok(map));
-    hipStream_t s = as_stream(stream);
-    if (dtype == BEER_F32)
-        return wave_fb_launch<float, true>(b, (const float*)pc_all, S_total, (float)scale,
-                                           alpha_ws, hub_ws, (float*)state_resps, (float)scale,
-                                           atomic_out, nullptr, gamma0_sum, nullptr, utt_llh,
-                                           nullptr, (float*)frame_llh, s, cat_counts, nullptr, map);
-    return wave_fb_launch<double, true>(b, (const double*)pc_all, S_total, scale, alpha_ws,
-                                        hub_ws, (double*)state_resps, scale, atomic_out, nullptr,
-                                        gamma0_sum, nullptr, utt_llh, nullptr, (double*)frame_llh,
-                                        s, cat_counts, nullptr, map);
+    FbArgs a;
+    a.pc = pc_all; a.S_total = S_total; a.scale = a.resp_scale = scale;
+    a.alpha_ws = alpha_ws; a.hub_ws = hub_ws; a.out = state_resps; a.atomic_out = atomic_out;
+    a.gamma0_sum = gamma0_sum; a.utt_llh = utt_llh; a.frame_llh = frame_llh;
+    a.arc_counts = cat_counts; a.map = map; a.s = as_stream(stream);
+    BEER_DISPATCH(dtype, wave_fb_launch, b, a, Fused{});
 }
+
+// (the order their device code is emitted in: float beside double, as it always was)
+[[maybe_unused]] static const void* const kGroupCatKernels[] = {
+    (const void*)fb_lowdeg_kernel<float, true>, (const void*)fb_lowdeg_kernel<double, true>,
+    (const void*)fb_cat_kernel<float, false>, (const void*)fb_cat_kernel<double, false>,
+    (const void*)fb_cat_kernel<float, true>, (const void*)fb_cat_kernel<double, true>,
+    (const void*)last_frame_cat_kernel<float>, (const void*)last_frame_cat_kernel<double>};
 
 int beer_hmm_forward_backward_cat(int dtype, const beer_batch* b, const void* pc_llhs,
                                   double* alpha_ws, double* hub_ws, void* gamma,
                                   double* gamma0_sum, const beer_cat_map* map,
                                   double* cat_counts, void* lognorm_mean, void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1 && b->max_states <= 32767);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(b->max_hubs == 0);
+    BEER_REQUIRE(fb_batch_ok(dtype, b) && b->max_hubs == 0);
     if (b->nutt == 0) return BEER_OK;
     BEER_REQUIRE(pc_llhs && alpha_ws && gamma && cat_counts && cat_map_ok(map));
-    hipStream_t s = as_stream(stream);
-    if (wave_fb_ok(b) && hub_ws) {
-        if (dtype == BEER_F32)
-            return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
-                                                alpha_ws, hub_ws, (float*)gamma, 1.f, 0, nullptr,
-                                                gamma0_sum, nullptr, nullptr, (float*)lognorm_mean,
-                                                nullptr, s, cat_counts, nullptr, map);
-        return wave_fb_launch<double, false>(b, (const double*)pc_llhs, b->max_states, 1.0,
-                                             alpha_ws, hub_ws, (double*)gamma, 1.0, 0, nullptr,
-                                             gamma0_sum, nullptr, nullptr, (double*)lognorm_mean,
-                                             nullptr, s, cat_counts, nullptr, map);
-    }
-    // beyond the one-wave kernels: the workgroup kernels' per-arc sums by category, then the
-    // last frames' posteriors
-    if (lowdeg_fb_ok(b)) {
-        const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
-        const int threads = lowdeg_fb_threads(b);
-        if (dtype == BEER_F32)
-            hipLaunchKernelGGL((fb_lowdeg_kernel<float, true>), dim3(b->nutt), dim3(threads), lds,
-                               s, *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, cat_counts,
-                               gamma0_sum, nullptr, (float*)lognorm_mean, *map);
-        else
-            hipLaunchKernelGGL((fb_lowdeg_kernel<double, true>), dim3(b->nutt), dim3(threads), lds,
-                               s, *b, (const double*)pc_llhs, alpha_ws, (double*)gamma, cat_counts,
-                               gamma0_sum, nullptr, (double*)lognorm_mean, *map);
-    } else {
-        const size_t lds = fb_lds_bytes(b, dtype, true, false);
-        const bool big = fb_general_big(b, dtype, true);
-#define BEER_FBC(T_, BIG_, LDS_, GRID_)                                                          \
-    do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fb_cat_kernel<T_, BIG_>),        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
-        hipLaunchKernelGGL((fb_cat_kernel<T_, BIG_>), dim3(GRID_), dim3(kFbThreads), LDS_, s,    \
-                           *b, (const T_*)pc_llhs, alpha_ws, (T_*)gamma, cat_counts, gamma0_sum, \
-                           (T_*)lognorm_mean, hub_ws, *map);                                     \
-    } while (0)
-        if (!big) {
-            if (dtype == BEER_F32) BEER_FBC(float, false, lds, b->nutt);
-            else BEER_FBC(double, false, lds, b->nutt);
-        } else {
-            const size_t lds_big = fb_lds_bytes(b, dtype, true, true);
-            BEER_REQUIRE(fb_general_big_ok(b, dtype, true) && hub_ws);
-            const int grid = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
-            if (dtype == BEER_F32) BEER_FBC(float, true, lds_big, grid);
-            else BEER_FBC(double, true, lds_big, grid);
-        }
-#undef BEER_FBC
-    }
-    BEER_LAUNCH_CHECK();
-    if (dtype == BEER_F32)
-        hipLaunchKernelGGL(last_frame_cat_kernel<float>, dim3(b->nutt), dim3(256), 0, s, *b,
-                           (const float*)gamma, *map, cat_counts);
-    else
-        hipLaunchKernelGGL(last_frame_cat_kernel<double>, dim3(b->nutt), dim3(256), 0, s, *b,
-                           (const double*)gamma, *map, cat_counts);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    FbArgs a;
+    a.pc = pc_llhs; a.S_total = b->max_states; a.alpha_ws = alpha_ws; a.hub_ws = hub_ws;
+    a.out = gamma; a.gamma0_sum = gamma0_sum; a.lognorm_mean = lognorm_mean;
+    a.arc_counts = cat_counts; a.map = map; a.s = as_stream(stream);
+    if (wave_fb_ok(b) && hub_ws) BEER_DISPATCH(dtype, wave_fb_launch, b, a, Packed{});
+    BEER_DISPATCH(dtype, group_fb_launch, b, a, std::true_type{});
 }
 
 int beer_hmm_path_counts_cat(const beer_batch* b, const int64_t* path, const beer_cat_map* map,
@@ -2442,18 +2495,7 @@ int beer_hmm_path_counts_cat(const beer_batch* b, const int64_t* path, const bee
 
 int beer_hmm_last_frame_sum(int dtype, const beer_batch* b, const void* gamma, double* out,
                             void* stream) {
-    BEER_REQUIRE(b && b->nutt >= 0 && b->n_graphs == 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    if (b->nutt == 0) return BEER_OK;
-    BEER_REQUIRE(gamma && out);
-    if (dtype == BEER_F32)
-        hipLaunchKernelGGL(last_frame_kernel<float>, dim3(b->nutt), dim3(256), 0, as_stream(stream),
-                           *b, (const float*)gamma, out);
-    else
-        hipLaunchKernelGGL(last_frame_kernel<double>, dim3(b->nutt), dim3(256), 0,
-                           as_stream(stream), *b, (const double*)gamma, out);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    BEER_DISPATCH(dtype, last_frame_launch, b, gamma, out, stream);
 }
 
 int beer_hmm_gather(int dtype, const beer_batch* batch_h, int S_total, const void* pc_all,
@@ -2468,67 +2510,25 @@ int beer_hmm_scatter(int dtype, const beer_batch* batch_h, int S_total, const vo
                   exp_llh, utt_llh, stream);
 }
 
+[[maybe_unused]] static const void* const kGroupKernels[] = {
+    (const void*)fb_lowdeg_kernel<float, false>, (const void*)fb_lowdeg_kernel<double, false>,
+    (const void*)fb_kernel<float, false>, (const void*)fb_kernel<double, false>,
+    (const void*)fb_kernel<float, true>, (const void*)fb_kernel<double, true>};
+
 int beer_hmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llhs,
                               double* alpha_ws, double* hub_ws, void* gamma, double* xi_sum,
                               double* gamma0_sum, double* hub_flow, void* lognorm_mean,
                               void* stream) {
     BEER_REQUIRE(fb_batch_ok(dtype, b));
     if (b->nutt == 0) return BEER_OK;
-    hipStream_t s = as_stream(stream);
-    const bool want_xi = xi_sum != nullptr;
-    const bool flow_ok = fb_flow_ok(want_xi, hub_flow != nullptr);
-    if (wave_fb_ok(b) && hub_ws && flow_ok) {
-        // one wave per utterance, no barriers
-        if (dtype == BEER_F32)
-            return wave_fb_launch<float, false>(b, (const float*)pc_llhs, b->max_states, 1.f,
-                                                alpha_ws, hub_ws, (float*)gamma, 1.f, 0, xi_sum,
-                                                gamma0_sum, hub_flow, nullptr,
-                                                (float*)lognorm_mean, nullptr, s);
-        return wave_fb_launch<double, false>(b, (const double*)pc_llhs, b->max_states, 1.0,
-                                             alpha_ws, hub_ws, (double*)gamma, 1.0, 0, xi_sum,
-                                             gamma0_sum, hub_flow, nullptr,
-                                             (double*)lognorm_mean, nullptr, s);
-    }
-    if (lowdeg_fb_ok(b) && flow_ok) {
-        // factorised low-degree recursion: one thread per state
-        const size_t lds = ((size_t)3 * b->max_states + 4 * kMaxHubs + 8) * sizeof(double);
-        const int threads = lowdeg_fb_threads(b);
-        if (dtype == BEER_F32)
-            hipLaunchKernelGGL(fb_lowdeg_kernel<float>, dim3(b->nutt), dim3(threads), lds, s,
-                               *b, (const float*)pc_llhs, alpha_ws, (float*)gamma, xi_sum,
-                               gamma0_sum, hub_flow, (float*)lognorm_mean, beer_cat_map{});
-        else
-            hipLaunchKernelGGL(fb_lowdeg_kernel<double>, dim3(b->nutt), dim3(threads), lds, s,
-                               *b, (const double*)pc_llhs, alpha_ws, (double*)gamma, xi_sum,
-                               gamma0_sum, hub_flow, (double*)lognorm_mean, beer_cat_map{});
-        BEER_LAUNCH_CHECK();
-        return BEER_OK;
-    }
-    const size_t lds = fb_lds_bytes(b, dtype, want_xi, false);
-    const bool big = fb_general_big(b, dtype, want_xi);
-#define BEER_FB(T_, BIG_, LDS_, GRID_)                                                           \
-    do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fb_kernel<T_, BIG_>),            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);      \
-        hipLaunchKernelGGL((fb_kernel<T_, BIG_>), dim3(GRID_), dim3(kFbThreads), LDS_, s, *b,    \
-                           (const T_*)pc_llhs, alpha_ws, (T_*)gamma, xi_sum, gamma0_sum,         \
-                           (T_*)lognorm_mean, hub_ws);                                           \
-    } while (0)
-    if (!big) {
-        if (dtype == BEER_F32) BEER_FB(float, false, lds, b->nutt);
-        else BEER_FB(double, false, lds, b->nutt);
-    } else {
-        // arc lists beyond a CU's LDS: per-arc scratch in `hub_ws`
-        // (beer_hmm_fb_scratch_doubles), the per-state arrays must still fit
-        const size_t lds_big = fb_lds_bytes(b, dtype, want_xi, true);
-        BEER_REQUIRE(fb_general_big_ok(b, dtype, want_xi) && hub_ws);
-        const int grid = b->nutt < kFbBigBlocks ? b->nutt : kFbBigBlocks;
-        if (dtype == BEER_F32) BEER_FB(float, true, lds_big, grid);
-        else BEER_FB(double, true, lds_big, grid);
-    }
-#undef BEER_FB
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    FbArgs a;
+    a.pc = pc_llhs; a.S_total = b->max_states; a.alpha_ws = alpha_ws; a.hub_ws = hub_ws;
+    a.out = gamma; a.xi_sum = xi_sum; a.gamma0_sum = gamma0_sum; a.hub_flow = hub_flow;
+    a.lognorm_mean = lognorm_mean; a.s = as_stream(stream);
+    // one wave per utterance, no barriers; else a workgroup
+    if (wave_fb_ok(b) && hub_ws && fb_flow_ok(xi_sum != nullptr, hub_flow != nullptr))
+        BEER_DISPATCH(dtype, wave_fb_launch, b, a, Packed{});
+    BEER_DISPATCH(dtype, group_fb_launch, b, a, std::false_type{});
 }
 
 int beer_hmm_fb_log_count(const beer_batch* b, const double* hub_ws, int64_t* count,
@@ -2563,69 +2563,21 @@ size_t beer_hmm_fb_scratch_doubles(int dtype, const beer_batch* b, int want_xi) 
 
 int beer_hmm_trans_posteriors(int dtype, int64_t T, int S, const double* alpha, const void* llhs,
                               const void* gamma, const void* trans, void* xi, void* stream) {
-    BEER_REQUIRE(T >= 0 && S >= 1 && (dtype == BEER_F32 || dtype == BEER_F64));
-    if (T <= 1) return BEER_OK;
-    BEER_REQUIRE(alpha && llhs && gamma && trans && xi);
-    if (dtype == BEER_F32)
-        hipLaunchKernelGGL(xi_dense_kernel<float>, dim3((unsigned)(T - 1)), dim3(256), 0,
-                           as_stream(stream), T, S, alpha, (const float*)llhs, (const float*)gamma,
-                           (const float*)trans, (float*)xi);
-    else
-        hipLaunchKernelGGL(xi_dense_kernel<double>, dim3((unsigned)(T - 1)), dim3(256), 0,
-                           as_stream(stream), T, S, alpha, (const double*)llhs,
-                           (const double*)gamma, (const double*)trans, (double*)xi);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    BEER_DISPATCH(dtype, xi_dense_launch, T, S, alpha, llhs, gamma, trans, xi, stream);
 }
 
 int beer_hmm_viterbi(int dtype, const beer_batch* b, const void* pc_llhs, int32_t* bt_ws,
                      int64_t* path, int map_pdf, void* stream) {
     BEER_REQUIRE(b && b->nutt >= 0 && b->max_states >= 1);
     if (b->nutt == 0) return BEER_OK;
-    hipStream_t s = as_stream(stream);
-    // LDS: two trellis columns, a chunk of back-pointers and, when they fit, the arcs
-    const size_t elem = dtype == BEER_F32 ? sizeof(float) : sizeof(double);
-    const size_t base = (size_t)2 * b->max_states * elem +
-                        (size_t)kViterbiChunk * b->max_states * sizeof(int32_t);
-    const size_t arcs = ((size_t)b->max_states + 2 + b->max_arcs) * sizeof(int32_t) +
-                        (size_t)b->max_arcs * elem;
-    BEER_REQUIRE(base <= 160 * 1024);
-    const int arcs_in_lds = base + arcs <= 64 * 1024;
-    const size_t lds = base + (arcs_in_lds ? arcs : 0);
-    // four lanes per state when 512 threads suffice for that, else 256 threads
-    const int vthreads = 4 * b->max_states <= kViterbiThreads ? kViterbiThreads : kHmmThreads;
-    if (dtype == BEER_F32) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(viterbi_kernel<float>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
-        hipLaunchKernelGGL(viterbi_kernel<float>, dim3(b->nutt), dim3(vthreads), lds, s, *b,
-                           (const float*)pc_llhs, bt_ws, path, map_pdf, arcs_in_lds);
-    } else if (dtype == BEER_F64) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(viterbi_kernel<double>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
-        hipLaunchKernelGGL(viterbi_kernel<double>, dim3(b->nutt), dim3(vthreads), lds, s, *b,
-                           (const double*)pc_llhs, bt_ws, path, map_pdf, arcs_in_lds);
-    } else {
-        return BEER_EINVAL;
-    }
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    BEER_DISPATCH(dtype, viterbi_launch, b, pc_llhs, bt_ws, path, map_pdf, stream);
 }
 
 int beer_hmm_path_posteriors(int dtype, const beer_batch* b, const int64_t* path, void* gamma,
                              double* xi_sum, double* gamma0_sum, void* stream) {
     BEER_REQUIRE(b && b->nutt >= 0);
     if (b->nutt == 0) return BEER_OK;
-    hipStream_t s = as_stream(stream);
-    if (dtype == BEER_F32)
-        hipLaunchKernelGGL(path_post_kernel<float>, dim3(b->nutt, 2), dim3(256), 0, s, *b, path,
-                           (float*)gamma, xi_sum, gamma0_sum);
-    else if (dtype == BEER_F64)
-        hipLaunchKernelGGL(path_post_kernel<double>, dim3(b->nutt, 2), dim3(256), 0, s, *b, path,
-                           (double*)gamma, xi_sum, gamma0_sum);
-    else
-        return BEER_EINVAL;
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    BEER_DISPATCH(dtype, path_post_launch, b, path, gamma, xi_sum, gamma0_sum, stream);
 }
 
 }  // extern "C"

@@ -150,6 +150,32 @@ def gather(batch, pc_all, scale=1.):
     return out
 
 
+def _route(dtype, desc, want_xi, have_hub_flow):
+    'beer_hmm_fb_route: the kernel family (and its launch shape) the C entry points pick.'
+    return _hip.lib().beer_hmm_fb_route(_hip.dtype_code(dtype), ctypes.byref(desc),
+                                        int(want_xi), int(have_hub_flow))
+
+
+def _workspace(batch, desc=None, want_xi=False, packed=True):
+    '''(packed gamma or None, alpha, hub_ws).  `hub_ws`: hub values per frame, or -- `desc` may take
+    the general kernel with arc lists too long for LDS -- that kernel's per-arc scratch.'''
+    dev, f64 = batch.device, torch.float64
+    n_ws = 0 if desc is None else _hip.lib().beer_hmm_fb_scratch_doubles(
+        _hip.dtype_code(batch.dtype), ctypes.byref(desc), int(want_xi))
+    return (torch.empty(batch.n_elems, dtype=batch.dtype, device=dev) if packed else None,
+            torch.empty(batch.n_elems, dtype=f64, device=dev),
+            torch.empty(max(_hip.MAX_HUBS * batch.n_frames, n_ws), dtype=f64, device=dev))
+
+
+def _note_alpha(batch, alpha, route, hub_ws):
+    '''What a call on `route` left in `alpha` (for `trans_posteriors_dense`; None: the fused launch
+    keeps nothing): the one-wave kernels SCALED PROBABILITIES, the others logarithms.'''
+    batch.last_alpha = alpha
+    batch.last_alpha_is_log = _hip.fb_family(route) != _hip.FB_WAVE
+    if not batch.last_alpha_is_log:
+        counting_log_space.note(batch, hub_ws)
+
+
 def forward_backward(batch, pc_llhs, want_xi=False, want_lognorm=False, dense_xi=False):
     '''(gamma packed, xi_sum [S,S] fp64 or None, gamma0_sum [S] fp64 or None,
     lognorm_mean [nutt] or None, hub_flow [S] fp64 or None).  xi / gamma0 need
@@ -158,10 +184,12 @@ def forward_backward(batch, pc_llhs, want_xi=False, want_lognorm=False, dense_xi
     `hub_flow`; `dense_xi=True` forces the general kernel and a complete
     [S, S] matrix.'''
     dt, dev = batch.dtype, batch.device
-    st = batch.struct
-    lowdeg_flag = st.all_lowdeg
-    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
-    alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
+    desc = batch.struct
+    if dense_xi:
+        # the general kernel: a complete [S, S] matrix and log-space forward values in `alpha`.
+        # On a copy: the batch's descriptor is shared with later calls and other host threads.
+        desc = _hip.Batch.from_buffer_copy(desc)
+        desc.all_lowdeg = 0
     xi = g0 = ln = flow = None
     if want_xi:
         if not batch.shared_graph:
@@ -172,39 +200,20 @@ def forward_backward(batch, pc_llhs, want_xi=False, want_lognorm=False, dense_xi
         flow = torch.zeros(S, dtype=torch.float64, device=dev)
     if want_lognorm:
         ln = torch.empty(batch.nutt, dtype=dt, device=dev)
-    try:
-        if dense_xi:
-            # the general kernel: a complete [S, S] matrix, and log-space forward values in
-            # `alpha` (what `trans_posteriors_dense` reads; the one-wave kernel keeps scaled
-            # probabilities there).  The descriptor is shared with later calls on the same
-            # batch: the flag is put back below.
-            st.all_lowdeg = 0
-        # hub values per frame, or -- graphs too dense for the arc lists to sit in LDS --
-        # the general kernel's per-arc scratch
-        n_ws = max(_hip.MAX_HUBS * batch.n_frames,
-                   _hip.lib().beer_hmm_fb_scratch_doubles(_hip.dtype_code(dt), batch.ref(),
-                                                          int(want_xi)))
-        hub_ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
-        # which kernel family the C entry point picks (wave_fb_ok of csrc/hmm.hip): the
-        # one-wave kernel leaves SCALED PROBABILITIES in `alpha`, the others logarithms
-        alpha_is_log = not fused_ok(batch)
-        _hip.call('beer_hmm_forward_backward', _hip.dtype_code(dt), batch.ref(),
-                  _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma),
-                  _hip.ptr(xi), _hip.ptr(g0), _hip.ptr(flow), _hip.ptr(ln))
-    except _hip.HipError as err:
-        if 'invalid argument' in str(err) and not st.all_lowdeg:
-            raise _hip.HipError(
-                f'forward-backward: a graph of the batch has {st.max_states} states; the general '
-                "kernel keeps five per-state arrays in the CU's 160 KB of LDS (about 4000 states). "
-                'Graphs with at most 8 arcs per state besides a declared hub '
-                '(CompiledGraph.set_hub) run at any size') from err
-        raise
-    finally:
-        st.all_lowdeg = lowdeg_flag
-    batch.last_alpha = alpha              # (for `trans_posteriors_dense`)
-    batch.last_alpha_is_log = alpha_is_log
-    if not alpha_is_log:
-        counting_log_space.note(batch, hub_ws)
+    route = _route(dt, desc, want_xi, 1)
+    if route == _hip.EINVAL and not desc.all_lowdeg:
+        err = _hip.HipError(
+            f'forward-backward: a graph of the batch has {desc.max_states} states; the general '
+            "kernel keeps five per-state arrays in the CU's 160 KB of LDS (about 4000 states). "
+            'Graphs with at most 8 arcs per state besides a declared hub '
+            '(CompiledGraph.set_hub) run at any size')
+        err.rc = route
+        raise err
+    gamma, alpha, hub_ws = _workspace(batch, desc, want_xi)
+    _hip.call('beer_hmm_forward_backward', _hip.dtype_code(dt), ctypes.byref(desc),
+              _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma),
+              _hip.ptr(xi), _hip.ptr(g0), _hip.ptr(flow), _hip.ptr(ln))
+    _note_alpha(batch, alpha, route, hub_ws)
     return gamma, xi, g0, ln, flow
 
 
@@ -255,15 +264,13 @@ class counting_log_space:
             self.launches += 1
 
 
-FUSED_MAX_STATES = 256      # kWvMaxStates of csrc/hmm.hip
-
-
 def fused_ok(batch):
     '''True when `posteriors_fused` takes the batch: low-degree graphs of <= 256
     states with at most one hub of <= 64 members a side (wave_fb_ok of csrc/hmm.hip).'''
-    st = batch.struct
-    return bool(st.all_lowdeg) and st.max_states <= FUSED_MAX_STATES and \
-        1 <= st.max_degree <= _hip.SEG and st.max_hubs <= 1 and st.max_hub_members <= 64
+    # (= wave_fb_ok: nothing else decides without xi, and no HmmBatch is refused: 1..32767 states)
+    if not hasattr(batch, '_fused'):                 # (asked once per descriptor)
+        batch._fused = _hip.fb_family(_route(batch.dtype, batch.struct, 0, 0)) == _hip.FB_WAVE
+    return batch._fused
 
 
 FUSED_ROW_MAX = 512          # kWvRowMax of hmm.hip: pdf ids of a set that fit a wave's LDS row
@@ -295,8 +302,7 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
     out_mode = 2 if (repeats or not covers) and S_total <= FUSED_ROW_MAX else (1 if repeats else 0)
     make = torch.empty if (out_mode == 2 or (not repeats and covers)) else torch.zeros
     sr = make(batch.n_frames, S_total, dtype=dt, device=dev)
-    alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
-    hub_ws = torch.empty(_hip.MAX_HUBS * batch.n_frames, dtype=torch.float64, device=dev)
+    _, alpha, hub_ws = _workspace(batch, packed=False)
     g0 = flow = None
     if want_counts:
         if not batch.shared_graph:
@@ -314,23 +320,22 @@ def posteriors_fused(batch, pc_all, scale=1., want_counts=False, utt_llh=None, f
     args = (_hip.dtype_code(dt), batch.ref(), S_total, _hip.ptr(pc_all), float(scale),
             _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(sr), out_mode, _hip.ptr(g0),
             _hip.ptr(flow), _hip.ptr(utt_llh), _hip.ptr(frame_llh))
+    counts = ()
     if want_transitions and batch.bound_set is not None:
         # alignment graphs bound to the model: the counts by category, any graph per utterance
         cat_counts = _cat_buffer(batch)
         _hip.call('beer_hmm_posteriors_fused_cat', *args[:9], _hip.ptr(g0), *args[11:],
                   ctypes.byref(batch.cat_map), _hip.ptr(cat_counts))
-        counting_log_space.note(batch, hub_ws)
-        return sr, g0, flow, ('cat', cat_counts, None)
-    if want_transitions:
+        counts = (('cat', cat_counts, None),)
+    elif want_transitions:
         arc_counts, src_flow = _count_buffers(batch)
         _hip.call('beer_hmm_posteriors_fused_counts', *args, _hip.ptr(arc_counts),
                   _hip.ptr(src_flow))
+        counts = (('arcs', arc_counts, src_flow),)
     else:
         _hip.call('beer_hmm_posteriors_fused', *args)
-    counting_log_space.note(batch, hub_ws)
-    if want_transitions:
-        return sr, g0, flow, ('arcs', arc_counts, src_flow)
-    return sr, g0, flow
+    _note_alpha(batch, None, _hip.FB_WAVE, hub_ws)
+    return (sr, g0, flow) + counts
 
 
 def lowdeg_arcs(batch):
@@ -349,7 +354,7 @@ def _cat_buffer(batch):
 def _count_buffers(batch):
     if not batch.shared_graph or not fused_ok(batch):
         raise ValueError('the one-wave transition counts: one graph for the whole batch, of at '
-                         f'most {FUSED_MAX_STATES} states with at most {_hip.SEG} arcs a state '
+                         f'most 256 states with at most {_hip.SEG} arcs a state '
                          'besides one declared hub of at most 64 phones')
     dev = batch.device
     S = batch.n_states[0]
@@ -383,17 +388,11 @@ def forward_backward_counts(batch, pc_llhs):
         # alignment graphs bound to the model (`beer_hmm_forward_backward_cat`): any graph per
         # utterance, the one-wave kernels or -- beyond 256 states -- the workgroup kernels
         cat_counts = _cat_buffer(batch)
-        gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
-        alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
-        n_ws = max(_hip.MAX_HUBS * batch.n_frames,
-                   _hip.lib().beer_hmm_fb_scratch_doubles(_hip.dtype_code(dt), batch.ref(), 1))
-        hub_ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+        gamma, alpha, hub_ws = _workspace(batch, batch.struct, want_xi=True)
         _hip.call('beer_hmm_forward_backward_cat', _hip.dtype_code(dt), batch.ref(),
                   _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma), None,
                   ctypes.byref(batch.cat_map), _hip.ptr(cat_counts), None)
-        batch.last_alpha = alpha
-        batch.last_alpha_is_log = not fused_ok(batch)
-        counting_log_space.note(batch, hub_ws)
+        _note_alpha(batch, alpha, _route(dt, batch.struct, 1, 1), hub_ws)
         return gamma, None, None, None, ('cat', cat_counts, None)
     if not batch.shared_graph:
         raise ValueError('transition counts need one graph for the whole batch')
@@ -402,17 +401,13 @@ def forward_backward_counts(batch, pc_llhs):
         return gamma, g0, None, xi, ('dense', xi, last_frame_sum(batch, gamma))
     arc_counts, src_flow = _count_buffers(batch)
     S = batch.n_states[0]
-    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
-    alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
-    hub_ws = torch.empty(_hip.MAX_HUBS * batch.n_frames, dtype=torch.float64, device=dev)
+    gamma, alpha, hub_ws = _workspace(batch)
     g0 = torch.zeros(S, dtype=torch.float64, device=dev)
     flow = torch.zeros(S, dtype=torch.float64, device=dev)
     _hip.call('beer_hmm_forward_backward_counts', _hip.dtype_code(dt), batch.ref(),
               _hip.ptr(pc_llhs), _hip.ptr(alpha), _hip.ptr(hub_ws), _hip.ptr(gamma),
               _hip.ptr(g0), _hip.ptr(flow), _hip.ptr(arc_counts), _hip.ptr(src_flow), None)
-    batch.last_alpha = alpha
-    batch.last_alpha_is_log = False
-    counting_log_space.note(batch, hub_ws)
+    _note_alpha(batch, alpha, _hip.FB_WAVE, hub_ws)
     return gamma, g0, flow, None, ('arcs', arc_counts, src_flow)
 
 

@@ -190,12 +190,10 @@ def _cached_batch(graph, run_lengths, dtype):
     dg = graph.device_graph(dtype)
     hit = cache.get(key)
     if hit is not None and hit.dgraphs[0] is dg:
-        hit.struct.all_lowdeg = hit.lowdeg_default       # forward_backward may have cleared it
         return hit
     if len(cache) >= 8:
         cache.clear()
     batch = hk.HmmBatch([graph], [0] * len(run_lengths), run_lengths, dtype)
-    batch.lowdeg_default = batch.struct.all_lowdeg
     cache[key] = batch
     return batch
 

@@ -265,3 +265,132 @@ def test_viterbi_table_covers_the_thread_schemes():
             if kk == k and T >= 31:
                 a, b = ft.tie_share(g, ft.viterbi_inputs(S, [T], 2100 + u)[0])
                 assert 20 * a >= b
+
+
+# --- argument validation of every beer_hmm_* entry point of csrc/hmm.hip --------------------------
+# Rows that return before any HIP call, so they run without a GPU; the codes are literals.
+
+_SCRATCH = ctypes.create_string_buffer(64)
+P = ctypes.cast(_SCRATCH, ctypes.c_void_p)          # "some buffer": never reached by these rows
+
+
+def _cmap(arc_cat=P, last_cat=P, arc_off=P, state_off=P):
+    return _hip.CatMap(arc_cat, last_cat, arc_off, state_off)
+
+
+# name -> the argument list (without the stream) from: dtype, batch, every buffer, S_total,
+# atomic_out, category map, element / frame count, hub_ws alone
+ENTRY_ARGS = {
+    'gather': lambda d, b, p, S, a, m, n, h: (d, b, S, p, 1., p),
+    'scatter': lambda d, b, p, S, a, m, n, h: (d, b, S, p, p, 1., p, p, p),
+    'forward_backward': lambda d, b, p, S, a, m, n, h: (d, b, p, p, h, p, p, p, p, p),
+    'fb_log_count': lambda d, b, p, S, a, m, n, h: (b, h, p),
+    'posteriors_fused': lambda d, b, p, S, a, m, n, h: (d, b, S, p, 1., p, h, p, a, p, p, p, p),
+    'posteriors_fused_counts':
+        lambda d, b, p, S, a, m, n, h: (d, b, S, p, 1., p, h, p, a, p, p, p, p, p, p),
+    'forward_backward_counts': lambda d, b, p, S, a, m, n, h: (d, b, p, p, h, p, p, p, p, p, p),
+    'last_frame_sum': lambda d, b, p, S, a, m, n, h: (d, b, p, p),
+    'refresh_weights': lambda d, b, p, S, a, m, n, h: (d, n, p, p, p, p),
+    'posteriors_fused_cat':
+        lambda d, b, p, S, a, m, n, h: (d, b, S, p, 1., p, h, p, a, p, p, p, m, p),
+    'forward_backward_cat': lambda d, b, p, S, a, m, n, h: (d, b, p, p, h, p, p, m, p, p),
+    'path_counts_cat': lambda d, b, p, S, a, m, n, h: (b, p, m, p),
+    'trans_posteriors': lambda d, b, p, S, a, m, n, h: (d, n, S, p, p, p, p, p),
+    'viterbi': lambda d, b, p, S, a, m, n, h: (d, b, p, p, p, 0),
+    'path_posteriors': lambda d, b, p, S, a, m, n, h: (d, b, p, p, p, p),
+}
+WITH_BATCH = [n for n in ENTRY_ARGS if n not in ('refresh_weights', 'trans_posteriors')]
+FUSED = ['posteriors_fused', 'posteriors_fused_counts', 'posteriors_fused_cat']
+WAVE_ONLY = FUSED + ['forward_backward_counts', 'fb_log_count']
+CAT = ['posteriors_fused_cat', 'forward_backward_cat']
+CHECKS_STATES = FUSED + ['forward_backward', 'forward_backward_counts', 'forward_backward_cat',
+                         'viterbi']
+DENSE = dict(all_lowdeg=0, max_degree=0)
+
+
+def _two_graphs():
+    b = desc(64)
+    b.n_graphs = 2
+    return b
+
+
+def validation_rows():
+    'Rows (what, entry point, keyword arguments of `validate`, expected code).'
+    rows = []
+
+    def add(what, names, want, **kw):
+        rows.extend((what, n, kw, want) for n in names)
+
+    add('null batch', WITH_BATCH, -100000, b=None)
+    add('negative nutt', WITH_BATCH, -100000, b=desc(64, nutt=-1))
+    add('empty batch, null buffers', [n for n in WITH_BATCH if n != 'fb_log_count'], 0,
+        b=desc(64, nutt=0), p=None, h=None, m=None)
+    add('empty batch, null count', ['fb_log_count'], -100000, b=desc(64, nutt=0), p=None, h=None)
+    add('empty batch, null hub_ws', ['fb_log_count'], 0, b=desc(64, nutt=0), h=None)
+    add('no elements / one frame', ['refresh_weights', 'trans_posteriors'], 0, n=0, p=None)
+    add('one frame', ['trans_posteriors'], 0, n=1, p=None)
+    add('negative count', ['refresh_weights', 'trans_posteriors'], -100000, n=-1)
+    add('no state', ['trans_posteriors'], -100000, S=0)
+    add('null buffers', ['refresh_weights', 'trans_posteriors'], -100000, n=2, p=None)
+    add('null buffers', WAVE_ONLY + ['last_frame_sum', 'forward_backward_cat', 'path_counts_cat'],
+        -100000, p=None, h=None)
+    # dtype 99: the two entry points that look at the batch first take an empty one
+    by_dtype = [n for n in ENTRY_ARGS if n not in ('fb_log_count', 'path_counts_cat')]
+    add('dtype 99, empty batch', [n for n in by_dtype if n not in ('viterbi', 'path_posteriors')],
+        -100000, d=99, b=desc(64, nutt=0), n=0)
+    add('dtype 99, empty batch', ['viterbi', 'path_posteriors'], 0, d=99, b=desc(64, nutt=0))
+    add('dtype 99', by_dtype, -100000, d=99)
+    add('no states', CHECKS_STATES, -100000, b=desc(0))
+    add('32768 states', ['forward_backward', 'forward_backward_cat', 'viterbi'], -100000,
+        b=desc(32768, **DENSE))
+    add('not a one-wave descriptor', WAVE_ONLY, -100000, b=desc(300))
+    add('no low-degree image', WAVE_ONLY, -100000, b=desc(64, all_lowdeg=0))
+    add('two graphs', ['posteriors_fused_counts', 'forward_backward_counts', 'last_frame_sum'],
+        -100000, b=_two_graphs())
+    add('a hub', CAT, -100000, b=desc(64, max_hubs=1, members=3))
+    add('null map', CAT + ['path_counts_cat'], -100000, m=None)
+    for member in ('arc_cat', 'last_cat', 'arc_off', 'state_off'):
+        add(f'null {member}', CAT + ['path_counts_cat'], -100000, m=_cmap(**{member: None}))
+    add('no pdf column', FUSED + ['gather', 'scatter'], -100000, S=0)
+    add('no pdf column, empty batch', FUSED + ['gather', 'scatter'], -100000, S=0,
+        b=desc(64, nutt=0))
+    add('rows of 513 columns through LDS', FUSED, -100000, S=513, a=2)
+    # the general kernel: per-state arrays beyond a CU's LDS; per-arc scratch without `hub_ws`
+    add('beyond LDS', ['forward_backward', 'forward_backward_cat'], -100000,
+        b=desc(32767, max_arcs=100000, max_segs=40000, **DENSE))
+    add('arc lists beyond LDS, null hub_ws', ['forward_backward', 'forward_backward_cat'],
+        -100000, b=desc(100, max_arcs=10000, max_segs=1300, **DENSE), h=None)
+    return rows
+
+
+def validate(name, d=F32, b=None, p=P, S=5, a=0, m=_cmap(), n=2, h=P):
+    args = ENTRY_ARGS[name](d, ctypes.byref(b) if b is not None else None, p, S, a,
+                            ctypes.byref(m) if m is not None else None, n, h)
+    return getattr(_hip.lib(), 'beer_hmm_' + name)(*args, None)
+
+
+VALIDATION = validation_rows()
+
+
+@pytest.mark.parametrize('what,name,kw,want', VALIDATION,
+                         ids=[f'{r[1]}-{r[0].replace(" ", "_")}' for r in VALIDATION])
+def test_entry_points_validate_their_arguments(what, name, kw, want):
+    kw = dict(kw)
+    if 'b' not in kw and name in WITH_BATCH:
+        kw['b'] = desc(64)
+    assert validate(name, **kw) == want
+
+
+def test_validation_table_names_every_entry_point_of_the_file():
+    text = open(os.path.join(ROOT, 'beer_amd', 'csrc', 'hmm.hip')).read()
+    defined = set(re.findall(r'^(?:int|size_t) beer_hmm_(\w+)\(', text, re.M))
+    host_only = {'fb_route', 'fb_scratch_doubles'}          # (no stream; see below and above)
+    assert defined == set(ENTRY_ARGS) | host_only
+    assert {r[1] for r in VALIDATION} == set(ENTRY_ARGS)
+    scratch = _hip.lib().beer_hmm_fb_scratch_doubles
+    big = desc(100, max_arcs=10000, max_segs=1300, **DENSE)
+    assert scratch(F64, None, 1) == 0 and scratch(99, ctypes.byref(big), 1) == 0
+    assert scratch(F64, ctypes.byref(desc(100, nutt=0, max_arcs=10000, **DENSE)), 1) == 0
+    assert scratch(F64, ctypes.byref(big), 1) == 3 * (2 * 10000 + 1300)
+    assert route(None) == -100000 and route(desc(64), 99) == -100000
+    assert route(desc(64, nutt=0), 99) == -100000 and route(desc(64, nutt=0)) == 0x1014

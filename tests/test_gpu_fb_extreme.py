@@ -408,9 +408,47 @@ def test_per_frame_transition_posteriors_through_the_model_protocol(cov):
     gamma = hk.forward_backward(batch, pc.reshape(-1))[0]
     with pytest.raises(ValueError):
         hk.trans_posteriors_dense(batch, pc.reshape(-1), gamma, hmm.graph.trans_log_probs)
-    assert batch.struct.all_lowdeg == 1
+    assert batch.struct.all_lowdeg == 1 and hk.fused_ok(batch)
+    before = bytes(batch.struct)
     hk.forward_backward(batch, pc.reshape(-1), dense_xi=True)
-    assert batch.struct.all_lowdeg == 1                  # (the shared descriptor is put back)
+    assert bytes(batch.struct) == before                 # (the shared descriptor is never written)
+    assert batch.last_alpha_is_log
+    # ... nor when the call raises: a graph over the general kernel's LDS limit (a hand-set
+    # `max_states`, nothing that large is allocated) is refused from the route, before any launch
+    batch.struct.max_states = 32767
+    batch.struct.max_arcs, batch.struct.max_segs = 100000, 40000
+    before = bytes(batch.struct)
+    torch.cuda.synchronize()
+    allocated, last = torch.cuda.memory_allocated(), batch.last_alpha
+    with pytest.raises(_hip.HipError, match='five per-state arrays') as err:
+        hk.forward_backward(batch, pc.reshape(-1), dense_xi=True)
+    assert type(err.value) is _hip.HipError and err.value.rc == _hip.EINVAL
+    assert bytes(batch.struct) == before
+    # (no workspace was allocated for a launch and the tail of the call did not run)
+    assert torch.cuda.memory_allocated() == allocated and batch.last_alpha is last
+
+
+def test_cached_route_and_dense_descriptor_do_not_leak_into_each_other():
+    '''5 states, utterances of 3 and 4 frames: after `forward_backward(dense_xi=True)` -- the
+    general kernel on a copy of the descriptor -- a plain call on the same batch is back on the
+    one-wave kernel, with a fresh batch's results (the suite's float64 bound, 1e-9).'''
+    rng = np.random.RandomState(11)
+    init, final, trans = _strict_chain(5, rng, np.float64)
+    graph = beer.graph.CompiledGraph(tt(init), tt(final), tt(trans), list(range(5)))
+    lens = [3, 4]
+    flat = tt(rng.randn(sum(lens) * 5) * 2)
+
+    def fresh():
+        return hk.HmmBatch([graph], [0] * len(lens), lens, torch.float64)
+    want = hk.forward_backward(fresh(), flat, want_xi=True, want_lognorm=True)
+    batch = fresh()
+    assert hk.fused_ok(batch)                            # (the route is cached from here on)
+    hk.forward_backward(batch, flat, want_xi=True, dense_xi=True)
+    assert batch.last_alpha_is_log is True and hk.fused_ok(batch)
+    got = hk.forward_backward(batch, flat, want_xi=True, want_lognorm=True)
+    assert batch.last_alpha_is_log is False
+    for g, w, what in zip(got, want, ('gamma', 'xi_sum', 'gamma0', 'lognorm', 'hub_flow')):
+        assert_close(npy(g), npy(w), 1e-9, what)
 
 
 @pytest.mark.parametrize('dtype', [torch.float64, torch.float32])

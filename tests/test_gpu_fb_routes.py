@@ -2,7 +2,7 @@
 oracle, on graphs that sit on the dispatch boundaries (tests/fb_truth.py).
 
 One static table: each case names the family `beer_hmm_forward_backward` must launch for it
-(`beer_hmm_fb_route`), and each test first holds the C layer's choice, Python's restatement
+(`beer_hmm_fb_route`), and each test first holds the C layer's choice, what Python made
 of it (`hk.fused_ok`, `batch.last_alpha_is_log`) and the table against each other -- if the two
 layers disagree, `trans_posteriors_dense` reads scaled probabilities as logarithms.  Then every
 output of every entry point that runs on that route is compared with the float64 oracle:
