@@ -240,6 +240,7 @@ SIGNATURES = {
     'beer_hmm_fb_route': [c_i, c_p, c_i, c_i],                     # (host only: no stream)
     'beer_hmm_posteriors_bigram': [c_i, c_p, ctypes.c_int32, c_l, c_p, c_p, c_i, c_p, c_d, c_p,
                                    c_p, c_p, c_i, c_p, c_p],
+    'beer_hmm_bigram_route': [c_i, c_p, ctypes.c_int32, ctypes.c_int32],  # (host only: no stream)
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],

@@ -72,6 +72,36 @@ __host__ __device__ inline size_t bg_w_bytes(int P) {
 }
 __host__ __device__ inline int bg_wave_doubles(int ns) { return 2 * ns + 2 * kBgVec; }
 
+// The launch shape, shared by the launcher and beer_hmm_bigram_route (host only).
+// States per lane (5: the recipe's 100 phones of 3 states)
+inline int bg_spl(int S) { return S <= 64 ? 1 : (S <= 128 ? 2 : (S <= 256 ? 4 : (S <= 320 ? 5 : 8))); }
+// Residual arcs of a state unrolled per side
+inline int bg_deg(int max_degree) { return max_degree <= 2 ? 2 : (max_degree <= 4 ? 4 : 8); }
+// Waves whose columns fit the LDS behind W (0: not even one)
+template <typename WT>
+inline int bg_lds_waves(int P, int spl) {
+    const size_t wbytes = bg_w_bytes<WT>(P);
+    const size_t per_wave = (size_t)bg_wave_doubles(64 * spl) * sizeof(double);
+    if (wbytes + per_wave > (size_t)kMaxDynLds) return 0;
+    return (int)(((size_t)kMaxDynLds - wbytes) / per_wave);
+}
+// n_cu <= 0: the current device's CUs, 256 if it cannot be asked
+inline int bg_n_cu(int n_cu) {
+    if (n_cu > 0) return n_cu;
+    int dev = 0;
+    n_cu = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    return n_cu;
+}
+// Waves per workgroup: enough workgroups to spread the utterances over the CUs, as many waves
+// as the LDS allows (`room`, at most kBgMaxWaves) to share one copy of W
+inline int bg_waves(int room, int32_t nutt, int n_cu) {
+    const int want = (nutt + n_cu - 1) / (n_cu > 0 ? n_cu : 1);
+    const int waves = room < kBgMaxWaves ? room : kBgMaxWaves;
+    return want < waves ? (want > 0 ? want : 1) : waves;
+}
+
 template <typename T, typename WT, int SPL, int DEG>
 __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
     beer_bigram g, int32_t nutt, int64_t n_frames, const int64_t* __restrict__ frame_off,
@@ -351,22 +381,12 @@ int bigram_launch(const beer_bigram* g, int32_t nutt, int64_t n_frames, const in
                   const int32_t* order, int S_total, const void* pc_all, double scale,
                   double* alpha_ws, double* uv_ws, void* out, int atomic_out, double* utt_llh,
                   int32_t* flags, hipStream_t s) {
-    const int S = g->n_states;
-    // (5: the recipe's 100 phones of 3 states)
-    const int spl = S <= 64 ? 1 : (S <= 128 ? 2 : (S <= 256 ? 4 : (S <= 320 ? 5 : 8)));
-    const int deg = g->max_degree <= 2 ? 2 : (g->max_degree <= 4 ? 4 : 8);
+    const int spl = bg_spl(g->n_states), deg = bg_deg(g->max_degree);
+    const int room = bg_lds_waves<WT>(g->n_phones, spl);
+    if (room < 1) return BEER_EINVAL;
+    const int waves = bg_waves(room, nutt, bg_n_cu(0));
     const size_t wbytes = bg_w_bytes<WT>(g->n_phones);
     const size_t per_wave = (size_t)bg_wave_doubles(64 * spl) * sizeof(double);
-    if (wbytes + per_wave > (size_t)kMaxDynLds) return BEER_EINVAL;
-    int waves = (int)(((size_t)kMaxDynLds - wbytes) / per_wave);
-    // enough workgroups to spread the utterances over the CUs, as many waves as the LDS
-    // allows to share one copy of W
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int want = (nutt + n_cu - 1) / (n_cu > 0 ? n_cu : 1);
-    waves = waves < kBgMaxWaves ? waves : kBgMaxWaves;
-    waves = want < waves ? (want > 0 ? want : 1) : waves;
     const size_t lds = wbytes + (size_t)waves * per_wave;
     const dim3 grid((unsigned)((nutt + waves - 1) / waves)), block(64 * waves);
 #define BEER_BG(SPL_, DEG_)                                                                      \
@@ -395,6 +415,14 @@ int bigram_launch(const beer_bigram* g, int32_t nutt, int64_t n_frames, const in
     return BEER_OK;
 }
 
+// What both entry points ask of the descriptor
+inline bool bigram_graph_ok(int dtype, const beer_bigram* g, int32_t nutt) {
+    return g && nutt >= 0 && (dtype == BEER_F32 || dtype == BEER_F64) &&
+           g->n_states >= 1 && g->n_states <= kBgMaxStates &&
+           g->n_phones >= 1 && g->n_phones <= kBgMaxPhones &&
+           g->max_degree >= 0 && g->max_degree <= BEER_SEG;
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,11 +432,7 @@ int beer_hmm_posteriors_bigram(int dtype, const beer_bigram* g, int32_t nutt,
                                const void* pc_all, double scale, double* alpha_ws,
                                double* uv_ws, void* state_resps, int atomic_out,
                                double* utt_llh, int32_t* flags, void* stream) {
-    BEER_REQUIRE(g && nutt >= 0 && S_total >= 1);
-    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(g->n_states >= 1 && g->n_states <= kBgMaxStates);
-    BEER_REQUIRE(g->n_phones >= 1 && g->n_phones <= kBgMaxPhones);
-    BEER_REQUIRE(g->max_degree >= 0 && g->max_degree <= BEER_SEG);
+    BEER_REQUIRE(bigram_graph_ok(dtype, g, nutt) && S_total >= 1);
     BEER_REQUIRE(n_frames >= 0);
     if (nutt == 0) return BEER_OK;
     BEER_REQUIRE(frame_off && pc_all && alpha_ws && uv_ws && state_resps && utt_llh && flags);
@@ -420,6 +444,15 @@ int beer_hmm_posteriors_bigram(int dtype, const beer_bigram* g, int32_t nutt,
     return bigram_launch<double, double>(g, nutt, n_frames, frame_off, order, S_total, pc_all, scale,
                                          alpha_ws, uv_ws, state_resps, atomic_out, utt_llh,
                                          flags, s);
+}
+
+int beer_hmm_bigram_route(int dtype, const beer_bigram* g, int32_t nutt, int32_t n_cu) {
+    BEER_REQUIRE(bigram_graph_ok(dtype, g, nutt));
+    // (W is fp64 for either dtype)
+    const int spl = bg_spl(g->n_states);
+    const int room = bg_lds_waves<double>(g->n_phones, spl);
+    BEER_REQUIRE(room >= 1);
+    return spl | bg_deg(g->max_degree) << 8 | bg_waves(room, nutt, bg_n_cu(n_cu)) << 16;
 }
 
 }  // extern "C"

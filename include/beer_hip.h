@@ -797,6 +797,17 @@ int beer_hmm_posteriors_bigram(int dtype, const beer_bigram* graph, int32_t nutt
                                void* state_resps, int atomic_out, double* utt_llh,
                                int32_t* flags, void* stream);
 
+/* The launch shape beer_hmm_posteriors_bigram picks for this descriptor and batch size
+ * (host only: it reads n_states, n_phones and max_degree, and launches nothing), built from
+ * the launcher's own expressions:
+ *   SPL | DEG << 8 | waves << 16
+ * SPL in {1, 2, 4, 5, 8} states per lane for at most 64 / 128 / 256 / 320 / 512 states, DEG in
+ * {2, 4, 8} residual arcs per state unrolled, waves (= utterances) per workgroup:
+ * min(8, what the LDS holds behind W, ceil(nutt / n_cu)), at least 1.  `n_cu` <= 0: the
+ * current device's compute units as the launcher asks for them, 256 if that fails.
+ * BEER_EINVAL exactly where beer_hmm_posteriors_bigram refuses the descriptor. */
+int beer_hmm_bigram_route(int dtype, const beer_bigram* graph, int32_t nutt, int32_t n_cu);
+
 /* Per-frame transition posteriors in the reference's own layout, xi [T-1, S, S]
  * (beer/graph.py:308-323: normalised per frame, NaN -> 0), for ONE utterance,
  * from what beer_hmm_forward_backward left behind: `alpha` (its fp64 workspace
