@@ -153,6 +153,27 @@ def fb_family(route):
     return route & 0xF000
 
 
+# BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
+ESTEP_PLAIN, ESTEP_PACKED, ESTEP_IMAGE = 0, 1, 2
+ARG_PC_LLH, ARG_LOG_NORM, ARG_RESPS, ARG_LLH_SUM, ARG_LABELS, ARG_SCALED, ARG_LOG_WEIGHTS = \
+    1, 2, 4, 8, 16, 32, 64
+ESTEP_GENERIC, ESTEP_EXACT_F32, ESTEP_EXACT_F64, ESTEP_LLHX, ESTEP_LNFI = \
+    0x10000000, 0x20000000, 0x30000000, 0x40000000, 0x50000000
+ESTEP_GENERIC_PASS1, ESTEP_GENERIC_FUSED, ESTEP_GENERIC_NORMALISE, ESTEP_GENERIC_LABELS = 1, 2, 3, 4
+ESTEP_X_PACKED, ESTEP_X_LNO, ESTEP_X_IMG, ESTEP_X_BL = 0x100, 0x200, 0x400, 0x800
+ESTEP_X_NARROW, ESTEP_X_LANE_MAJOR, ESTEP_X_PADDED, ESTEP_X_XT = 0x1000, 0x2000, 0x4000, 0x8000
+
+
+def estep_family(route):
+    'BEER_ESTEP_FAMILY: the kernel family of a `beer_estep_route` value.'
+    return route & 0x70000000
+
+
+def estep_route(entry, dtype_code_, cov, D, S, G, args, workspace_bytes):
+    '`beer_estep_route`: the kernel family and launch form an E-step entry point picks (host only).'
+    return lib().beer_estep_route(entry, dtype_code_, cov, D, S, G, args, workspace_bytes)
+
+
 BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
 BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
 
@@ -218,6 +239,7 @@ SIGNATURES = {
     'beer_frame_image': [c_i, c_l, c_i, c_p, c_p, c_z, c_p],
     'beer_mixtureset_lognorm_image': [c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                       c_z, c_p],
+    'beer_estep_route': [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_uint, c_z],  # (host only: no stream)
     'beer_pack_resps': [c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_weights_from_acc': [c_i, c_i, c_i, c_p, c_p, c_p],
     'beer_tied_lognorm': [c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],

@@ -314,44 +314,71 @@ int llh_launch(int64_t nframes, int D, int K, const void* X, const void* expT, c
     return BEER_OK;
 }
 
+// What beer_mixtureset_estep does with a call, decided on the host from the shape and from
+// which arguments are given: refused, one of the matrix-core families (estep_mfma.h), or the
+// generic kernels above.  estep_launch acts on it, beer_estep_route reports it.
+struct EstepPlan {
+    int rc;                 // BEER_EINVAL: the entry point refuses the call
+    bool exact_mfma;        // the exact fp32 / fp64 MFMA kernel (estep_mfma.hip)
+    bool use_x;             // the bf16x3 kernels (estep_bf16.hip)
+    bool need_norm;         // generic: a normalisation follows pass 1 ...
+    bool fuse;              // ... inside pass 1
+    bool ln_is_w;           // G == 1, no responsibilities wanted: pass 1 writes log_norm
+};
+
+EstepPlan estep_plan(size_t elem, bool exact, int cov, int D, int S, int G, bool pc_llh,
+                     bool log_norm, bool comp_resps, bool llh_sum, bool labels, bool unscaled,
+                     bool ws, size_t ws_bytes) {
+    EstepPlan p = {};
+    p.rc = BEER_EINVAL;
+    if (!(D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2)) return p;
+    if (labels && S != 1) return p;
+    // The normaliser works in place on the responsibilities buffer; without one
+    // (pc_llh only, or G == 1 log_norm only) pass 1 alone is enough.
+    p.need_norm = (log_norm || comp_resps || llh_sum) && !labels;
+    // group-aligned shapes on every arithmetic; any G on the split path when only the
+    // log-normalisers are wanted (groups padded to a power of two)
+    // (the exact kernels take D <= 96 / 64, the bf16x3 kernels D <= 128)
+    const bool aligned = beer_mfma::supported_llh(D, S, G, elem) &&
+                         ws_bytes >= beer_mfma::estep_workspace_bytes(elem, cov, D, S, G);
+    const bool split_ws = elem == 4 && !exact &&
+                          ws_bytes >= beer_mfma::estepx_workspace_bytes(cov, D, S, G) &&
+                          beer_mfma::estepx_workspace_bytes(cov, D, S, G) > 0;
+    const bool aligned_x = split_ws && beer_mfma::supported_llh_x(D, S, G);
+    const bool padded = split_ws && !comp_resps && beer_mfma::supported_llh_split(D, S, G);
+    p.use_x = aligned_x || padded;
+    const bool mfma_ok = !labels && !pc_llh && unscaled && ws && (aligned || p.use_x) &&
+                         (log_norm || comp_resps || llh_sum);
+    p.use_x = mfma_ok && p.use_x;
+    p.exact_mfma = mfma_ok && !p.use_x;
+    // G == 1: log_norm == w; let pass 1 write into log_norm directly (the matrix-core
+    // path keeps the responsibilities in registers and needs no buffer for any G).
+    p.ln_is_w = p.need_norm && !comp_resps && !mfma_ok;
+    if (p.ln_is_w && !(G == 1 && log_norm)) return p;
+    if (labels && !(pc_llh || comp_resps)) return p;
+    // generic kernels; the normalisation is fused when a component chunk holds
+    // whole states
+    p.fuse = !mfma_ok && p.need_norm && !labels && (kCompChunk % G == 0) && (comp_resps || G == 1);
+    p.rc = BEER_OK;
+    return p;
+}
+
 template <typename T>
 int estep_launch(int cov, int64_t nframes, int D, int S, int G, const void* X, const void* expT,
                  const void* logw, const int64_t* labels, double stat_scale, void* pc_llh,
                  void* log_norm, void* comp_resps, double* llh_sum, void* ws, size_t ws_bytes,
                  void* stream, bool exact) {
-    BEER_REQUIRE(nframes >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(X && expT);
-    BEER_REQUIRE(!labels || S == 1);
+    BEER_REQUIRE(nframes >= 0 && X && expT);
+    const EstepPlan p = estep_plan(sizeof(T), exact, cov, D, S, G, pc_llh, log_norm, comp_resps,
+                                   llh_sum, labels, stat_scale == 1.0, ws, ws_bytes);
+    if (p.rc != BEER_OK) return p.rc;
     if (nframes == 0) return BEER_OK;
     hipStream_t s = as_stream(stream);
     const int K = S * G;
-    // The normaliser works in place on the responsibilities buffer; without one
-    // (pc_llh only, or G == 1 log_norm only) pass 1 alone is enough.
-    const bool need_norm = (log_norm || comp_resps || llh_sum) && !labels;
-    void* w_buf = comp_resps;
-    // group-aligned shapes on every arithmetic; any G on the split path when only the
-    // log-normalisers are wanted (groups padded to a power of two)
-    // (the exact kernels take D <= 96 / 64, the bf16x3 kernels D <= 128)
-    const bool aligned = beer_mfma::supported_llh(D, S, G, sizeof(T)) &&
-                         ws_bytes >= beer_mfma::estep_workspace_bytes(sizeof(T), cov, D, S, G);
-    const bool split_ws = sizeof(T) == 4 && !exact &&
-                          ws_bytes >= beer_mfma::estepx_workspace_bytes(cov, D, S, G) &&
-                          beer_mfma::estepx_workspace_bytes(cov, D, S, G) > 0;
-    const bool aligned_x = split_ws && beer_mfma::supported_llh_x(D, S, G);
-    const bool padded = split_ws && !comp_resps && beer_mfma::supported_llh_split(D, S, G);
-    const bool use_x = aligned_x || padded;
-    const bool mfma_ok = !labels && !pc_llh && stat_scale == 1.0 && ws && (aligned || use_x) &&
-                         (log_norm || comp_resps || llh_sum);
-    if (need_norm && !w_buf && !mfma_ok) {
-        // G == 1: log_norm == w; let pass 1 write into log_norm directly (the
-        // matrix-core path keeps the responsibilities in registers and needs no
-        // buffer for any G).
-        BEER_REQUIRE(G == 1 && log_norm);
-        w_buf = log_norm;
-    }
+    const bool need_norm = p.need_norm, use_x = p.use_x, mfma_ok = p.use_x || p.exact_mfma;
+    void* w_buf = p.ln_is_w ? log_norm : comp_resps;
     int rc;
     void* pc_arg = labels ? (pc_llh ? pc_llh : comp_resps) : pc_llh;
-    BEER_REQUIRE(!labels || pc_arg);
     void* w_arg = labels ? nullptr : (need_norm ? w_buf : nullptr);
 
     if (mfma_ok) {
@@ -371,9 +398,7 @@ int estep_launch(int cov, int64_t nframes, int D, int S, int G, const void* X, c
                                           (double*)comp_resps, (double*)log_norm, llh_sum, ws,
                                           ws_bytes, s);
     }
-    // generic kernels; the normalisation is fused when a component chunk holds
-    // whole states
-    const bool fuse = need_norm && !labels && (kCompChunk % G == 0) && (comp_resps || G == 1);
+    const bool fuse = p.fuse;
     const int fuse_G = fuse ? G : 0;
     void* ln_arg = fuse ? log_norm : nullptr;
     double* sum_arg = fuse ? llh_sum : nullptr;
@@ -493,6 +518,56 @@ int beer_mixtureset_estep(int dtype, int cov, int64_t T, int D, int S, int G, co
                   workspace_bytes, stream, exact);
 }
 
+int beer_estep_route(int entry, int dtype, int cov, int D, int S, int G, unsigned args,
+                     size_t workspace_bytes) {
+    const bool exact = (dtype & BEER_EXACT) != 0;
+    dtype &= ~BEER_EXACT;
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    BEER_REQUIRE(D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
+    const bool pc = args & BEER_ARG_PC_LLH, ln = args & BEER_ARG_LOG_NORM;
+    const bool resps = args & BEER_ARG_RESPS, sum = args & BEER_ARG_LLH_SUM;
+    const bool labels = args & BEER_ARG_LABELS, logw = args & BEER_ARG_LOG_WEIGHTS;
+    beer_mfma::LlhxForm x = {};
+    if (entry == BEER_ESTEP_PLAIN) {
+        const EstepPlan p = estep_plan(dtype == BEER_F64 ? 8 : 4, exact, cov, D, S, G, pc, ln, resps,
+                                       sum, labels, !(args & BEER_ARG_SCALED),
+                                       workspace_bytes > 0, workspace_bytes);
+        if (p.rc != BEER_OK) return p.rc;
+        if (p.exact_mfma) {
+            const beer_mfma::LlhForm f = beer_mfma::llh_form(S, G);
+            return (dtype == BEER_F64 ? BEER_ESTEP_EXACT_F64 : BEER_ESTEP_EXACT_F32) | f.NT |
+                   f.GQ << 5 | f.jw << 8 | (f.nchunks > 0xfff ? 0xfff : f.nchunks) << 16;
+        }
+        if (!p.use_x)
+            return BEER_ESTEP_GENERIC | (labels ? BEER_ESTEP_GENERIC_LABELS
+                                         : !p.need_norm ? BEER_ESTEP_GENERIC_PASS1
+                                         : p.fuse ? BEER_ESTEP_GENERIC_FUSED
+                                                  : BEER_ESTEP_GENERIC_NORMALISE);
+        x = beer_mfma::llhx_form(cov, D, S, G, resps, false, false, workspace_bytes);
+    } else if (entry == BEER_ESTEP_PACKED) {
+        // one mixture: beer_mixture_estep_packed (K = G); a set: beer_mixtureset_estep_packed
+        BEER_REQUIRE(dtype == BEER_F32 && !exact && !pc && !labels && !(args & BEER_ARG_SCALED));
+        BEER_REQUIRE(resps && workspace_bytes > 0);
+        if (S == 1) BEER_REQUIRE(logw && beer_mfma::supported_llh_x(D, 1, G));
+        else BEER_REQUIRE(beer_mixtureset_packed_supported(cov, D, S, G));
+        x = beer_mfma::llhx_form(cov, D, S, G, true, true, false, workspace_bytes);
+    } else if (entry == BEER_ESTEP_IMAGE) {
+        BEER_REQUIRE(dtype == BEER_F32 && !exact && !pc && !labels && !(args & BEER_ARG_SCALED));
+        BEER_REQUIRE(ln && !resps && workspace_bytes > 0);
+        x = beer_mfma::llhx_form(cov, D, S, G, false, false, true, workspace_bytes);
+    } else {
+        return BEER_EINVAL;
+    }
+    if (x.rc != BEER_OK) return x.rc;
+    const int nchunks = (x.nchunks > 0xfff ? 0xfff : x.nchunks) << 16;
+    if (x.lnfi) return BEER_ESTEP_LNFI | x.NT | x.nku << 5 | x.lnfi_g << 8 | nchunks;
+    return BEER_ESTEP_LLHX | x.NT | x.GQ << 5 | (x.packed ? BEER_ESTEP_X_PACKED : 0) |
+           (x.lno ? BEER_ESTEP_X_LNO : 0) | (x.img ? BEER_ESTEP_X_IMG : 0) |
+           (x.bl ? BEER_ESTEP_X_BL : 0) | (x.narrow ? BEER_ESTEP_X_NARROW : 0) |
+           (x.lane_major ? BEER_ESTEP_X_LANE_MAJOR : 0) | (x.Gp != G ? BEER_ESTEP_X_PADDED : 0) |
+           (x.xt ? BEER_ESTEP_X_XT : 0) | nchunks;
+}
+
 size_t beer_estep_workspace_bytes(int dtype, int cov, int D, int S, int G) {
     if (cov < 0 || cov > 2) return 0;
     dtype &= ~BEER_EXACT;
@@ -597,6 +672,8 @@ int beer_mixtureset_lognorm_image(int cov, int64_t T, int D, int S, int G, const
                                   void* workspace, size_t workspace_bytes, void* stream) {
     BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
     BEER_REQUIRE(frame_image && workspace && log_norm && (T == 0 || (X && exp_stats)));
+    // (an empty batch of a shape the image kernels do not take is refused like a full one)
+    BEER_REQUIRE(beer_mfma::llhx_form(cov, D, S, G, false, false, true, workspace_bytes).rc == BEER_OK);
     if (T == 0) return BEER_OK;
     return beer_mfma::estep_bf16x3(cov, T, D, S, G, X, exp_stats, log_weights, nullptr, log_norm,
                                    llh_sum, workspace, workspace_bytes, as_stream(stream), false,

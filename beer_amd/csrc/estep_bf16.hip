@@ -2242,36 +2242,98 @@ size_t estepx_workspace_bytes(int cov, int D, int S, int G) {
 
 bool supported_frame_image(int cov, int D);
 
-int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, const float* expT,
-                 const float* logw, float* resps, float* log_norm, double* llh_sum, void* ws,
-                 size_t ws_bytes, hipStream_t s, bool packed, const void* image) {
-    if (packed && S != 1 && !supported_llh_packed_sets(cov, D, S, G)) return BEER_EINVAL;
+// Every decision of estep_bf16x3, host only: the launcher below dispatches on the form,
+// beer_estep_route reports it.
+LlhxForm llhx_form(int cov, int D, int S, int G, bool resps, bool packed, bool image,
+                   size_t ws_bytes) {
+    LlhxForm f = {};
+    f.rc = BEER_EINVAL;
+    if (packed && S != 1 && !supported_llh_packed_sets(cov, D, S, G)) return f;
     if (!supported_llh_padded(D, S, G) || ws_bytes < estepx_workspace_bytes(cov, D, S, G))
-        return BEER_EINVAL;
+        return f;
     // mixture sets whose G is not a power of two: groups padded to Gp slots (logit
     // -1e30), log-normalisers only (the responsibilities would come out in the padded
     // layout)
-    const int Greal = G, Kreal = S * G;
+    const int Greal = G;
     if (S > 1) G = group_pad(G);
-    if (G != Greal && resps) return BEER_EINVAL;
+    if (G != Greal && resps) return f;
+    f.Gp = G;
+    f.packed = packed;
     const int K = S * G;
     // a set of at most 128 single Gaussians (the per-state log-likelihoods of an HMM with one
     // Gaussian per state: 120 states at config 4) is one chunk of 8 / 4 component tiles, not
     // of 16 half of which would be padding
-    const bool narrow = S > 1 && Greal == 1 && K <= 128 && !packed && !image;
+    f.narrow = S > 1 && Greal == 1 && K <= 128 && !packed && !image;
     // (a frame image of four k-steps, D = 41 .. 48: chunks of 8 component tiles, whose packed
     // parameters -- 96 KiB -- fit the LDS of lnfi_kernel; groups of 4 / 8 stay inside a lane)
-    const bool lnfi8 = image && !narrow && S > 1 && !resps && !packed && cov != BEER_FULL &&
-                       (nslab_of(cov, D) + 7) / 8 == 4 && (G == 4 || G == 8) &&
-                       beer::option(BEER_OPT_LNFI);
-    const int NT = narrow ? (K <= 64 ? 4 : 8) : (lnfi8 ? 8 : ntx_for(S, K));
-    const int nchunks = lnfi8 ? (K + 127) / 128 : nchunksx_for(S, K), nk = nk16_of(cov, D);
-    const int kpad = nchunks * NT * 16;
+    f.lnfi8 = image && !f.narrow && S > 1 && !resps && !packed && cov != BEER_FULL &&
+              (nslab_of(cov, D) + 7) / 8 == 4 && (G == 4 || G == 8) &&
+              beer::option(BEER_OPT_LNFI);
+    f.NT = f.narrow ? (K <= 64 ? 4 : 8) : (f.lnfi8 ? 8 : ntx_for(S, K));
+    f.nchunks = f.lnfi8 ? (K + 127) / 128 : nchunksx_for(S, K);
     // a frame fragment image: mixture sets, log-normalisers only, groups of >= 4 (refused
     // here, before anything is launched)
     if (image && (S == 1 || packed || resps || G < 4 || cov == BEER_FULL ||
                   !supported_frame_image(cov, D)))
-        return BEER_EINVAL;
+        return f;
+    f.rc = BEER_OK;
+    // log-normalisers only, groups of 4 / 8 / 16: the image is dealt out lane-major and the
+    // log-sum-exp of a state stays inside a lane (lognorm_epilogue_lane_major)
+    f.lane_major = S > 1 && !resps && !packed &&
+                   ((f.NT == 16 && (G == 4 || G == 8 || G == 16)) || f.lnfi8);
+    // the packed full-covariance forms stage a k-step's packed parameters in LDS (BL)
+    const bool k1_lds = cov == BEER_FULL && k1_lds_fits(D, nk16_of(cov, D)) &&
+                        beer::option(BEER_OPT_K1_LDS);
+    if (S == 1) {
+        f.gl = 16;
+        f.jw = 4;
+        f.GQ = f.NT == 4 ? 1 : (f.NT == 8 ? 2 : 4);
+        // 129 .. 256 components: a wave's 64 frames are one tile of the accumulation;
+        // it leaves them behind transposed
+        f.xt = packed && f.NT == 16;
+        f.bl = f.xt && k1_lds;
+        return f;
+    }
+    f.jw = G < 4 ? G : 4;
+    f.gl = f.lane_major ? 0 : (G < 4 ? 1 : (G < 64 ? G / 4 : 16));
+    const int gq = G <= 64 ? 1 : G / 64;
+    f.GQ = gq == 1 ? 1 : (gq == 2 ? 2 : 4);
+    if (f.narrow) {
+        f.GQ = 1;
+        return f;
+    }
+    if (packed) {
+        // the responsibilities within each state's mixture as the accumulation's LDS tiles
+        f.GQ = gq == 1 ? 1 : 2;
+        f.bl = k1_lds;
+        return f;
+    }
+    const int nku = (nslab_of(cov, D) + 7) / 8;
+    if (image && f.lane_major && (nku <= 3 || f.lnfi8) && beer::option(BEER_OPT_LNFI)) {
+        // lane-major groups over a frame image: the chunk's parameters in LDS, a workgroup
+        // walks a block of frames (lnfi_kernel)
+        f.lnfi = true;
+        f.nku = f.lnfi8 ? 4 : (nku == 1 ? 1 : (nku == 2 ? 2 : 3));
+        f.lnfi_g = G == 4 ? 4 : (G == 8 ? 8 : 16);
+        return f;
+    }
+    // ... with the A fragments from the caller's frame fragment image
+    f.img = image;
+    // log-normalisers only (the accumulation recomputes the responsibilities)
+    f.lno = image || (!resps && f.jw == 4);
+    return f;
+}
+
+int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, const float* expT,
+                 const float* logw, float* resps, float* log_norm, double* llh_sum, void* ws,
+                 size_t ws_bytes, hipStream_t s, bool packed, const void* image) {
+    const LlhxForm f = llhx_form(cov, D, S, G, resps != nullptr, packed, image != nullptr, ws_bytes);
+    if (f.rc != BEER_OK) return f.rc;
+    const int Greal = G, Kreal = S * G;
+    G = f.Gp;
+    const int K = S * G;
+    const int NT = f.NT, nchunks = f.nchunks, nk = nk16_of(cov, D);
+    const int kpad = nchunks * NT * 16;
     g_cov_of_launch = cov;
     char* w = reinterpret_cast<char*>(ws);
     void* P = w;
@@ -2280,10 +2342,7 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
     w += up256((size_t)(nk + 1) * 8 * sizeof(int));
     float* c0 = reinterpret_cast<float*>(w);
     hipLaunchKernelGGL(const_max_kernel, dim3(1), dim3(256), 0, s, cov, D, Kreal, expT, logw, c0);
-    // log-normalisers only, groups of 4 / 8 / 16: the image is dealt out lane-major and the
-    // log-sum-exp of a state stays inside a lane (lognorm_epilogue_lane_major)
-    const bool lane_major = S > 1 && !resps && !packed &&
-                            ((NT == 16 && (G == 4 || G == 8 || G == 16)) || lnfi8);
+    const bool lane_major = f.lane_major;
     hipLaunchKernelGGL(packx_kernel, dim3(kpad), dim3(256),
                        (size_t)stats_dim(cov, D) * sizeof(float), s, cov, D, Kreal, NT, expT, logw,
                        reinterpret_cast<unsigned short*>(P), tab, Greal, G, c0, lane_major ? 1 : 0);
@@ -2300,13 +2359,11 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
                                                            nk, X, P, tab, c0, resps, log_norm,    \
                                                            llh_sum, s, ##__VA_ARGS__);            \
     } while (0)
+    const int gl = f.gl, jw = f.jw;
     if (S == 1) {
-        const int gl = 16, jw = 4;
         if (packed) {
             if (NT == 4) BEER_LLHX(4, 2, 1, true, false);
             if (NT == 8) BEER_LLHX(8, 2, 2, true, false);
-            // 129 .. 256 components: a wave's 64 frames are one tile of the accumulation;
-            // it leaves them behind transposed
             float* xt = reinterpret_cast<float*>(reinterpret_cast<char*>(resps) +
                                                  packed_tiles_bytes(nframes, K));
             const int xtf = xt_pieces(D) * (kPiece / 4);
@@ -2316,7 +2373,7 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
             // 2.3 ms for 64 x 256 per wave with one wave per SIMD (a retired variant), whose
             // hand-placed main loop ran at 90 % of the MFMA rate but whose epilogue, 0.4 ms,
             // nothing covered.
-            if (full && k1_lds_fits(D, nk) && beer::option(BEER_OPT_K1_LDS))
+            if (f.bl)
                 return launch_llhx<16, 2, 4, true, false, false, false, true>(
                     nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm,
                     llh_sum, s, xt, xtf);
@@ -2326,17 +2383,13 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
         if (NT == 8) BEER_LLHX(8, 2, 2, false, false);
         BEER_LLHX(16, 2, 4, false, false);
     }
-    const int jw = G < 4 ? G : 4;
-    const int gl = lane_major ? 0 : (G < 4 ? 1 : (G < 64 ? G / 4 : 16));
-    const int gq = G <= 64 ? 1 : G / 64;
-    if (narrow) {
+    if (f.narrow) {
         if (NT == 4) BEER_LLHX(4, 2, 1, false, false);
         BEER_LLHX(8, 2, 1, false, false);
     }
     if (packed) {
-        // the responsibilities within each state's mixture as the accumulation's LDS tiles
-        if (full && k1_lds_fits(D, nk) && beer::option(BEER_OPT_K1_LDS)) {
-            if (gq == 1)
+        if (f.bl) {
+            if (f.GQ == 1)
                 return launch_llhx<16, 2, 1, true, false, false, false, true>(
                     nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm,
                     llh_sum, s);
@@ -2344,15 +2397,13 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
                 nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm, llh_sum,
                 s);
         }
-        switch (gq) {
+        switch (f.GQ) {
             case 1: BEER_LLHX(16, 2, 1, true, false);
             default: BEER_LLHX(16, 2, 2, true, false);
         }
     }
-    if (image && lane_major && ((nslab_of(cov, D) + 7) / 8 <= 3 || lnfi8) && beer::option(BEER_OPT_LNFI)) {
-        // lane-major groups over a frame image: the chunk's parameters in LDS, a workgroup
-        // walks a block of frames (lnfi_kernel)
-        const int nku = (nslab_of(cov, D) + 7) / 8;
+    if (f.lnfi) {
+        const int nku = f.nku;
         // frames per workgroup: whole rounds of its 8 waves (256 frames); the block length
         // that minimises rounds of 256 workgroups x (block + the LDS fill, worth ~128 frames)
         int64_t best_fpb = 256, best_cost = -1;
@@ -2377,35 +2428,33 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
         if (G == 4) BEER_LNFI(NKU_, 4, 16); else if (G == 8) BEER_LNFI(NKU_, 8, 16);             \
         else BEER_LNFI(NKU_, 16, 16);                                                            \
     } while (0)
-        if (lnfi8) { if (G == 4) BEER_LNFI(4, 4, 8); else BEER_LNFI(4, 8, 8); }
+        if (f.lnfi8) { if (G == 4) BEER_LNFI(4, 4, 8); else BEER_LNFI(4, 8, 8); }
         else if (nku == 1) BEER_LNFI_G(1); else if (nku == 2) BEER_LNFI_G(2); else BEER_LNFI_G(3);
 #undef BEER_LNFI_G
 #undef BEER_LNFI
         BEER_LAUNCH_CHECK();
         return BEER_OK;
     }
-    if (image) {
-        // ... with the A fragments from the caller's frame fragment image
+    if (f.img) {
 #define BEER_LNI(GQ_)                                                                            \
     return launch_llhx<16, 2, GQ_, false, true, true, true>(nframes, D, K, S, G, gl, jw, nchunks, \
                                                             nk, X, P, tab, c0, resps, log_norm,  \
                                                             llh_sum, s, nullptr, 0, image)
-        switch (gq) {
+        switch (f.GQ) {
             case 1: BEER_LNI(1);
             case 2: BEER_LNI(2);
             default: BEER_LNI(4);
         }
 #undef BEER_LNI
     }
-    if (!resps && jw == 4) {
-        // log-normalisers only (the accumulation recomputes the responsibilities)
-        switch (gq) {
+    if (f.lno) {
+        switch (f.GQ) {
             case 1: BEER_LLHX(16, 2, 1, false, true);
             case 2: BEER_LLHX(16, 2, 2, false, true);
             default: BEER_LLHX(16, 2, 4, false, true);
         }
     }
-    switch (gq) {
+    switch (f.GQ) {
         case 1: BEER_LLHX(16, 2, 1, false, false);
         case 2: BEER_LLHX(16, 2, 2, false, false);
         default: BEER_LLHX(16, 2, 4, false, false);

@@ -39,6 +39,25 @@ int estep_bf16x3(int cov, int64_t T, int D, int S, int G, const float* X, const 
                  size_t ws_bytes, hipStream_t s, bool packed = false,
                  const void* frame_image = nullptr);
 
+// The launch form of an E-step on the matrix cores, decided on the host from the shape, the
+// outputs wanted and the option table.  The launchers dispatch on it and beer_estep_route
+// (estep.hip) reports it: one copy of the rules.
+struct LlhForm {                     // llh_kernel<T, NT, MT, GQ> of estep_mfma.hip
+    int NT, GQ, jw, gl, nchunks;
+};
+LlhForm llh_form(int S, int G);
+struct LlhxForm {                    // llhx_kernel / lnfi_kernel of estep_bf16.hip
+    int rc;                          // BEER_EINVAL: estep_bf16x3 refuses the call
+    int NT, GQ, jw, gl, nchunks;
+    int Gp;                          // slots per group of the parameter image (>= G)
+    bool packed, lno, img, bl, narrow, lnfi8, lane_major;
+    bool xt;                         // 129 .. 256 components, packed: X^T left behind the tiles
+    bool lnfi;                       // lnfi_kernel<nku, lnfi_g, NT>
+    int nku, lnfi_g;
+};
+LlhxForm llhx_form(int cov, int D, int S, int G, bool resps, bool packed, bool image,
+                   size_t ws_bytes);
+
 int unpack_resps(int64_t T, int K, const void* packed, float* resps, hipStream_t s);
 // comp_resps [T, S*G] (x state_resps [T, S], nullable) -> packed tiles
 int pack_resps(int64_t T, int D, int S, int G, const float* X, const float* R, const float* SR,

@@ -428,7 +428,7 @@ int estep_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const 
     const int K = S * G;
     if (!supported_llh(D, S, G, sizeof(T)) || ws_bytes < estep_workspace_bytes(sizeof(T), cov, D, S, G))
         return BEER_EINVAL;
-    const int NT = nt_for(S, K), nchunks = nchunks_for(S, K);
+    const int NT = llh_form(S, G).NT, nchunks = llh_form(S, G).nchunks;
     const int nsp = nslab_padded(cov, D);
     const int nslab = nsp - 1;                                  // even, >= nslab_of()
     T* P = reinterpret_cast<T*>(ws);
@@ -448,16 +448,14 @@ int estep_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const 
 #define BEER_LLH(NT_, GQ_) \
     return launch_llh<T, NT_, MT, GQ_>(nframes, D, K, S, G, gl, jw, nchunks, nslab, X, P, tab, \
                                        c0, resps, log_norm, llh_sum, s)
+    const LlhForm f = llh_form(S, G);
+    const int gl = f.gl, jw = f.jw;
     if (S == 1) {                                   // one group = the whole (padded) chunk
-        const int gl = 16, jw = 4;
         if (NT == 4) BEER_LLH(4, 1);
         if (NT == 8) BEER_LLH(8, 2);
         BEER_LLH(16, 4);
     }
-    const int jw = G < 4 ? G : 4;
-    const int gl = G < 4 ? 1 : (G < 64 ? G / 4 : 16);
-    const int gq = G <= 64 ? 1 : G / 64;
-    switch (gq) {
+    switch (f.GQ) {
         case 1: BEER_LLH(16, 1);
         case 2: BEER_LLH(16, 2);
         default: BEER_LLH(16, 4);
@@ -530,6 +528,26 @@ static bool supported_llh_dim(int D, int S, int G, int max_d) {
     if (S == 1) return K >= 16 && K <= 256;
     return K >= 16 && G <= 256 && (G & (G - 1)) == 0;
 }
+// NT component tiles per chunk, GQ column tiles per group, jw components of a group per lane,
+// gl lanes per group, chunks of 256 components
+LlhForm llh_form(int S, int G) {
+    const int K = S * G;
+    LlhForm f;
+    f.NT = nt_for(S, K);
+    f.nchunks = nchunks_for(S, K);
+    if (S == 1) {
+        f.gl = 16;
+        f.jw = 4;
+        f.GQ = f.NT == 4 ? 1 : (f.NT == 8 ? 2 : 4);
+        return f;
+    }
+    f.jw = G < 4 ? G : 4;
+    f.gl = G < 4 ? 1 : (G < 64 ? G / 4 : 16);
+    const int gq = G <= 64 ? 1 : G / 64;
+    f.GQ = gq == 1 ? 1 : (gq == 2 ? 2 : 4);
+    return f;
+}
+
 bool supported_llh(int D, int S, int G, size_t elem) { return supported_llh_dim(D, S, G, max_dim(elem)); }
 bool supported_llh_x(int D, int S, int G) { return supported_llh_dim(D, S, G, kMaxDimX); }
 

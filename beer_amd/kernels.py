@@ -56,6 +56,29 @@ def normal_llh(stats, exp_stats, cov_type):
     return out
 
 
+def estep_call_plan(f32, exact, cov_type, D, S, G, labels, scale, want_resps, ws_bytes):
+    '''(need_resps, try_image) of a `beer_mixtureset_estep` call, from its arguments alone:
+    whether the call needs a responsibilities buffer, and whether the log-normalisers may
+    come from a frame image (`beer_mixtureset_lognorm_image`).  `f32`: float32 frames,
+    `exact`: on the exact fp32 kernels; `labels`: given or not; `ws_bytes`: what
+    `beer_estep_workspace_bytes` said (0: no matrix-core kernel for the shape).
+
+    The generic kernels normalise in place in the responsibilities buffer; the matrix-core
+    kernels keep them in registers.  Those take group-aligned shapes (one mixture, or G a
+    power of two) in every arithmetic -- the exact float32 ones up to D = 96, where the
+    workspace query still answers for the bf16x3 kernels -- and any G on the float32 bf16x3
+    path when no responsibilities are wanted (padded groups).  This restates the library's
+    dispatch; tests/test_estep_routes_host.py holds it against `beer_estep_route`.'''
+    aligned = S == 1 or (G & (G - 1)) == 0
+    fast = f32 and not exact
+    on_matrix_cores = ws_bytes > 0 and not labels and scale == 1.0 and \
+        ((aligned and not (f32 and exact and D > _hip.MAX_DIM_F32)) or (fast and not want_resps))
+    need_resps = want_resps or (G > 1 and not on_matrix_cores)
+    try_image = not need_resps and on_matrix_cores and S > 1 and G >= 4 and fast and \
+        cov_type != 'full'
+    return need_resps, try_image
+
+
 def mixtureset_estep(stats, exp_stats, log_weights, S, G, cov_type, labels=None,
                      want_resps=True, llh_sum=None):
     '''(log_norm [T,S], comp_resps [T,S*G] or None).  `log_weights` [S,G] or
@@ -71,21 +94,14 @@ def mixtureset_estep(stats, exp_stats, log_weights, S, G, cov_type, labels=None,
     log_norm = torch.empty(T, S, dtype=X.dtype, device=X.device)
     ws, ws_bytes = _hip.workspace('beer_estep_workspace_bytes', X.dtype,
                                   _hip.COV_CODE[cov_type], D, S, G, X.device)
-    # the generic kernels normalise in place in the responsibilities buffer; the
-    # matrix-core kernels keep them in registers.  Those take group-aligned shapes
-    # (one mixture, or G a power of two) in every arithmetic, and any G on the
-    # float32 bf16x3 path when no responsibilities are wanted (padded groups).
     exact = _exact(X)
-    aligned = S == 1 or (G & (G - 1)) == 0
-    on_matrix_cores = ws is not None and labels is None and st.scale == 1.0 and \
-        (aligned or (X.dtype == torch.float32 and not exact and not want_resps))
-    need_resps = want_resps or (G > 1 and not on_matrix_cores)
+    need_resps, try_image = estep_call_plan(X.dtype == torch.float32, exact, cov_type, D, S, G,
+                                            labels is not None, st.scale, want_resps, ws_bytes)
     resps = torch.empty(T, K, dtype=X.dtype, device=X.device) if need_resps else None
     lab = None
     if labels is not None:
         lab = _hip.on_device(torch.as_tensor(labels)).to(torch.int64).contiguous()
-    if not need_resps and on_matrix_cores and S > 1 and G >= 4 and not exact and \
-            X.dtype == torch.float32 and _hip.f32_fast_ok(X):
+    if try_image:
         # log-normalisers only, on the bf16x3 path: the logits' A fragments from the frame
         # fragment image where the frames have one (the fused accumulation uses the same)
         img = st.frame_image(cov_type)
@@ -106,7 +122,7 @@ def mixtureset_estep(stats, exp_stats, log_weights, S, G, cov_type, labels=None,
     try:
         launch(resps)
     except _hip.HipInvalid:
-        # `on_matrix_cores` above restates the library's own dispatch; should the two
+        # `estep_call_plan` restates the library's own dispatch; should the two
         # ever disagree, the library refuses a G > 1 call without a responsibilities
         # buffer (the generic kernels normalise in it): give it one
         if resps is not None or G == 1:

@@ -419,6 +419,59 @@ int beer_mixtureset_lognorm_image(int cov, int64_t T, int D, int S, int G, const
 int beer_frame_image(int cov, int64_t T, int D, const float* X, void* image,
                      size_t image_bytes, void* stream);
 
+/* The kernel family and launch form an E-step entry point picks for a call (host only: it
+ * launches nothing and touches no device), built from the launchers' own decisions
+ * (estep.hip: estep_plan; estep_mfma.hip: llh_form; estep_bf16.hip: llhx_form); it reads
+ * BEER_OPT_K1_LDS and BEER_OPT_LNFI from the option table as they do.
+ *   entry            BEER_ESTEP_PLAIN: beer_mixtureset_estep; BEER_ESTEP_PACKED:
+ *                    beer_mixture_estep_packed (S == 1, K = G) / beer_mixtureset_estep_packed
+ *                    (S > 1); BEER_ESTEP_IMAGE: beer_mixtureset_lognorm_image
+ *   dtype            BEER_F32 / BEER_F64, | BEER_EXACT
+ *   args             which arguments are non-NULL (BEER_ARG_RESPS: comp_resps / packed_resps),
+ *                    BEER_ARG_SCALED: stat_scale != 1
+ *   workspace_bytes  0: no workspace
+ * BEER_EINVAL exactly where the entry point refuses the call (T >= 0 and the frames given);
+ * else family | form:
+ *   BEER_ESTEP_GENERIC   | BEER_ESTEP_GENERIC_PASS1 / _FUSED / _NORMALISE / _LABELS
+ *   BEER_ESTEP_EXACT_F32 / _F64 (llh_kernel<T, NT, MT, GQ>)
+ *                        | NT (4 / 8 / 16) | GQ (1 / 2 / 4) << 5 | jw << 8 | chunks << 16
+ *   BEER_ESTEP_LLHX (llhx_kernel<NT, MT, GQ, PACKED, SQ, LNO, IMG, BL>; SQ = not full)
+ *                        | NT | GQ << 5 | BEER_ESTEP_X_* | chunks << 16
+ *   BEER_ESTEP_LNFI (lnfi_kernel<NKU, G, NT>)
+ *                        | NT (16 / 8) | NKU (1 .. 4) << 5 | G (4 / 8 / 16) << 8 | chunks << 16
+ * chunks: component chunks of 16 NT slots (capped at 4095 in the value).  Every form is held
+ * against the oracle in tests/test_gpu_estep_routes.py. */
+#define BEER_ESTEP_PLAIN 0
+#define BEER_ESTEP_PACKED 1
+#define BEER_ESTEP_IMAGE 2
+#define BEER_ARG_PC_LLH 1u
+#define BEER_ARG_LOG_NORM 2u
+#define BEER_ARG_RESPS 4u
+#define BEER_ARG_LLH_SUM 8u
+#define BEER_ARG_LABELS 16u
+#define BEER_ARG_SCALED 32u
+#define BEER_ARG_LOG_WEIGHTS 64u
+#define BEER_ESTEP_GENERIC 0x10000000
+#define BEER_ESTEP_EXACT_F32 0x20000000
+#define BEER_ESTEP_EXACT_F64 0x30000000
+#define BEER_ESTEP_LLHX 0x40000000
+#define BEER_ESTEP_LNFI 0x50000000
+#define BEER_ESTEP_FAMILY(route) ((route) & 0x70000000)
+#define BEER_ESTEP_GENERIC_PASS1 1      /* llh_kernel alone (pc_llh, or G == 1 log_norm) */
+#define BEER_ESTEP_GENERIC_FUSED 2      /* llh_kernel with the normalisation inside */
+#define BEER_ESTEP_GENERIC_NORMALISE 3  /* llh_kernel + normalise_kernel */
+#define BEER_ESTEP_GENERIC_LABELS 4     /* llh_kernel + labels_kernel */
+#define BEER_ESTEP_X_PACKED 0x100       /* responsibilities as packed tiles */
+#define BEER_ESTEP_X_LNO 0x200          /* log-normalisers only */
+#define BEER_ESTEP_X_IMG 0x400          /* A fragments from the frame image */
+#define BEER_ESTEP_X_BL 0x800           /* packed parameters staged in LDS (BEER_OPT_K1_LDS) */
+#define BEER_ESTEP_X_NARROW 0x1000      /* <= 128 single Gaussians: one chunk of 4 / 8 tiles */
+#define BEER_ESTEP_X_LANE_MAJOR 0x2000  /* groups of 4 / 8 / 16 inside a lane */
+#define BEER_ESTEP_X_PADDED 0x4000      /* groups padded to a power of two */
+#define BEER_ESTEP_X_XT 0x8000          /* 129 .. 256 packed components: X^T left behind */
+int beer_estep_route(int entry, int dtype, int cov, int D, int S, int G, unsigned args,
+                     size_t workspace_bytes);
+
 /* Mixture-weight statistics from the accumulated Gaussian statistics: the
  * zero-order count is N_k = -2 * acc[k, Q-2]; out[s,g] = N_{s,g} for
  * g < G-1 and out[s,G-1] = sum_g N_{s,g} -- the "last column <- row sum"
