@@ -365,8 +365,12 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def stream_id():
+    return torch.cuda.current_stream().cuda_stream
+
+
 def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return ctypes.c_void_p(stream_id())
 
 
 def call(name, *args):
@@ -440,58 +444,48 @@ def call_host(name, *args):
         raise HipInvalid(f'{name} failed: invalid argument')
 
 
-# Scratch buffers are filed per (query, shape, device, STREAM): two host threads on two streams
-# get buffers of their own; two threads sharing ONE stream would share them, which the stream's
+# Scratch buffers are filed per (key, device, STREAM): two host threads on two streams get
+# buffers of their own; two threads sharing ONE stream would share them, which the stream's
 # order makes safe (a kernel that uses a workspace is queued before the next one that does).
 _workspaces = {}
 
 
-def workspace(query, dtype, cov, D, S, G, device):
-    '''(tensor, nbytes) scratch for the MFMA implementation of a call, or
-    (None, 0) when the shape has none.  One buffer per (query, shape, stream)
-    is kept and reused: the kernels leave no state in it.'''
-    nbytes = getattr(lib(), query)(dtype_code(dtype), cov, D, S, G)
+def scratch(key, nbytes, device):
+    '''(tensor, nbytes) scratch of `nbytes` for the call `key` names, or (None, 0) for none:
+    one buffer per (key, device, current stream) is kept, reused and grown on demand -- the
+    kernels leave no state in it.'''
     if nbytes == 0:
         return None, 0
-    key = (query, dtype, cov, D, S, G, device, torch.cuda.current_stream().cuda_stream)
+    key = (key, device, stream_id())
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _workspaces[key] = buf
+        buf = _workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
     return buf, nbytes
+
+
+def workspace(query, dtype, cov, D, S, G, device):
+    '''`scratch` for the MFMA implementation of a call, of the size `query` gives its shape
+    ((None, 0) when the shape has none).'''
+    return scratch((query, dtype, cov, D, S, G),
+                   getattr(lib(), query)(dtype_code(dtype), cov, D, S, G), device)
 
 
 def frames_workspace(dtype, exact, cov, T, D, S, G, device):
-    """(tensor, nbytes) scratch of `beer_normal_accumulate` over T frames (for some shapes it
-    holds per-chain partial sums, hence T); one buffer per (shape, stream), grown on demand."""
-    nbytes = lib().beer_accumulate_frames_workspace_bytes(dtype_code(dtype, exact), cov, T, D, S, G)
-    if nbytes == 0:
-        return None, 0
-    key = ('frames', dtype, cov, D, S, G, device, torch.cuda.current_stream().cuda_stream)
-    buf = _workspaces.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _workspaces[key] = buf
-    return buf, nbytes
+    """`scratch` of `beer_normal_accumulate` over T frames (for some shapes it holds per-chain
+    partial sums, hence T)."""
+    return scratch(('frames', dtype, cov, D, S, G), lib().beer_accumulate_frames_workspace_bytes(
+        dtype_code(dtype, exact), cov, T, D, S, G), device)
 
 
 def packed_workspace(cov, T, D, K, device, sets=None):
-    '''(tensor, nbytes) scratch of `beer_normal_accumulate_packed` (grows with T:
-    it holds the transposed frames) or, with `sets = (S, G)`, of
-    `beer_mixtureset_accumulate_packed` (... and state posteriors); one buffer per
-    (shape, stream), grown on demand.'''
+    '''`scratch` of `beer_normal_accumulate_packed` (grows with T: it holds the transposed
+    frames) or, with `sets = (S, G)`, of `beer_mixtureset_accumulate_packed` (... and state
+    posteriors).'''
     if sets is None:
         nbytes = lib().beer_accumulate_packed_workspace_bytes(cov, T, D, K)
     else:
         nbytes = lib().beer_mixtureset_accumulate_packed_workspace_bytes(cov, T, D, *sets)
-    if nbytes == 0:
-        return None, 0
-    key = ('packed', cov, D, K, device, torch.cuda.current_stream().cuda_stream)
-    buf = _workspaces.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _workspaces[key] = buf
-    return buf, nbytes
+    return scratch(('packed', cov, D, K), nbytes, device)
 
 
 _staging = threading.local()    # per host thread: .ring [(pinned buffer, event)], .next

@@ -321,9 +321,11 @@ struct EstepPlan {
     int rc;                 // BEER_EINVAL: the entry point refuses the call
     bool exact_mfma;        // the exact fp32 / fp64 MFMA kernel (estep_mfma.hip)
     bool use_x;             // the bf16x3 kernels (estep_bf16.hip)
-    bool need_norm;         // generic: a normalisation follows pass 1 ...
-    bool fuse;              // ... inside pass 1
-    bool ln_is_w;           // G == 1, no responsibilities wanted: pass 1 writes log_norm
+    // generic: pass 1 writes the per-component values to pc_llh and, when a normalisation
+    // follows (need_norm), the logits to comp_resps ...
+    bool need_norm;
+    bool fuse;              // ... which happens inside pass 1: it writes log_norm and llh_sum
+    bool pc_in_resps;       // labels without pc_llh: labels_kernel reads them from comp_resps
 };
 
 EstepPlan estep_plan(size_t elem, bool exact, int cov, int D, int S, int G, bool pc_llh,
@@ -351,11 +353,11 @@ EstepPlan estep_plan(size_t elem, bool exact, int cov, int D, int S, int G, bool
                          (log_norm || comp_resps || llh_sum);
     p.use_x = mfma_ok && p.use_x;
     p.exact_mfma = mfma_ok && !p.use_x;
-    // G == 1: log_norm == w; let pass 1 write into log_norm directly (the matrix-core
+    // G == 1: log_norm == w; the fused pass 1 writes log_norm and no logits (the matrix-core
     // path keeps the responsibilities in registers and needs no buffer for any G).
-    p.ln_is_w = p.need_norm && !comp_resps && !mfma_ok;
-    if (p.ln_is_w && !(G == 1 && log_norm)) return p;
+    if (p.need_norm && !comp_resps && !mfma_ok && !(G == 1 && log_norm)) return p;
     if (labels && !(pc_llh || comp_resps)) return p;
+    p.pc_in_resps = labels && !pc_llh;
     // generic kernels; the normalisation is fused when a component chunk holds
     // whole states
     p.fuse = !mfma_ok && p.need_norm && !labels && (kCompChunk % G == 0) && (comp_resps || G == 1);
@@ -371,23 +373,14 @@ int estep_launch(int cov, int64_t nframes, int D, int S, int G, const void* X, c
     BEER_REQUIRE(nframes >= 0 && X && expT);
     const EstepPlan p = estep_plan(sizeof(T), exact, cov, D, S, G, pc_llh, log_norm, comp_resps,
                                    llh_sum, labels, stat_scale == 1.0, ws, ws_bytes);
-    if (p.rc != BEER_OK) return p.rc;
-    if (nframes == 0) return BEER_OK;
+    if (p.rc != BEER_OK || nframes == 0) return p.rc;
     hipStream_t s = as_stream(stream);
-    const int K = S * G;
-    const bool need_norm = p.need_norm, use_x = p.use_x, mfma_ok = p.use_x || p.exact_mfma;
-    void* w_buf = p.ln_is_w ? log_norm : comp_resps;
-    int rc;
-    void* pc_arg = labels ? (pc_llh ? pc_llh : comp_resps) : pc_llh;
-    void* w_arg = labels ? nullptr : (need_norm ? w_buf : nullptr);
-
-    if (mfma_ok) {
-        // gfx950 matrix-core path: GEMM + (grouped) softmax fused, one kernel
-        if (use_x)
-            return beer_mfma::estep_bf16x3(cov, nframes, D, S, G, (const float*)X,
-                                           (const float*)expT, (const float*)logw,
-                                           (float*)comp_resps, (float*)log_norm, llh_sum, ws,
-                                           ws_bytes, s);
+    // gfx950 matrix-core path: GEMM + (grouped) softmax fused, one kernel
+    if (p.use_x)
+        return beer_mfma::estep_bf16x3(cov, nframes, D, S, G, (const float*)X, (const float*)expT,
+                                       (const float*)logw, (float*)comp_resps, (float*)log_norm,
+                                       llh_sum, ws, ws_bytes, s);
+    if (p.exact_mfma)
         return sizeof(T) == 4
                    ? beer_mfma::estep_f32(cov, nframes, D, S, G, (const float*)X,
                                           (const float*)expT, (const float*)logw,
@@ -397,39 +390,27 @@ int estep_launch(int cov, int64_t nframes, int D, int S, int G, const void* X, c
                                           (const double*)expT, (const double*)logw,
                                           (double*)comp_resps, (double*)log_norm, llh_sum, ws,
                                           ws_bytes, s);
-    }
-    const bool fuse = p.fuse;
-    const int fuse_G = fuse ? G : 0;
-    void* ln_arg = fuse ? log_norm : nullptr;
-    double* sum_arg = fuse ? llh_sum : nullptr;
-    if (fuse && w_buf == log_norm) w_arg = nullptr;      // G == 1, no resps wanted
-    if (cov == BEER_FULL)
-        rc = llh_launch<T, BEER_FULL>(nframes, D, K, X, expT, logw, stat_scale, pc_arg, w_arg,
-                                      fuse_G, ln_arg, sum_arg, s);
-    else if (cov == BEER_DIAG)
-        rc = llh_launch<T, BEER_DIAG>(nframes, D, K, X, expT, logw, stat_scale, pc_arg, w_arg,
-                                      fuse_G, ln_arg, sum_arg, s);
-    else
-        rc = llh_launch<T, BEER_ISO>(nframes, D, K, X, expT, logw, stat_scale, pc_arg, w_arg,
-                                     fuse_G, ln_arg, sum_arg, s);
+    const int K = S * G;
+    void* pc = p.pc_in_resps ? comp_resps : pc_llh;
+    static_assert(BEER_FULL == 0 && BEER_DIAG == 1 && BEER_ISO == 2, "pass1 is indexed by cov");
+    constexpr decltype(&llh_launch<T, BEER_FULL>) pass1[] = {
+        llh_launch<T, BEER_FULL>, llh_launch<T, BEER_DIAG>, llh_launch<T, BEER_ISO>};
+    const int rc = pass1[cov](nframes, D, K, X, expT, logw, stat_scale, pc,
+                              p.need_norm ? comp_resps : nullptr, p.fuse ? G : 0,
+                              p.fuse ? log_norm : nullptr, p.fuse ? llh_sum : nullptr, s);
     if (rc != BEER_OK) return rc;
-    if (fuse) return BEER_OK;
-
     if (labels) {
-        const T* pc = (const T*)pc_arg;
         // when pc aliases comp_resps the kernel reads pc[t,label] before it
         // overwrites the row: one thread owns the whole row.
         hipLaunchKernelGGL(labels_kernel<T>, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0,
-                           s, nframes, K, labels, pc, (T*)comp_resps, (T*)log_norm, llh_sum);
+                           s, nframes, K, labels, (const T*)pc, (T*)comp_resps, (T*)log_norm,
+                           llh_sum);
         BEER_LAUNCH_CHECK();
-        return BEER_OK;
-    }
-    if (need_norm) {
+    } else if (p.need_norm && !p.fuse) {
+        // (a normalisation that is not fused has a responsibilities buffer: estep_plan)
         const int64_t n = nframes * S;
-        const bool alias = (w_buf == log_norm);
         hipLaunchKernelGGL(normalise_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                           nframes, S, G, (T*)w_buf, alias ? (T*)nullptr : (T*)log_norm,
-                           comp_resps != nullptr, llh_sum);
+                           nframes, S, G, (T*)comp_resps, (T*)log_norm, true, llh_sum);
         BEER_LAUNCH_CHECK();
     }
     return BEER_OK;
@@ -503,6 +484,37 @@ int segment_sum_launch(int32_t nutt, const int64_t* frame_off, const void* v, do
     return BEER_OK;
 }
 
+// What the packed (one mixture, or `set`) and the image entry points refuse, from the shape,
+// the arguments given and the workspace (0 bytes: none): they call it with what they were
+// handed, beer_estep_route with its mask.  The rest is estep_bf16x3's own (llhx_form).
+int estepx_refusal(int entry, bool set, int cov, int D, int S, int G, unsigned args,
+                   size_t ws_bytes) {
+    const bool packed = entry == BEER_ESTEP_PACKED, resps = args & BEER_ARG_RESPS;
+    BEER_REQUIRE(D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
+    BEER_REQUIRE(!(args & (BEER_ARG_PC_LLH | BEER_ARG_LABELS | BEER_ARG_SCALED)));
+    // packed: responsibilities; one mixture needs its weights, a set a shape the packed
+    // accumulation takes too.  Image: log-normalisers only
+    if (packed)
+        BEER_REQUIRE(resps && (set ? beer_mixtureset_packed_supported(cov, D, S, G)
+                                   : S == 1 && (args & BEER_ARG_LOG_WEIGHTS)));
+    else
+        BEER_REQUIRE((args & BEER_ARG_LOG_NORM) && !resps);
+    return beer_mfma::llhx_form(cov, D, S, G, packed, packed, !packed, ws_bytes).rc;
+}
+
+// ... and what they do once their own pointer checks are through
+int estepx_entry(int entry, bool set, int cov, int64_t T, int D, int S, int G, const float* X,
+                 const float* exp_stats, const float* logw, const void* image, float* log_norm,
+                 void* resps, double* llh_sum, void* ws, size_t ws_bytes, void* stream) {
+    const unsigned args = (log_norm ? BEER_ARG_LOG_NORM : 0u) | (resps ? BEER_ARG_RESPS : 0u) |
+                          (llh_sum ? BEER_ARG_LLH_SUM : 0u) | (logw ? BEER_ARG_LOG_WEIGHTS : 0u);
+    const int rc = estepx_refusal(entry, set, cov, D, S, G, args, ws ? ws_bytes : 0);
+    if (rc != BEER_OK || T == 0) return rc;
+    return beer_mfma::estep_bf16x3(cov, T, D, S, G, X, exp_stats, logw, (float*)resps, log_norm,
+                                   llh_sum, ws, ws_bytes, as_stream(stream),
+                                   entry == BEER_ESTEP_PACKED, image);
+}
+
 }  // namespace
 
 extern "C" {
@@ -523,14 +535,12 @@ int beer_estep_route(int entry, int dtype, int cov, int D, int S, int G, unsigne
     const bool exact = (dtype & BEER_EXACT) != 0;
     dtype &= ~BEER_EXACT;
     BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
-    BEER_REQUIRE(D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    const bool pc = args & BEER_ARG_PC_LLH, ln = args & BEER_ARG_LOG_NORM;
-    const bool resps = args & BEER_ARG_RESPS, sum = args & BEER_ARG_LLH_SUM;
-    const bool labels = args & BEER_ARG_LABELS, logw = args & BEER_ARG_LOG_WEIGHTS;
-    beer_mfma::LlhxForm x = {};
+    const bool resps = args & BEER_ARG_RESPS, labels = args & BEER_ARG_LABELS;
+    bool packed = false;
     if (entry == BEER_ESTEP_PLAIN) {
-        const EstepPlan p = estep_plan(dtype == BEER_F64 ? 8 : 4, exact, cov, D, S, G, pc, ln, resps,
-                                       sum, labels, !(args & BEER_ARG_SCALED),
+        const EstepPlan p = estep_plan(dtype == BEER_F64 ? 8 : 4, exact, cov, D, S, G,
+                                       args & BEER_ARG_PC_LLH, args & BEER_ARG_LOG_NORM, resps,
+                                       args & BEER_ARG_LLH_SUM, labels, !(args & BEER_ARG_SCALED),
                                        workspace_bytes > 0, workspace_bytes);
         if (p.rc != BEER_OK) return p.rc;
         if (p.exact_mfma) {
@@ -543,21 +553,17 @@ int beer_estep_route(int entry, int dtype, int cov, int D, int S, int G, unsigne
                                          : !p.need_norm ? BEER_ESTEP_GENERIC_PASS1
                                          : p.fuse ? BEER_ESTEP_GENERIC_FUSED
                                                   : BEER_ESTEP_GENERIC_NORMALISE);
-        x = beer_mfma::llhx_form(cov, D, S, G, resps, false, false, workspace_bytes);
-    } else if (entry == BEER_ESTEP_PACKED) {
-        // one mixture: beer_mixture_estep_packed (K = G); a set: beer_mixtureset_estep_packed
-        BEER_REQUIRE(dtype == BEER_F32 && !exact && !pc && !labels && !(args & BEER_ARG_SCALED));
-        BEER_REQUIRE(resps && workspace_bytes > 0);
-        if (S == 1) BEER_REQUIRE(logw && beer_mfma::supported_llh_x(D, 1, G));
-        else BEER_REQUIRE(beer_mixtureset_packed_supported(cov, D, S, G));
-        x = beer_mfma::llhx_form(cov, D, S, G, true, true, false, workspace_bytes);
-    } else if (entry == BEER_ESTEP_IMAGE) {
-        BEER_REQUIRE(dtype == BEER_F32 && !exact && !pc && !labels && !(args & BEER_ARG_SCALED));
-        BEER_REQUIRE(ln && !resps && workspace_bytes > 0);
-        x = beer_mfma::llhx_form(cov, D, S, G, false, false, true, workspace_bytes);
+    } else if (entry == BEER_ESTEP_PACKED || entry == BEER_ESTEP_IMAGE) {
+        // the float32 entry points of the bf16x3 kernels; packed: beer_mixture_estep_packed for
+        // one mixture (K = G), beer_mixtureset_estep_packed for a set
+        BEER_REQUIRE(dtype == BEER_F32 && !exact);
+        BEER_REQUIRE(estepx_refusal(entry, S != 1, cov, D, S, G, args, workspace_bytes) == BEER_OK);
+        packed = entry == BEER_ESTEP_PACKED;
     } else {
         return BEER_EINVAL;
     }
+    const beer_mfma::LlhxForm x = beer_mfma::llhx_form(cov, D, S, G, resps, packed,
+                                                       entry == BEER_ESTEP_IMAGE, workspace_bytes);
     if (x.rc != BEER_OK) return x.rc;
     const int nchunks = (x.nchunks > 0xfff ? 0xfff : x.nchunks) << 16;
     if (x.lnfi) return BEER_ESTEP_LNFI | x.NT | x.nku << 5 | x.lnfi_g << 8 | nchunks;
@@ -601,14 +607,9 @@ int beer_mixture_estep_packed(int cov, int64_t T, int D, int K, const float* X,
                               const float* exp_stats, const float* log_weights, float* log_norm,
                               void* packed_resps, double* llh_sum, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && K >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(X && exp_stats && log_weights && packed_resps && workspace);
-    BEER_REQUIRE(beer_mfma::supported_llh_x(D, 1, K));
-    BEER_REQUIRE(workspace_bytes >= beer_mfma::estepx_workspace_bytes(cov, D, 1, K));
-    if (T == 0) return BEER_OK;
-    return beer_mfma::estep_bf16x3(cov, T, D, 1, K, X, exp_stats, log_weights,
-                                   reinterpret_cast<float*>(packed_resps), log_norm, llh_sum,
-                                   workspace, workspace_bytes, as_stream(stream), true);
+    BEER_REQUIRE(T >= 0 && X && exp_stats);
+    return estepx_entry(BEER_ESTEP_PACKED, false, cov, T, D, 1, K, X, exp_stats, log_weights, nullptr,
+                        log_norm, packed_resps, llh_sum, workspace, workspace_bytes, stream);
 }
 
 int beer_normal_accumulate_packed(int cov, int64_t T, int D, int K, const float* X,
@@ -638,14 +639,9 @@ int beer_mixtureset_estep_packed(int cov, int64_t T, int D, int S, int G, const 
                                  const float* exp_stats, const float* log_weights,
                                  float* log_norm, void* packed_resps, double* llh_sum,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(X && exp_stats && packed_resps && workspace);
-    BEER_REQUIRE(beer_mixtureset_packed_supported(cov, D, S, G));
-    BEER_REQUIRE(workspace_bytes >= beer_mfma::estepx_workspace_bytes(cov, D, S, G));
-    if (T == 0) return BEER_OK;
-    return beer_mfma::estep_bf16x3(cov, T, D, S, G, X, exp_stats, log_weights,
-                                   reinterpret_cast<float*>(packed_resps), log_norm, llh_sum,
-                                   workspace, workspace_bytes, as_stream(stream), true);
+    BEER_REQUIRE(T >= 0 && X && exp_stats);
+    return estepx_entry(BEER_ESTEP_PACKED, true, cov, T, D, S, G, X, exp_stats, log_weights, nullptr,
+                        log_norm, packed_resps, llh_sum, workspace, workspace_bytes, stream);
 }
 
 int beer_mixtureset_accumulate_packed(int cov, int64_t T, int D, int S, int G, const float* X,
@@ -670,14 +666,10 @@ int beer_mixtureset_lognorm_image(int cov, int64_t T, int D, int S, int G, const
                                   const float* exp_stats, const float* log_weights,
                                   const void* frame_image, float* log_norm, double* llh_sum,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(frame_image && workspace && log_norm && (T == 0 || (X && exp_stats)));
     // (an empty batch of a shape the image kernels do not take is refused like a full one)
-    BEER_REQUIRE(beer_mfma::llhx_form(cov, D, S, G, false, false, true, workspace_bytes).rc == BEER_OK);
-    if (T == 0) return BEER_OK;
-    return beer_mfma::estep_bf16x3(cov, T, D, S, G, X, exp_stats, log_weights, nullptr, log_norm,
-                                   llh_sum, workspace, workspace_bytes, as_stream(stream), false,
-                                   frame_image);
+    BEER_REQUIRE(T >= 0 && frame_image && (T == 0 || (X && exp_stats)));
+    return estepx_entry(BEER_ESTEP_IMAGE, true, cov, T, D, S, G, X, exp_stats, log_weights,
+                        frame_image, log_norm, nullptr, llh_sum, workspace, workspace_bytes, stream);
 }
 
 size_t beer_frame_image_bytes(int cov, int64_t T, int D) {

@@ -716,33 +716,44 @@ inline bool k1_lds_fits(int D, int nk) {
     return 2 * lds <= (size_t)beer::kMaxDynLds;
 }
 
-// covariance type of the E-step being launched (the launch helpers below take the
-// shape, not the type; SQ = false kernels are full covariance by construction)
-thread_local int g_cov_of_launch = BEER_FULL;
+// What estep_bf16x3 hands its kernels: the padded shape, the launch form, the parameter image
+// in the workspace and the caller's buffers (absent outputs are null).
+struct LlhxArgs {
+    int64_t nframes;
+    int D, K, S, G;                  // K = S G, G the padded group size
+    int gl, jw, nchunks, nk;
+    int nku;                         // k-steps that hold slabs (the table's slab count)
+    const float* X;
+    const void* P;                   // packed parameters, slab table, constant
+    const int* tab;
+    const float* c0;
+    float *resps, *log_norm;
+    double* llh_sum;
+    float* xt_out;                   // X^T left behind the packed tiles (xt), xt_floats per tile
+    int xt_floats;
+    const void* img;                 // the caller's frame fragment image
+    hipStream_t s;
+};
 
 template <int NT, int MT, int GQ, bool PACKED = false, bool SQ = true, bool LNO = false,
           bool IMG = false, bool BL = false>
-int launch_llhx(int64_t nframes, int D, int K, int S, int G, int gl, int jw, int nchunks, int nk,
-                const float* X, const void* P, const int* tab, const float* c0, float* resps,
-                float* log_norm, double* llh_sum, hipStream_t s, float* xt_out = nullptr,
-                int xt_floats = 0, const void* img = nullptr) {
-    const int LD = ld16_of(D);
-    // k-steps that hold slabs: the slab count is the table's (full: SQ = false)
-    const int nku = (nslabx_of(SQ ? g_cov_of_launch : BEER_FULL, D) + 7) / 8;
+int launch_llhx(const LlhxArgs& a) {
+    const int LD = ld16_of(a.D);
     constexpr int FB = 16 * MT * (kThreads / 64);
-    size_t lds = (size_t)FB * LD * sizeof(float) + (size_t)(nk + 1) * 8 * sizeof(int);
+    size_t lds = (size_t)FB * LD * sizeof(float) + (size_t)(a.nk + 1) * 8 * sizeof(int);
     if (BL) lds = ((lds + 1023) & ~(size_t)1023) + 2 * (size_t)(8 * kBlockU4 * 16);
-    const int64_t blocks = (nframes + FB - 1) / FB;
-    if (nchunks != (K + 16 * NT - 1) / (16 * NT)) return BEER_EINVAL;
-    const int cg = xcd_chunk_group(nchunks, (size_t)nku * NT * kBlockU4 * 16);
+    const int64_t blocks = (a.nframes + FB - 1) / FB;
+    if (a.nchunks != (a.K + 16 * NT - 1) / (16 * NT)) return BEER_EINVAL;
+    const int cg = xcd_chunk_group(a.nchunks, (size_t)a.nku * NT * kBlockU4 * 16);
     (void)hipFuncSetAttribute(
         reinterpret_cast<const void*>(llhx_kernel<NT, MT, GQ, PACKED, SQ, LNO, IMG, BL>),
         hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
     hipLaunchKernelGGL((llhx_kernel<NT, MT, GQ, PACKED, SQ, LNO, IMG, BL>),
-                       dim3(nchunks > 1 ? xcd_grid(blocks, nchunks, cg) : (unsigned)blocks),
-                       dim3(kThreads), lds, s, nframes, D, K, S, G, gl, jw, nk, X,
-                       reinterpret_cast<const u4*>(P), tab, resps, log_norm, llh_sum, xt_out,
-                       xt_floats, nku, cg, c0, reinterpret_cast<const u4*>(img));
+                       dim3(a.nchunks > 1 ? xcd_grid(blocks, a.nchunks, cg) : (unsigned)blocks),
+                       dim3(kThreads), lds, a.s, a.nframes, a.D, a.K, a.S, a.G, a.gl, a.jw, a.nk,
+                       a.X, reinterpret_cast<const u4*>(a.P), a.tab, a.resps, a.log_norm,
+                       a.llh_sum, a.xt_out, a.xt_floats, a.nku, cg, a.c0,
+                       reinterpret_cast<const u4*>(a.img));
     BEER_LAUNCH_CHECK();
     return BEER_OK;
 }
@@ -2324,142 +2335,129 @@ LlhxForm llhx_form(int cov, int D, int S, int G, bool resps, bool packed, bool i
     return f;
 }
 
+namespace {
+
+// frames per workgroup of lnfi_kernel: whole rounds of its 8 waves (256 frames); the block
+// length that minimises rounds of 256 workgroups x (block + the LDS fill, worth ~128 frames)
+int64_t lnfi_frames_per_workgroup(int64_t nframes, int nchunks) {
+    int64_t best_fpb = 256, best_cost = -1;
+    for (int64_t fpb = 256; fpb <= 8192; fpb += 256) {
+        const int64_t wgs = (nframes + fpb - 1) / fpb * nchunks;
+        const int64_t cost = (wgs + 255) / 256 * (fpb + 128);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_fpb = fpb; }
+    }
+    return best_fpb;
+}
+
+// lane-major groups over a frame image: the chunk's parameters in LDS, a workgroup walks a
+// block of frames
+template <int NKU, int G, int NT>
+int launch_lnfi(const LlhxArgs& a) {
+    const int64_t fpb = lnfi_frames_per_workgroup(a.nframes, a.nchunks);
+    const size_t lds = (size_t)NKU * NT * kBlockU4 * 16;
+    const dim3 grid(xcd_grid((a.nframes + fpb - 1) / fpb, a.nchunks, a.nchunks));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lnfi_kernel<NKU, G, NT>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL((lnfi_kernel<NKU, G, NT>), grid, dim3(512), lds, a.s, a.nframes, a.K, a.S,
+                       a.nk, reinterpret_cast<const u4*>(a.img), reinterpret_cast<const u4*>(a.P),
+                       a.log_norm, a.llh_sum, fpb, a.c0);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+// The instantiations estep_bf16x3 launches, keyed on the form: llhx_kernel<NT, 2, GQ, packed,
+// SQ, lno, img, bl> (nku = 0) with SQ = false for full covariances, or lnfi_kernel<nku, GQ, NT>
+// (GQ: the group size; diagonal / isotropic only).
+struct LlhxRow {
+    int NT, GQ, nku;
+    bool packed, lno, img, bl;
+    int (*full)(const LlhxArgs&);
+    int (*sq)(const LlhxArgs&);
+};
+template <int NT, int GQ, bool PACKED, bool LNO>
+constexpr LlhxRow llhx_row() {
+    return {NT, GQ, 0, PACKED, LNO, false, false, launch_llhx<NT, 2, GQ, PACKED, false, LNO>,
+            launch_llhx<NT, 2, GQ, PACKED, true, LNO>};
+}
+// a k-step's packed parameters staged in LDS (packed, full covariance)
+template <int GQ>
+constexpr LlhxRow bl_row() {
+    return {16, GQ, 0, true, false, false, true,
+            launch_llhx<16, 2, GQ, true, false, false, false, true>, nullptr};
+}
+// the A fragments from the caller's frame fragment image (log-normalisers only)
+template <int GQ>
+constexpr LlhxRow img_row() {
+    return {16, GQ, 0, false, true, true, false, nullptr,
+            launch_llhx<16, 2, GQ, false, true, true, true>};
+}
+template <int NKU, int G, int NT>
+constexpr LlhxRow lnfi_row() {
+    return {NT, G, NKU, false, false, false, false, nullptr, launch_lnfi<NKU, G, NT>};
+}
+const LlhxRow kLlhxRows[] = {
+    // one mixture, packed: NT = 4 / 8 / 16.  At 16 (32 frames x 256 components per wave, two
+    // waves per SIMD) the epilogue of one wave (its 48 KB of packed tiles leave at the CU's
+    // store-issue rate) runs under the other's MFMAs.  Measured at K = 256, D = 40, 1 M frames:
+    // 2.0 ms against 2.3 ms for 64 x 256 per wave with one wave per SIMD (a retired variant),
+    // whose hand-placed main loop ran at 90 % of the MFMA rate but whose epilogue, 0.4 ms,
+    // nothing covered.
+    llhx_row<4, 1, true, false>(), llhx_row<8, 2, true, false>(), bl_row<4>(),
+    llhx_row<16, 4, true, false>(),
+    // one mixture; a set of at most 128 single Gaussians (narrow: GQ = 1)
+    llhx_row<4, 1, false, false>(), llhx_row<8, 2, false, false>(), llhx_row<16, 4, false, false>(),
+    llhx_row<8, 1, false, false>(),
+    // mixture sets, packed
+    bl_row<1>(), bl_row<2>(), llhx_row<16, 1, true, false>(), llhx_row<16, 2, true, false>(),
+    lnfi_row<4, 4, 8>(), lnfi_row<4, 8, 8>(),
+    lnfi_row<1, 4, 16>(), lnfi_row<1, 8, 16>(), lnfi_row<1, 16, 16>(),
+    lnfi_row<2, 4, 16>(), lnfi_row<2, 8, 16>(), lnfi_row<2, 16, 16>(),
+    lnfi_row<3, 4, 16>(), lnfi_row<3, 8, 16>(), lnfi_row<3, 16, 16>(),
+    img_row<1>(), img_row<2>(), img_row<4>(),
+    // mixture sets: log-normalisers only, then with responsibilities
+    llhx_row<16, 1, false, true>(), llhx_row<16, 2, false, true>(), llhx_row<16, 4, false, true>(),
+    llhx_row<16, 1, false, false>(), llhx_row<16, 2, false, false>(),
+};
+
+}  // namespace
+
 int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, const float* expT,
                  const float* logw, float* resps, float* log_norm, double* llh_sum, void* ws,
                  size_t ws_bytes, hipStream_t s, bool packed, const void* image) {
     const LlhxForm f = llhx_form(cov, D, S, G, resps != nullptr, packed, image != nullptr, ws_bytes);
     if (f.rc != BEER_OK) return f.rc;
-    const int Greal = G, Kreal = S * G;
-    G = f.Gp;
-    const int K = S * G;
-    const int NT = f.NT, nchunks = f.nchunks, nk = nk16_of(cov, D);
-    const int kpad = nchunks * NT * 16;
-    g_cov_of_launch = cov;
+    const int Kreal = S * G, nk = nk16_of(cov, D);
+    LlhxArgs a = {};
+    a.nframes = nframes, a.D = D, a.K = S * f.Gp, a.S = S, a.G = f.Gp;
+    a.gl = f.gl, a.jw = f.jw, a.nchunks = f.nchunks, a.nk = nk;
+    a.nku = (nslabx_of(cov, D) + 7) / 8;
+    a.X = X, a.resps = resps, a.log_norm = log_norm, a.llh_sum = llh_sum, a.img = image, a.s = s;
     char* w = reinterpret_cast<char*>(ws);
-    void* P = w;
-    w += p_image_bytes(nchunks, nk, NT);
+    a.P = w;
+    w += p_image_bytes(f.nchunks, nk, f.NT);
     int* tab = reinterpret_cast<int*>(w);
     w += up256((size_t)(nk + 1) * 8 * sizeof(int));
     float* c0 = reinterpret_cast<float*>(w);
+    a.tab = tab, a.c0 = c0;
+    if (f.xt) {
+        a.xt_out = reinterpret_cast<float*>(reinterpret_cast<char*>(resps) +
+                                            packed_tiles_bytes(nframes, a.K));
+        a.xt_floats = xt_pieces(D) * (kPiece / 4);
+    }
     hipLaunchKernelGGL(const_max_kernel, dim3(1), dim3(256), 0, s, cov, D, Kreal, expT, logw, c0);
-    const bool lane_major = f.lane_major;
-    hipLaunchKernelGGL(packx_kernel, dim3(kpad), dim3(256),
-                       (size_t)stats_dim(cov, D) * sizeof(float), s, cov, D, Kreal, NT, expT, logw,
-                       reinterpret_cast<unsigned short*>(P), tab, Greal, G, c0, lane_major ? 1 : 0);
+    hipLaunchKernelGGL(packx_kernel, dim3(f.nchunks * f.NT * 16), dim3(256),
+                       (size_t)stats_dim(cov, D) * sizeof(float), s, cov, D, Kreal, f.NT, expT, logw,
+                       reinterpret_cast<unsigned short*>(ws), tab, G, f.Gp, c0,
+                       f.lane_major ? 1 : 0);
     BEER_LAUNCH_CHECK();
-    const bool full = cov == BEER_FULL;
-#define BEER_LLHX(NT_, MT_, GQ_, PK_, LNO_, ...)                                                  \
-    do {                                                                                          \
-        if (full)                                                                                 \
-            return launch_llhx<NT_, MT_, GQ_, PK_, false, LNO_>(nframes, D, K, S, G, gl, jw,      \
-                                                                nchunks, nk, X, P, tab, c0,       \
-                                                                resps, log_norm, llh_sum, s,      \
-                                                                ##__VA_ARGS__);                   \
-        return launch_llhx<NT_, MT_, GQ_, PK_, true, LNO_>(nframes, D, K, S, G, gl, jw, nchunks,  \
-                                                           nk, X, P, tab, c0, resps, log_norm,    \
-                                                           llh_sum, s, ##__VA_ARGS__);            \
-    } while (0)
-    const int gl = f.gl, jw = f.jw;
-    if (S == 1) {
-        if (packed) {
-            if (NT == 4) BEER_LLHX(4, 2, 1, true, false);
-            if (NT == 8) BEER_LLHX(8, 2, 2, true, false);
-            float* xt = reinterpret_cast<float*>(reinterpret_cast<char*>(resps) +
-                                                 packed_tiles_bytes(nframes, K));
-            const int xtf = xt_pieces(D) * (kPiece / 4);
-            // 32 frames x 256 components per wave, two waves per SIMD: the epilogue of one
-            // wave (its 48 KB of packed tiles leave at the CU's store-issue rate) runs under
-            // the other's MFMAs.  Measured at K = 256, D = 40, 1 M frames: 2.0 ms against
-            // 2.3 ms for 64 x 256 per wave with one wave per SIMD (a retired variant), whose
-            // hand-placed main loop ran at 90 % of the MFMA rate but whose epilogue, 0.4 ms,
-            // nothing covered.
-            if (f.bl)
-                return launch_llhx<16, 2, 4, true, false, false, false, true>(
-                    nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm,
-                    llh_sum, s, xt, xtf);
-            BEER_LLHX(16, 2, 4, true, false, xt, xtf);
+    const int nku = f.lnfi ? f.nku : 0, gq = f.lnfi ? f.lnfi_g : f.GQ;
+    for (const LlhxRow& r : kLlhxRows)
+        if (r.NT == f.NT && r.GQ == gq && r.nku == nku && r.packed == f.packed && r.lno == f.lno &&
+            r.img == f.img && r.bl == f.bl) {
+            const auto launch = cov == BEER_FULL ? r.full : r.sq;
+            return launch ? launch(a) : BEER_EINVAL;
         }
-        if (NT == 4) BEER_LLHX(4, 2, 1, false, false);
-        if (NT == 8) BEER_LLHX(8, 2, 2, false, false);
-        BEER_LLHX(16, 2, 4, false, false);
-    }
-    if (f.narrow) {
-        if (NT == 4) BEER_LLHX(4, 2, 1, false, false);
-        BEER_LLHX(8, 2, 1, false, false);
-    }
-    if (packed) {
-        if (f.bl) {
-            if (f.GQ == 1)
-                return launch_llhx<16, 2, 1, true, false, false, false, true>(
-                    nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm,
-                    llh_sum, s);
-            return launch_llhx<16, 2, 2, true, false, false, false, true>(
-                nframes, D, K, S, G, gl, jw, nchunks, nk, X, P, tab, c0, resps, log_norm, llh_sum,
-                s);
-        }
-        switch (f.GQ) {
-            case 1: BEER_LLHX(16, 2, 1, true, false);
-            default: BEER_LLHX(16, 2, 2, true, false);
-        }
-    }
-    if (f.lnfi) {
-        const int nku = f.nku;
-        // frames per workgroup: whole rounds of its 8 waves (256 frames); the block length
-        // that minimises rounds of 256 workgroups x (block + the LDS fill, worth ~128 frames)
-        int64_t best_fpb = 256, best_cost = -1;
-        for (int64_t fpb = 256; fpb <= 8192; fpb += 256) {
-            const int64_t wgs = (nframes + fpb - 1) / fpb * nchunks;
-            const int64_t cost = (wgs + 255) / 256 * (fpb + 128);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_fpb = fpb; }
-        }
-        const size_t lds = (size_t)nku * NT * kBlockU4 * 16;
-        const int64_t gz = (nframes + best_fpb - 1) / best_fpb;
-        const dim3 grid(xcd_grid(gz, nchunks, nchunks));
-#define BEER_LNFI(NKU_, G_, NT_)                                                                 \
-    do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lnfi_kernel<NKU_, G_, NT_>),     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
-        hipLaunchKernelGGL((lnfi_kernel<NKU_, G_, NT_>), grid, dim3(512), lds, s, nframes, K, S, \
-                           nk, reinterpret_cast<const u4*>(image), reinterpret_cast<const u4*>(P), \
-                           log_norm, llh_sum, best_fpb, c0);                                     \
-    } while (0)
-#define BEER_LNFI_G(NKU_)                                                                        \
-    do {                                                                                         \
-        if (G == 4) BEER_LNFI(NKU_, 4, 16); else if (G == 8) BEER_LNFI(NKU_, 8, 16);             \
-        else BEER_LNFI(NKU_, 16, 16);                                                            \
-    } while (0)
-        if (f.lnfi8) { if (G == 4) BEER_LNFI(4, 4, 8); else BEER_LNFI(4, 8, 8); }
-        else if (nku == 1) BEER_LNFI_G(1); else if (nku == 2) BEER_LNFI_G(2); else BEER_LNFI_G(3);
-#undef BEER_LNFI_G
-#undef BEER_LNFI
-        BEER_LAUNCH_CHECK();
-        return BEER_OK;
-    }
-    if (f.img) {
-#define BEER_LNI(GQ_)                                                                            \
-    return launch_llhx<16, 2, GQ_, false, true, true, true>(nframes, D, K, S, G, gl, jw, nchunks, \
-                                                            nk, X, P, tab, c0, resps, log_norm,  \
-                                                            llh_sum, s, nullptr, 0, image)
-        switch (f.GQ) {
-            case 1: BEER_LNI(1);
-            case 2: BEER_LNI(2);
-            default: BEER_LNI(4);
-        }
-#undef BEER_LNI
-    }
-    if (f.lno) {
-        switch (f.GQ) {
-            case 1: BEER_LLHX(16, 2, 1, false, true);
-            case 2: BEER_LLHX(16, 2, 2, false, true);
-            default: BEER_LLHX(16, 2, 4, false, true);
-        }
-    }
-    switch (f.GQ) {
-        case 1: BEER_LLHX(16, 2, 1, false, false);
-        case 2: BEER_LLHX(16, 2, 2, false, false);
-        default: BEER_LLHX(16, 2, 4, false, false);
-    }
-#undef BEER_LLHX
+    return BEER_EINVAL;
 }
 
 size_t accx_base_workspace_bytes(int cov, int D, int K) {

@@ -406,17 +406,27 @@ size_t align_up(size_t n) { return (n + 255) / 256 * 256; }
 inline int nt_for(int S, int K) { return S > 1 ? 16 : (K <= 64 ? 4 : (K <= 128 ? 8 : 16)); }
 inline int nchunks_for(int S, int K) { return S > 1 ? (K + 255) / 256 : 1; }
 
-template <typename T, int NT, int MT, int GQ>
-int launch_llh(int64_t nframes, int D, int K, int S, int G, int gl, int jw, int nchunks,
-               int nslab, const T* X, const T* P, const int* tab, const T* c0, T* resps,
-               T* log_norm, double* llh_sum, hipStream_t s) {
-    const int D4 = d4_of(D), LD = 4 * D4 + 5;
+template <typename T>
+struct LlhArgs {                    // of llh_kernel: shape, form, parameter image, outputs (or null)
+    int64_t nframes;
+    int D, K, S, G, gl, jw, nchunks, nslab;
+    const T *X, *P;
+    const int* tab;
+    const T* c0;
+    T *resps, *log_norm;
+    double* llh_sum;
+    hipStream_t s;
+};
+
+template <typename T, int NT, int GQ>
+int launch_llh(const LlhArgs<T>& a) {
+    constexpr int MT = sizeof(T) == 4 ? 2 : 1;
     constexpr int FB = 16 * MT * (kThreads / 64);
-    const size_t lds = (size_t)FB * LD * sizeof(T);
-    const int64_t blocks = (nframes + FB - 1) / FB;
-    hipLaunchKernelGGL((llh_kernel<T, NT, MT, GQ>), dim3((unsigned)blocks, (unsigned)nchunks),
-                       dim3(kThreads), lds, s, nframes, D, K, S, G, gl, jw, nslab, X, P, tab,
-                       resps, log_norm, llh_sum, c0);
+    const size_t lds = (size_t)FB * (4 * d4_of(a.D) + 5) * sizeof(T);
+    const int64_t blocks = (a.nframes + FB - 1) / FB;
+    hipLaunchKernelGGL((llh_kernel<T, NT, MT, GQ>), dim3((unsigned)blocks, (unsigned)a.nchunks),
+                       dim3(kThreads), lds, a.s, a.nframes, a.D, a.K, a.S, a.G, a.gl, a.jw,
+                       a.nslab, a.X, a.P, a.tab, a.resps, a.log_norm, a.llh_sum, a.c0);
     BEER_LAUNCH_CHECK();
     return BEER_OK;
 }
@@ -428,15 +438,12 @@ int estep_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const 
     const int K = S * G;
     if (!supported_llh(D, S, G, sizeof(T)) || ws_bytes < estep_workspace_bytes(sizeof(T), cov, D, S, G))
         return BEER_EINVAL;
-    const int NT = llh_form(S, G).NT, nchunks = llh_form(S, G).nchunks;
-    const int nsp = nslab_padded(cov, D);
-    const int nslab = nsp - 1;                                  // even, >= nslab_of()
+    const LlhForm f = llh_form(S, G);
+    const int NT = f.NT, nchunks = f.nchunks, nsp = nslab_padded(cov, D);
     T* P = reinterpret_cast<T*>(ws);
-    const size_t p_bytes = (size_t)nchunks * nsp * 64 * NT * sizeof(T);
-    int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up<T>(p_bytes));
     const int64_t total = (int64_t)nchunks * nsp * 64 * NT;
-    int64_t pblocks = (total + 255) / 256;
-    if (pblocks > 65535) pblocks = 65535;
+    int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + align_up<T>(total * sizeof(T)));
+    const int64_t pblocks = (total + 255) / 256 > 65535 ? 65535 : (total + 255) / 256;
     // (the constant's slot: behind the slab table, inside the workspace's spare 256 bytes)
     T* c0 = reinterpret_cast<T*>(reinterpret_cast<char*>(tab) +
                                  ((size_t)nsp * sizeof(int) + 15) / 16 * 16);
@@ -444,23 +451,15 @@ int estep_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const 
     hipLaunchKernelGGL(pack_kernel<T>, dim3((unsigned)pblocks), dim3(256), 0, s, cov, D, K, NT,
                        nchunks, expT, logw, P, tab, c0);
     BEER_LAUNCH_CHECK();
-    constexpr int MT = sizeof(T) == 4 ? 2 : 1;
-#define BEER_LLH(NT_, GQ_) \
-    return launch_llh<T, NT_, MT, GQ_>(nframes, D, K, S, G, gl, jw, nchunks, nslab, X, P, tab, \
-                                       c0, resps, log_norm, llh_sum, s)
-    const LlhForm f = llh_form(S, G);
-    const int gl = f.gl, jw = f.jw;
-    if (S == 1) {                                   // one group = the whole (padded) chunk
-        if (NT == 4) BEER_LLH(4, 1);
-        if (NT == 8) BEER_LLH(8, 2);
-        BEER_LLH(16, 4);
-    }
-    switch (f.GQ) {
-        case 1: BEER_LLH(16, 1);
-        case 2: BEER_LLH(16, 2);
-        default: BEER_LLH(16, 4);
-    }
-#undef BEER_LLH
+    const LlhArgs<T> a = {nframes, D, K, S, G, f.gl, f.jw, nchunks, nsp - 1 /* even, >= nslab_of() */,
+                          X, P, tab, c0, resps, log_norm, llh_sum, s};
+    // one mixture: one group = the whole (padded) chunk, GQ = NT / 4; a set: NT = 16
+    static constexpr struct { int NT, GQ; int (*launch)(const LlhArgs<T>&); } kForms[] = {
+        {4, 1, launch_llh<T, 4, 1>},   {8, 2, launch_llh<T, 8, 2>},   {16, 4, launch_llh<T, 16, 4>},
+        {16, 1, launch_llh<T, 16, 1>}, {16, 2, launch_llh<T, 16, 2>}};
+    for (const auto& k : kForms)
+        if (k.NT == NT && k.GQ == f.GQ) return k.launch(a);
+    return BEER_EINVAL;
 }
 
 template <typename T>

@@ -4,6 +4,7 @@ Shapes and argument checks only: the arithmetic is in beer_amd/csrc.  All
 returned tensors live on the GPU.
 """
 
+import functools
 import os
 
 import torch
@@ -56,27 +57,25 @@ def normal_llh(stats, exp_stats, cov_type):
     return out
 
 
-def estep_call_plan(f32, exact, cov_type, D, S, G, labels, scale, want_resps, ws_bytes):
-    '''(need_resps, try_image) of a `beer_mixtureset_estep` call, from its arguments alone:
-    whether the call needs a responsibilities buffer, and whether the log-normalisers may
-    come from a frame image (`beer_mixtureset_lognorm_image`).  `f32`: float32 frames,
-    `exact`: on the exact fp32 kernels; `labels`: given or not; `ws_bytes`: what
-    `beer_estep_workspace_bytes` said (0: no matrix-core kernel for the shape).
+@functools.lru_cache(maxsize=4096)
+def estep_buffers(dtype_code, cov, D, S, G, args, ws_bytes):
+    '''(need_resps, image_ok) of the `beer_mixtureset_estep` call with the `_hip.ARG_*` mask
+    `args` and a workspace of `ws_bytes`, as the library's own `beer_estep_route` answers (host
+    only, integers only): whether the call must be given a responsibilities buffer -- the
+    caller wants one, or the library refuses the call without one and takes it with one (the
+    generic kernels normalise in it) -- and whether `beer_mixtureset_lognorm_image` takes the
+    same call with a frame image.  A call refused either way raises `HipInvalid`.
 
-    The generic kernels normalise in place in the responsibilities buffer; the matrix-core
-    kernels keep them in registers.  Those take group-aligned shapes (one mixture, or G a
-    power of two) in every arithmetic -- the exact float32 ones up to D = 96, where the
-    workspace query still answers for the bf16x3 kernels -- and any G on the float32 bf16x3
-    path when no responsibilities are wanted (padded groups).  This restates the library's
-    dispatch; tests/test_estep_routes_host.py holds it against `beer_estep_route`.'''
-    aligned = S == 1 or (G & (G - 1)) == 0
-    fast = f32 and not exact
-    on_matrix_cores = ws_bytes > 0 and not labels and scale == 1.0 and \
-        ((aligned and not (f32 and exact and D > _hip.MAX_DIM_F32)) or (fast and not want_resps))
-    need_resps = want_resps or (G > 1 and not on_matrix_cores)
-    try_image = not need_resps and on_matrix_cores and S > 1 and G >= 4 and fast and \
-        cov_type != 'full'
-    return need_resps, try_image
+    Cached: the refusals behind the query (`estep_plan`, `llhx_form`) read the shape, the mask
+    and the workspace size only, never the option table.  The form does: it is not kept.'''
+    def refused(entry, mask):
+        return _hip.estep_route(entry, dtype_code, cov, D, S, G, mask, ws_bytes) == _hip.EINVAL
+    need_resps = bool(args & _hip.ARG_RESPS)
+    if not need_resps and refused(_hip.ESTEP_PLAIN, args):
+        need_resps = True
+    if need_resps and refused(_hip.ESTEP_PLAIN, args | _hip.ARG_RESPS):
+        raise _hip.HipInvalid('beer_mixtureset_estep failed: invalid argument')
+    return need_resps, not refused(_hip.ESTEP_IMAGE, args)
 
 
 def mixtureset_estep(stats, exp_stats, log_weights, S, G, cov_type, labels=None,
@@ -91,47 +90,30 @@ def mixtureset_estep(stats, exp_stats, log_weights, S, G, cov_type, labels=None,
     K = S * G
     if E.shape[0] != K:
         raise ValueError(f'{E.shape[0]} Gaussians for {S} x {G} mixture components')
+    code, cov = _hip.dtype_code(X.dtype, _exact(X)), _hip.COV_CODE[cov_type]
+    ws, ws_bytes = _hip.workspace('beer_estep_workspace_bytes', X.dtype, cov, D, S, G, X.device)
+    args = _hip.ARG_LOG_NORM | (_hip.ARG_RESPS if want_resps else 0) | \
+        (0 if llh_sum is None else _hip.ARG_LLH_SUM) | (0 if lw is None else _hip.ARG_LOG_WEIGHTS) | \
+        (0 if labels is None else _hip.ARG_LABELS) | (_hip.ARG_SCALED if st.scale != 1.0 else 0)
+    need_resps, image_ok = estep_buffers(code, cov, D, S, G, args, ws_bytes)
     log_norm = torch.empty(T, S, dtype=X.dtype, device=X.device)
-    ws, ws_bytes = _hip.workspace('beer_estep_workspace_bytes', X.dtype,
-                                  _hip.COV_CODE[cov_type], D, S, G, X.device)
-    exact = _exact(X)
-    need_resps, try_image = estep_call_plan(X.dtype == torch.float32, exact, cov_type, D, S, G,
-                                            labels is not None, st.scale, want_resps, ws_bytes)
+    # log-normalisers only, on the bf16x3 path: the logits' A fragments from the frame
+    # fragment image where the frames have one (the fused accumulation uses the same)
+    img = st.frame_image(cov_type) if image_ok else None
+    if img is not None:
+        _hip.call('beer_mixtureset_lognorm_image', cov, T, D, S, G, _hip.ptr(X), _hip.ptr(E),
+                  _hip.ptr(lw), _hip.ptr(img), _hip.ptr(log_norm), _hip.ptr(llh_sum),
+                  _hip.ptr(ws), ws_bytes)
+        return log_norm, None
+    # (the generic kernels normalise in the responsibilities buffer: wanted or not)
     resps = torch.empty(T, K, dtype=X.dtype, device=X.device) if need_resps else None
     lab = None
     if labels is not None:
         lab = _hip.on_device(torch.as_tensor(labels)).to(torch.int64).contiguous()
-    if try_image:
-        # log-normalisers only, on the bf16x3 path: the logits' A fragments from the frame
-        # fragment image where the frames have one (the fused accumulation uses the same)
-        img = st.frame_image(cov_type)
-        if img is not None:
-            try:
-                _hip.call('beer_mixtureset_lognorm_image', _hip.COV_CODE[cov_type], T, D, S, G,
-                          _hip.ptr(X), _hip.ptr(E), _hip.ptr(lw), _hip.ptr(img),
-                          _hip.ptr(log_norm), _hip.ptr(llh_sum), _hip.ptr(ws), ws_bytes)
-                return log_norm, None
-            except _hip.HipInvalid:
-                pass          # a shape the image kernels do not take (refused before any launch)
-
-    def launch(resps):
-        _hip.call('beer_mixtureset_estep', _hip.dtype_code(X.dtype, exact),
-                  _hip.COV_CODE[cov_type], T, D, S, G, _hip.ptr(X), _hip.ptr(E), _hip.ptr(lw),
-                  _hip.ptr(lab), st.scale, None, _hip.ptr(log_norm), _hip.ptr(resps),
-                  _hip.ptr(llh_sum), _hip.ptr(ws), ws_bytes)
-    try:
-        launch(resps)
-    except _hip.HipInvalid:
-        # `estep_call_plan` restates the library's own dispatch; should the two
-        # ever disagree, the library refuses a G > 1 call without a responsibilities
-        # buffer (the generic kernels normalise in it): give it one
-        if resps is not None or G == 1:
-            raise
-        resps = torch.empty(T, K, dtype=X.dtype, device=X.device)
-        launch(resps)
-        if not want_resps:
-            resps = None
-    return log_norm, resps
+    _hip.call('beer_mixtureset_estep', code, cov, T, D, S, G, _hip.ptr(X), _hip.ptr(E),
+              _hip.ptr(lw), _hip.ptr(lab), st.scale, None, _hip.ptr(log_norm), _hip.ptr(resps),
+              _hip.ptr(llh_sum), _hip.ptr(ws), ws_bytes)
+    return log_norm, resps if want_resps else None
 
 
 class PackedResps:
@@ -422,11 +404,9 @@ def mixtureset_accumulate_fused(stats, exp_stats, log_weights, log_norm, state_r
     if acc is None:
         acc = torch.zeros(K, st.shape[1], dtype=torch.float64, device=X.device)
     code = _hip.COV_CODE[cov_type]
-    nbytes = _hip.lib().beer_accumulate_fused_workspace_bytes(code, D, S, G)
-    key = ('accf', code, D, S, G, X.device, torch.cuda.current_stream().cuda_stream)
-    ws = _hip._workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _hip._workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    ws, nbytes = _hip.scratch(('accf', code, D, S, G),
+                              _hip.lib().beer_accumulate_fused_workspace_bytes(code, D, S, G),
+                              X.device)
     img = st.frame_image(cov_type)
     _hip.call('beer_mixtureset_accumulate_fused', code, T, D, S, G, _hip.ptr(X), _hip.ptr(E),
               _hip.ptr(lw), _hip.ptr(ln), _hip.ptr(sr), _hip.ptr(img), _hip.ptr(acc), _hip.ptr(ws),
@@ -707,12 +687,7 @@ def frames_llh_backward(stats, weights, grad, exp_stats):
         # the matrix-core kernels of this call are bf16x3; without a workspace the library
         # runs its thread-per-output kernel (float64 accumulation): exact, and slow
         nbytes = 0
-    ws = None
-    if nbytes:
-        key = ('sgrad', cov, D, K, X.device, torch.cuda.current_stream().cuda_stream)
-        ws = _hip._workspaces.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _hip._workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    ws, nbytes = _hip.scratch(('sgrad', cov, D, K), nbytes, X.device)
     _hip.call('beer_frames_llh_backward', code, cov, T, D, K, _hip.ptr(X), _hip.ptr(w),
               _hip.ptr(g), _hip.ptr(E), _hip.ptr(out), _hip.ptr(ws), nbytes)
     if st.scale != 1.0:

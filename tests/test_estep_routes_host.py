@@ -1,8 +1,8 @@
 """CPU checks of the E-step dispatch: `beer_estep_route` on both sides of every boundary of the
 launch code (csrc/estep.hip estep_plan, estep_mfma.hip llh_form, estep_bf16.hip llhx_form), the
 refusals of the entry points themselves, the case table of tests/test_gpu_estep_routes.py (every
-case's stated form what the query gives, every form the query can return named by a case), the
-Python restatement of the dispatch (`kernels.estep_call_plan`) against the library, and the
+case's stated form what the query gives, every form the query can return named by a case), what
+Python concludes from the query (`kernels.estep_buffers`), and the
 conditions under which the generated inputs of tests/estep_truth.py can tell a wrong kernel from a
 right one."""
 
@@ -321,33 +321,79 @@ def test_case_table_covers_what_the_issue_lists():
     assert table.RAGGED == (31, 32, 33, 63, 64, 65, 127, 128, 257)
 
 
-# --- Python's restatement of the dispatch --------------------------------------------------------
+# --- the refusals, once: entry point and query ---------------------------------------------------
+
+def test_packed_and_image_entry_points_refuse_what_the_query_refuses():
+    '''`beer_mixture_estep_packed`, `beer_mixtureset_estep_packed` and `beer_mixtureset_lognorm_image`
+    with T = 0 against the query on the rows of the boundary table that name them: the same answer
+    on both sides of every boundary, and each of the three on both sides of at least one.'''
+    buf = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p)
+    lib, seen = _hip.lib(), set()
+    for kw, _ in BOUNDARIES:
+        k = dict(arith='x', cov='full', D=13, S=1, G=16, args=LN | SUM | LW, ws=None, opts=())
+        k.update(kw)
+        a, cov, D, S, G = k['args'], _hip.COV_CODE[k['cov']], k['D'], k['S'], k['G']
+        if k.get('entry', PLAIN) == PLAIN or k['arith'] != 'x' or a & (PC | LABELS | SCALED) or k['opts']:
+            continue            # (no such argument; the options move no refusal)
+        if k['entry'] == IMAGE and a & RESPS:
+            continue
+        full = ws_bytes('x', k['cov'], D, S, G)
+        nws = full if k['ws'] is None else (0 if k['ws'] == 0 else full + k['ws'])
+        given = [buf if a & bit else None for bit in (LW, LN, RESPS, SUM)]
+        tail = (buf if nws else None, nws, None)
+        if k['entry'] == IMAGE:
+            name = 'beer_mixtureset_lognorm_image'
+            rc = lib.beer_mixtureset_lognorm_image(cov, 0, D, S, G, buf, buf, given[0], buf, given[1],
+                                                   given[3], *tail)
+        elif S == 1:
+            name = 'beer_mixture_estep_packed'
+            rc = lib.beer_mixture_estep_packed(cov, 0, D, G, buf, buf, *given, *tail)
+        else:
+            name = 'beer_mixtureset_estep_packed'
+            rc = lib.beer_mixtureset_estep_packed(cov, 0, D, S, G, buf, buf, *given, *tail)
+        refused = _hip.estep_route(k['entry'], _hip.F32, cov, D, S, G, a, nws) == EINVAL
+        assert rc in (0, EINVAL) and (rc == EINVAL) == refused, (name, kw, rc)
+        seen.add((name, refused))
+    assert seen == {(n, r) for n in ('beer_mixture_estep_packed', 'beer_mixtureset_estep_packed',
+                                     'beer_mixtureset_lognorm_image') for r in (False, True)}
+    # one mixture through the entry point of sets: refused, whatever the query says of S = 1
+    assert lib.beer_mixtureset_estep_packed(0, 0, 13, 1, 16, buf, buf, buf, buf, buf, None, buf,
+                                            ws_bytes('x', 'full', 13, 1, 16), None) == EINVAL
+
+
+# --- what Python concludes from the query --------------------------------------------------------
 
 def test_python_plan_agrees_with_the_library(swept):
-    '''`kernels.estep_call_plan` over the sweep: it asks for a responsibilities buffer whenever the
+    '''`kernels.estep_buffers` over the sweep: it asks for a responsibilities buffer whenever the
     library would run the generic kernels with G > 1, it never leaves the matrix cores by asking
     for one the caller does not want, and it never offers a frame image where the library refuses
-    one.  (It disagreed for exact float32 frames at 96 < D <= 128, where the workspace query
-    answers for the bf16x3 kernels: the call went through the `HipInvalid` retry.)'''
+    one -- by construction now: need_resps is "wanted, or refused without and taken with", image_ok
+    is "the image query does not refuse", and a call refused either way raises.  (The predicate it
+    replaces disagreed with the library for exact float32 frames at 96 < D <= 128.)'''
     lib = _hip.lib()
     for call, r in swept[1, 1]:
         entry, arith, cov, D, S, G, args, nws = call
         if entry != PLAIN or args == PC:
             continue
         want_resps = bool(args & RESPS)
-        need, image = kernels.estep_call_plan(arith != 'f64', arith == 'exact', cov, D, S, G,
-                                              bool(args & LABELS), .5 if args & SCALED else 1.,
-                                              want_resps, nws)
-        given = (args | RESPS) if need else args
-        got = lib.beer_estep_route(PLAIN, CODE_OF[arith], _hip.COV_CODE[cov], D, S, G, given, nws)
-        assert got != EINVAL or (S > 1 and args & LABELS), call
-        if _hip.estep_family(r if r != EINVAL else got) == _hip.ESTEP_GENERIC and G > 1:
+        code, c = CODE_OF[arith], _hip.COV_CODE[cov]
+        with_resps = lib.beer_estep_route(PLAIN, code, c, D, S, G, args | RESPS, nws)
+        if (r == EINVAL or want_resps) and with_resps == EINVAL:
+            assert S > 1 and args & LABELS, call
+            with pytest.raises(_hip.HipInvalid):
+                kernels.estep_buffers(code, c, D, S, G, args, nws)
+            continue
+        need, image = kernels.estep_buffers(code, c, D, S, G, args, nws)
+        assert need == (want_resps or (r == EINVAL and with_resps != EINVAL)), call
+        assert image == (lib.beer_estep_route(IMAGE, code, c, D, S, G, args, nws) != EINVAL), call
+        got = with_resps if need else r
+        assert got != EINVAL, call
+        if _hip.estep_family(got) == _hip.ESTEP_GENERIC and G > 1:
             assert need, call
         if not want_resps and r != EINVAL:
             assert not need, call                       # the library needs none: ask for none
-        if image and lib.beer_frame_image_bytes(_hip.COV_CODE[cov], 300, D) > 0:
-            assert lib.beer_estep_route(IMAGE, _hip.F32, _hip.COV_CODE[cov], D, S, G, LN | SUM | LW,
-                                        nws) != EINVAL, call
+        if image and lib.beer_frame_image_bytes(c, 300, D) > 0:
+            assert lib.beer_estep_route(IMAGE, _hip.F32, c, D, S, G, LN | SUM | LW, nws) != EINVAL, call
         assert not (image and (need or arith != 'x'))
 
 

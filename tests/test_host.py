@@ -441,6 +441,29 @@ def test_frames_workspace_of_the_diagonal_accumulation_is_bounded():
     assert q(F32, FULL, 1_000_000, 40, 256, 1) == base(F32, FULL, 40, 256, 1)
 
 
+def test_scratch_buffers_grow_and_are_filed_per_stream(monkeypatch):
+    '''`_hip.scratch`: nothing for 0 bytes; the same key never gives a smaller buffer than it gave
+    before (a smaller request reuses it, a larger one replaces it); another stream, another buffer.'''
+    stream = [1]
+    monkeypatch.setattr(_hip, 'stream_id', lambda: stream[0])
+    monkeypatch.setattr(_hip, '_workspaces', {})
+    cpu = torch.device('cpu')
+    assert _hip.scratch(('k', 1), 0, cpu) == (None, 0)
+    a, n = _hip.scratch(('k', 1), 100, cpu)
+    assert n == 100 and a.numel() == 100 and a.dtype == torch.uint8
+    b, n = _hip.scratch(('k', 1), 40, cpu)
+    assert b is a and n == 40
+    c, n = _hip.scratch(('k', 1), 300, cpu)
+    assert n == 300 and c.numel() == 300 and _hip.scratch(('k', 1), 100, cpu)[0] is c
+    assert _hip.scratch(('k', 2), 100, cpu)[0] is not c
+    stream[0] = 2
+    d, _ = _hip.scratch(('k', 1), 100, cpu)
+    assert d is not c and d.numel() == 100
+    stream[0] = 1
+    assert _hip.scratch(('k', 1), 300, cpu)[0] is c
+    assert len(_hip._workspaces) == 3
+
+
 def test_cli_model_builders_on_the_recipe_configuration():
     """`beer hmm mkphones / mkphoneloopgraph / mkdecodegraph` as builders (beer_amd/cli/hmm.py) on
     the configuration of recipes/aud/conf/hmm.yml (benchlib/recipe.py): unit graphs, pdf ids running
