@@ -174,6 +174,27 @@ def estep_route(entry, dtype_code_, cov, D, S, G, args, workspace_bytes):
     return lib().beer_estep_route(entry, dtype_code_, cov, D, S, G, args, workspace_bytes)
 
 
+# BEER_ACC_* of include/beer_hip.h: what `beer_accumulate_route` takes and returns
+ACC_PLAIN, ACC_PACKED, ACC_FUSED = 0, 1, 2
+ARG_STATE_RESPS, ARG_IMAGE = 128, 256
+ACC_GENERIC, ACC_EXACT_F32, ACC_EXACT_F64, ACC_DIAG, ACC_ACCX, ACC_ACCF = \
+    0x10000000, 0x20000000, 0x30000000, 0x40000000, 0x50000000, 0x60000000
+ACC_SR = 0x100
+ACC_D_PARTIAL = 0x200
+ACC_X_SX, ACC_X_XT_REUSED = 0x200, 0x400
+ACC_F_BLK, ACC_F_IMAGE = 0x200, 0x400
+
+
+def accumulate_family(route):
+    'BEER_ACC_FAMILY: the kernel family of a `beer_accumulate_route` value.'
+    return route & 0x70000000
+
+
+def accumulate_route(entry, dtype_code_, cov, T, D, S, G, args, workspace_bytes):
+    '`beer_accumulate_route`: the kernel family and launch form an accumulation picks (host only).'
+    return lib().beer_accumulate_route(entry, dtype_code_, cov, T, D, S, G, args, workspace_bytes)
+
+
 BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
 BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
 
@@ -240,6 +261,7 @@ SIGNATURES = {
     'beer_mixtureset_lognorm_image': [c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                       c_z, c_p],
     'beer_estep_route': [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_uint, c_z],  # (host only: no stream)
+    'beer_accumulate_route': [c_i, c_i, c_i, c_l, c_i, c_i, c_i, ctypes.c_uint, c_z],
     'beer_pack_resps': [c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_weights_from_acc': [c_i, c_i, c_i, c_p, c_p, c_p],
     'beer_tied_lognorm': [c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],

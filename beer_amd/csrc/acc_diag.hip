@@ -259,25 +259,35 @@ __global__ __launch_bounds__(256) void accd_reduce_kernel(int cov, int D, int K,
 inline int ad_kp(int K) { return K > 64 ? (K + 127) / 128 * 128 : 64; }
 inline int64_t ad_chains(int64_t T_) { return (T_ + kAdChain - 1) / kAdChain; }
 
-template <int NJ2>
-int launch_accd(int cov, int64_t T_, int D, int K, const float* X, const float* W, double* acc,
-                float* part, float* cpart, hipStream_t s) {
-    const unsigned gx = (unsigned)ad_chains(T_);
-    if (K > 64)
-        hipLaunchKernelGGL((accd_kernel<NJ2, 2>), dim3(gx, (K + 127) / 128), dim3(256), 0, s, cov,
-                           T_, D, K, X, W, acc, part, cpart);
-    else
-        hipLaunchKernelGGL((accd_kernel<NJ2, 1>), dim3(gx, 1), dim3(256), 0, s, cov, T_, D, K, X, W,
-                           acc, part, cpart);
+struct AccdArgs {                   // of accd_kernel and accd_reduce_kernel
+    int cov;
+    int64_t T;
+    int D, K;
+    const float *X, *W;
+    double* acc;
+    float *part, *cpart;            // null: fp64 atomics straight into `acc`
+    hipStream_t s;
+};
+
+template <int NJ2, int NC>
+int launch_accd(const AccdArgs& a) {
+    const unsigned gx = (unsigned)ad_chains(a.T);
+    hipLaunchKernelGGL((accd_kernel<NJ2, NC>), dim3(gx, NC == 2 ? (a.K + 127) / 128 : 1), dim3(256),
+                       0, a.s, a.cov, a.T, a.D, a.K, a.X, a.W, a.acc, a.part, a.cpart);
     BEER_LAUNCH_CHECK();
-    if (part) {
+    if (a.part) {
         const int DP = 16 * NJ2;
-        hipLaunchKernelGGL(accd_reduce_kernel, dim3((K * (2 * DP + 1) + 255) / 256, kAdSlices),
-                           dim3(256), 0, s, cov, D, K, DP, ad_kp(K), (int)gx, part, cpart, acc);
+        hipLaunchKernelGGL(accd_reduce_kernel, dim3((a.K * (2 * DP + 1) + 255) / 256, kAdSlices),
+                           dim3(256), 0, a.s, a.cov, a.D, a.K, DP, ad_kp(a.K), (int)gx, a.part,
+                           a.cpart, a.acc);
         BEER_LAUNCH_CHECK();
     }
     return BEER_OK;
 }
+// NJ2 tiles of 16 dimensions; wide: 128 components per workgroup (K > 64) instead of 64
+constexpr struct { int NJ2; int (*wide)(const AccdArgs&); int (*narrow)(const AccdArgs&); } kAccdRows[] = {
+    {1, launch_accd<1, 2>, launch_accd<1, 1>}, {2, launch_accd<2, 2>, launch_accd<2, 1>},
+    {3, launch_accd<3, 2>, launch_accd<3, 1>}, {4, launch_accd<4, 2>, launch_accd<4, 1>}};
 
 }  // namespace
 
@@ -290,31 +300,48 @@ bool supported_acc_diag(int cov, int64_t T_, int D, int K) {
 }
 
 // partial sums of every chain of frames: [chains][KP][2 DP] + [chains][KP] floats
-size_t acc_diag_workspace_bytes(int cov, int64_t T_, int D, int K) {
-    if (!supported_acc_diag(cov, T_, D, K)) return 0;
+AccdLayout accd_layout(int cov, int64_t T_, int D, int K) {
+    AccdLayout l = {};
+    if (!supported_acc_diag(cov, T_, D, K)) return l;
     const int DP = (D + 15) / 16 * 16;
-    const size_t bytes = (size_t)ad_chains(T_) * ad_kp(K) * (2 * DP + 1) * sizeof(float) + 256;
+    const size_t rows = (size_t)ad_chains(T_) * ad_kp(K) * sizeof(float);
     // (many components x many frames: the partial sums would outgrow what they save -- 32 MB
     // at config 4 -- and the call flushes with atomics instead)
-    return bytes <= kAdMaxPartialBytes ? bytes : 0;
+    if (rows * (2 * DP + 1) + 256 > kAdMaxPartialBytes) return l;
+    l.cpart = rows * 2 * DP;
+    l.bytes = rows * (2 * DP + 1) + 256;
+    return l;
+}
+size_t acc_diag_workspace_bytes(int cov, int64_t T_, int D, int K) {
+    return accd_layout(cov, T_, D, K).bytes;
+}
+
+AccdForm accd_form(int cov, int64_t T_, int D, int K, size_t ws_bytes) {
+    AccdForm f = {};
+    f.rc = BEER_EINVAL;
+    if (!supported_acc_diag(cov, T_, D, K)) return f;
+    f.NJ2 = (D + 15) / 16;
+    f.NC = K > 64 ? 2 : 1;
+    // (without the scratch: fp64 atomics straight into `acc` -- same sums, a third slower)
+    const size_t need = accd_layout(cov, T_, D, K).bytes;
+    f.partial = need && ws_bytes >= need && ad_chains(T_) > 1;
+    f.rc = BEER_OK;
+    return f;
 }
 
 int acc_diag_bf16x3(int cov, int64_t T_, int D, int K, const float* X, const float* W, double* acc,
                     void* ws, size_t ws_bytes, hipStream_t s) {
-    float *part = nullptr, *cpart = nullptr;
-    const size_t need = acc_diag_workspace_bytes(cov, T_, D, K);
-    // (without the scratch: fp64 atomics straight into `acc` -- same sums, a third slower)
-    if (ws && need && ws_bytes >= need && ad_chains(T_) > 1) {
-        const int DP = (D + 15) / 16 * 16;
-        part = reinterpret_cast<float*>(ws);
-        cpart = part + (size_t)ad_chains(T_) * ad_kp(K) * 2 * DP;
+    const AccdForm f = accd_form(cov, T_, D, K, ws ? ws_bytes : 0);
+    if (f.rc != BEER_OK) return f.rc;
+    AccdArgs a = {cov, T_, D, K, X, W, acc, nullptr, nullptr, s};
+    if (f.partial) {
+        const AccdLayout l = accd_layout(cov, T_, D, K);
+        a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + l.part);
+        a.cpart = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + l.cpart);
     }
-    switch ((D + 15) / 16) {
-        case 1: return launch_accd<1>(cov, T_, D, K, X, W, acc, part, cpart, s);
-        case 2: return launch_accd<2>(cov, T_, D, K, X, W, acc, part, cpart, s);
-        case 3: return launch_accd<3>(cov, T_, D, K, X, W, acc, part, cpart, s);
-        default: return launch_accd<4>(cov, T_, D, K, X, W, acc, part, cpart, s);
-    }
+    for (const auto& r : kAccdRows)
+        if (r.NJ2 == f.NJ2) return (f.NC == 2 ? r.wide : r.narrow)(a);
+    return BEER_EINVAL;
 }
 
 }  // namespace beer_mfma

@@ -431,46 +431,61 @@ int acc_launch(int64_t nframes, int D, int S, int G, const void* X, const void* 
     if (gz > max_z) gz = max_z;
     if (gz < 1) gz = 1;
     if (gz > 65535) gz = 65535;
-    int64_t fpb = (nframes + gz - 1) / gz;
-    fpb = (fpb + kAccTile - 1) / kAccTile * kAccTile;
-    gz = (nframes + fpb - 1) / fpb;
+    const beer_mfma::FrameSplit z = beer_mfma::frame_split(nframes, gz, kAccTile);
     const size_t lds = ((size_t)kAccTile * D + (size_t)kAccTile * kAccKB) * sizeof(T);
-    hipLaunchKernelGGL((accumulate_kernel<T, COV>), dim3(gx, gy, (unsigned)gz), dim3(kAccThreads),
-                       lds, s, nframes, D, S, G, (const T*)X, (const T*)cr, (const T*)sr, fpb, acc);
+    hipLaunchKernelGGL((accumulate_kernel<T, COV>), dim3(gx, gy, (unsigned)z.gz), dim3(kAccThreads),
+                       lds, s, nframes, D, S, G, (const T*)X, (const T*)cr, (const T*)sr, z.fpb, acc);
     BEER_LAUNCH_CHECK();
     return BEER_OK;
 }
 
-template <typename T>
-int accumulate_launch(int cov, int64_t nframes, int D, int S, int G, const void* X,
-                      const void* cr, const void* sr, double* acc, void* ws, size_t ws_bytes,
-                      void* stream, bool exact) {
-    BEER_REQUIRE(nframes >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(X && acc);
-    if (nframes == 0) return BEER_OK;
-    hipStream_t s = as_stream(stream);
+// What beer_normal_accumulate does with a call, in this order of precedence.
+struct AccPlan {
+    int rc;                 // BEER_EINVAL: the entry point refuses the call
+    bool diag;              // acc_diag.hip: the float32 weights split inside the kernel
+    bool exact_mfma;        // the exact fp32 / fp64 MFMA kernel (estep_mfma.hip)
+};                          // neither: accumulate_kernel above
+
+AccPlan accumulate_plan(size_t elem, bool exact, int cov, int64_t nframes, int D, int S, int G,
+                        bool cr, bool sr, bool ws, size_t ws_bytes) {
+    AccPlan p = {};
+    p.rc = BEER_EINVAL;
+    if (!(nframes >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2)) return p;
+    p.rc = BEER_OK;
     // (float32 responsibilities [T, K] in memory: the exact fp32 / fp64 MFMA kernels;
     // the bf16x3 accumulation takes packed tiles -- beer_pack_resps +
     // beer_normal_accumulate_packed -- whose size depends on T)
     // ... except diagonal / isotropic Gaussians without state posteriors (a set of single
     // Gaussians under an HMM: the prior of a VAE): few statistics per Gaussian, the float32
     // weights are split inside the kernel (acc_diag.hip)
-    if (sizeof(T) == 4 && !exact && cr && !sr &&
-        beer_mfma::supported_acc_diag(cov, nframes, D, S * G))
+    p.diag = elem == 4 && !exact && cr && !sr &&
+             beer_mfma::supported_acc_diag(cov, nframes, D, S * G);
+    p.exact_mfma = !p.diag && cr && ws && beer_mfma::supported_acc(D, S * G, elem) &&
+                   ws_bytes >= beer_mfma::acc_workspace_bytes(cov, D, S * G, elem);
+    return p;
+}
+
+template <typename T>
+int accumulate_launch(int cov, int64_t nframes, int D, int S, int G, const void* X,
+                      const void* cr, const void* sr, double* acc, void* ws, size_t ws_bytes,
+                      void* stream, bool exact) {
+    const AccPlan p = accumulate_plan(sizeof(T), exact, cov, nframes, D, S, G, cr, sr, ws, ws_bytes);
+    BEER_REQUIRE(p.rc == BEER_OK && X && acc);
+    if (nframes == 0) return BEER_OK;
+    hipStream_t s = as_stream(stream);
+    if (p.diag)
         return beer_mfma::acc_diag_bf16x3(cov, nframes, D, S * G, (const float*)X,
                                           (const float*)cr, acc, ws, ws_bytes, s);
-    if (cr && ws && beer_mfma::supported_acc(D, S * G, sizeof(T)) &&
-        ws_bytes >= beer_mfma::acc_workspace_bytes(cov, D, S * G, sizeof(T))) {
+    if (p.exact_mfma)
         return sizeof(T) == 4
                    ? beer_mfma::acc_f32(cov, nframes, D, S, G, (const float*)X, (const float*)cr,
                                         (const float*)sr, acc, ws, ws_bytes, s)
                    : beer_mfma::acc_f64(cov, nframes, D, S, G, (const double*)X,
                                         (const double*)cr, (const double*)sr, acc, ws, ws_bytes,
                                         s);
-    }
-    if (cov == BEER_FULL) return acc_launch<T, BEER_FULL>(nframes, D, S, G, X, cr, sr, acc, s);
-    if (cov == BEER_DIAG) return acc_launch<T, BEER_DIAG>(nframes, D, S, G, X, cr, sr, acc, s);
-    return acc_launch<T, BEER_ISO>(nframes, D, S, G, X, cr, sr, acc, s);
+    constexpr decltype(&acc_launch<T, BEER_FULL>) generic[] = {
+        acc_launch<T, BEER_FULL>, acc_launch<T, BEER_DIAG>, acc_launch<T, BEER_ISO>};
+    return generic[cov](nframes, D, S, G, X, cr, sr, acc, s);
 }
 
 template <typename T>
@@ -513,6 +528,25 @@ int estepx_entry(int entry, bool set, int cov, int64_t T, int D, int S, int G, c
     return beer_mfma::estep_bf16x3(cov, T, D, S, G, X, exp_stats, logw, (float*)resps, log_norm,
                                    llh_sum, ws, ws_bytes, as_stream(stream),
                                    entry == BEER_ESTEP_PACKED, image);
+}
+
+// What the packed accumulation entry points (one mixture of G components, or a `set`) and the
+// fused one refuse, from the shape and the workspace (0 bytes: none): they call it with what
+// they were handed, beer_accumulate_route with its arguments.
+int accx_refusal(bool set, int cov, int64_t T, int D, int S, int G, size_t ws_bytes) {
+    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
+    BEER_REQUIRE(!set || beer_mixtureset_packed_supported(cov, D, S, G));
+    BEER_REQUIRE(beer_mfma::accx_form(cov, D, S * G, S, G, set).rc == BEER_OK);
+    const size_t need = beer_mfma::accx_layout(cov, T, D, S * G, S, G, set).bytes;
+    BEER_REQUIRE(need > 0 && ws_bytes >= need);
+    return BEER_OK;
+}
+int accf_refusal(int cov, int64_t T, int D, int S, int G, size_t ws_bytes) {
+    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
+    BEER_REQUIRE(beer_mfma::accf_form(cov, D, S, G, false).rc == BEER_OK);
+    const size_t need = beer_mfma::accf_layout(cov, D, S, G).bytes;
+    BEER_REQUIRE(need > 0 && ws_bytes >= need);
+    return BEER_OK;
 }
 
 }  // namespace
@@ -603,6 +637,52 @@ int beer_normal_accumulate(int dtype, int cov, int64_t T, int D, int S, int G, c
                   state_resps, acc, workspace, workspace_bytes, stream, exact);
 }
 
+int beer_accumulate_route(int entry, int dtype, int cov, int64_t T, int D, int S, int G,
+                          unsigned args, size_t workspace_bytes) {
+    const bool exact = (dtype & BEER_EXACT) != 0;
+    dtype &= ~BEER_EXACT;
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    const bool sets = args & BEER_ARG_STATE_RESPS;
+    if (entry == BEER_ACC_PLAIN) {
+        const size_t elem = dtype == BEER_F64 ? 8 : 4;
+        const AccPlan p = accumulate_plan(elem, exact, cov, T, D, S, G, args & BEER_ARG_RESPS, sets,
+                                          workspace_bytes > 0, workspace_bytes);
+        if (p.rc != BEER_OK) return p.rc;
+        if (p.diag) {
+            const beer_mfma::AccdForm f = beer_mfma::accd_form(cov, T, D, S * G, workspace_bytes);
+            return f.rc != BEER_OK ? f.rc
+                                   : BEER_ACC_DIAG | f.NJ2 | f.NC << 4 |
+                                         (f.partial ? BEER_ACC_D_PARTIAL : 0);
+        }
+        if (p.exact_mfma) {
+            const beer_mfma::AccForm f = beer_mfma::acc_form(elem, cov, D, S * G, sets);
+            return f.rc != BEER_OK ? f.rc
+                                   : (elem == 8 ? BEER_ACC_EXACT_F64 : BEER_ACC_EXACT_F32) | f.NQ |
+                                         (f.has_sr ? BEER_ACC_SR : 0);
+        }
+        return BEER_ACC_GENERIC;
+    }
+    // the float32 entry points of the bf16x3 kernels
+    BEER_REQUIRE(dtype == BEER_F32 && !exact);
+    if (entry == BEER_ACC_PACKED) {
+        // beer_normal_accumulate_packed (K = S G), beer_mixtureset_accumulate_packed with
+        // state posteriors; both need the packed tiles
+        BEER_REQUIRE(args & BEER_ARG_RESPS);
+        BEER_REQUIRE(accx_refusal(sets, cov, T, D, S, G, workspace_bytes) == BEER_OK);
+        const beer_mfma::AccxForm f = beer_mfma::accx_form(cov, D, S * G, S, G, sets);
+        return BEER_ACC_ACCX | f.NQ | (f.sr ? BEER_ACC_SR : 0) | (f.sx ? BEER_ACC_X_SX : 0) |
+               (f.xt_reused ? BEER_ACC_X_XT_REUSED : 0);
+    }
+    if (entry == BEER_ACC_FUSED) {
+        BEER_REQUIRE(accf_refusal(cov, T, D, S, G, workspace_bytes) == BEER_OK);
+        const beer_mfma::AccfForm f = beer_mfma::accf_form(cov, D, S, G, args & BEER_ARG_IMAGE);
+        if (f.use_image)
+            return BEER_ACC_ACCF | BEER_ACC_F_IMAGE | f.NKU << 4 | f.ns_img << 16 | f.waves << 21;
+        return BEER_ACC_ACCF | f.NQT | (f.blk ? BEER_ACC_F_BLK : 0) | f.waves << 21;
+    }
+    return BEER_EINVAL;
+}
+
 int beer_mixture_estep_packed(int cov, int64_t T, int D, int K, const float* X,
                               const float* exp_stats, const float* log_weights, float* log_norm,
                               void* packed_resps, double* llh_sum, void* workspace,
@@ -615,10 +695,8 @@ int beer_mixture_estep_packed(int cov, int64_t T, int D, int K, const float* X,
 int beer_normal_accumulate_packed(int cov, int64_t T, int D, int K, const float* X,
                                   const void* packed_resps, double* acc, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && K >= 1 && cov >= 0 && cov <= 2);
     BEER_REQUIRE(X && packed_resps && acc && workspace);
-    BEER_REQUIRE(beer_mfma::supported_acc_x(D, K));
-    BEER_REQUIRE(workspace_bytes >= beer_mfma::accx_workspace_bytes(cov, T, D, K));
+    BEER_REQUIRE(accx_refusal(false, cov, T, D, 1, K, workspace_bytes) == BEER_OK);
     if (T == 0) return BEER_OK;
     return beer_mfma::acc_bf16x3_packed(cov, T, D, K, X, packed_resps, acc, workspace,
                                         workspace_bytes, as_stream(stream));
@@ -648,10 +726,8 @@ int beer_mixtureset_accumulate_packed(int cov, int64_t T, int D, int S, int G, c
                                       const void* packed_resps, const float* state_resps,
                                       double* acc, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
     BEER_REQUIRE(X && packed_resps && state_resps && acc && workspace);
-    BEER_REQUIRE(beer_mixtureset_packed_supported(cov, D, S, G));
-    BEER_REQUIRE(workspace_bytes >= beer_mfma::accxs_workspace_bytes(cov, T, D, S, G));
+    BEER_REQUIRE(accx_refusal(true, cov, T, D, S, G, workspace_bytes) == BEER_OK);
     if (T == 0) return BEER_OK;
     return beer_mfma::acc_bf16x3_packed(cov, T, D, S * G, X, packed_resps, acc, workspace,
                                         workspace_bytes, as_stream(stream), S, G, state_resps);
@@ -690,9 +766,7 @@ int beer_mixtureset_accumulate_fused(int cov, int64_t T, int D, int S, int G, co
                                      const float* log_norm, const float* state_resps,
                                      const void* frame_image, double* acc, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    BEER_REQUIRE(T >= 0 && D >= 1 && S >= 1 && G >= 1 && cov >= 0 && cov <= 2);
-    BEER_REQUIRE(beer_mfma::supported_accf(cov, D, S, G));
-    BEER_REQUIRE(workspace && workspace_bytes >= beer_mfma::accf_workspace_bytes(cov, D, S, G));
+    BEER_REQUIRE(accf_refusal(cov, T, D, S, G, workspace ? workspace_bytes : 0) == BEER_OK);
     if (T == 0) return BEER_OK;
     BEER_REQUIRE(X && exp_stats && log_norm && acc);
     return beer_mfma::acc_fused_bf16x3(cov, T, D, S, G, X, exp_stats, log_weights, log_norm,

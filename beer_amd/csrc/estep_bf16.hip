@@ -2163,6 +2163,16 @@ inline size_t p_image_bytes(int nchunks, int nk, int NT) {
     return up256(((size_t)nchunks * nk * NT + 4) * kBlockU4 * 16);
 }
 
+// [P image][slab table][c0 ...]: how the workspaces of the E-step and of the fused
+// accumulation begin
+struct PtabLayout {
+    size_t tab, c0;
+};
+inline PtabLayout ptab_layout(int nchunks, int nk, int NT) {
+    const size_t tab = p_image_bytes(nchunks, nk, NT);
+    return {tab, tab + up256((size_t)(nk + 1) * 8 * sizeof(int))};
+}
+
 }  // namespace
 
 #ifdef BEER_KERNEL_PROBE
@@ -2247,8 +2257,7 @@ size_t estepx_workspace_bytes(int cov, int D, int S, int G) {
     if (!supported_llh_padded(D, S, G)) return 0;
     if (S > 1) G = group_pad(G);
     const int K = S * G, NT = ntx_for(S, K), nchunks = nchunksx_for(S, K);
-    return p_image_bytes(nchunks, nk16_of(cov, D), NT) +
-           up256((size_t)(nk16_of(cov, D) + 1) * 8 * sizeof(int)) + 256;
+    return ptab_layout(nchunks, nk16_of(cov, D), NT).c0 + 256;
 }
 
 bool supported_frame_image(int cov, int D);
@@ -2432,13 +2441,10 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
     a.gl = f.gl, a.jw = f.jw, a.nchunks = f.nchunks, a.nk = nk;
     a.nku = (nslabx_of(cov, D) + 7) / 8;
     a.X = X, a.resps = resps, a.log_norm = log_norm, a.llh_sum = llh_sum, a.img = image, a.s = s;
-    char* w = reinterpret_cast<char*>(ws);
-    a.P = w;
-    w += p_image_bytes(f.nchunks, nk, f.NT);
-    int* tab = reinterpret_cast<int*>(w);
-    w += up256((size_t)(nk + 1) * 8 * sizeof(int));
-    float* c0 = reinterpret_cast<float*>(w);
-    a.tab = tab, a.c0 = c0;
+    const PtabLayout l = ptab_layout(f.nchunks, nk, f.NT);
+    int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + l.tab);
+    float* c0 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + l.c0);
+    a.P = ws, a.tab = tab, a.c0 = c0;
     if (f.xt) {
         a.xt_out = reinterpret_cast<float*>(reinterpret_cast<char*>(resps) +
                                             packed_tiles_bytes(nframes, a.K));
@@ -2460,18 +2466,7 @@ int estep_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X, 
     return BEER_EINVAL;
 }
 
-size_t accx_base_workspace_bytes(int cov, int D, int K) {
-    if (!supported_acc_x(D, K)) return 0;
-    const int nslab = nslabx_of(cov, D);
-    return up256((size_t)K * nslab * 4 * sizeof(double)) + up256((size_t)nslab * sizeof(int)) + 1024;
-}
-
-size_t accx_workspace_bytes(int cov, int64_t nframes, int D, int K) {
-    const size_t base = accx_base_workspace_bytes(cov, D, K);
-    if (base == 0) return 0;
-    const int64_t tiles = (nframes + kAxFT - 1) / kAxFT;
-    return base + (size_t)tiles * xt_pieces(D) * kPiece;
-}
+// ---- accumulation over packed tiles (accx_kernel) --------------------------------------------
 
 // ... with state posteriors multiplied in by the accumulation kernel: S states of G
 // components (a power of two, 8 .. 128)
@@ -2481,95 +2476,88 @@ bool supported_acc_sets(int cov, int D, int S, int G) {
 inline int acc_sets_spad(int S, int G) {
     return (S * G + kPackedComps - 1) / kPackedComps * (kPackedComps / G);
 }
-size_t accxs_workspace_bytes(int cov, int64_t nframes, int D, int S, int G) {
-    if (!supported_acc_sets(cov, D, S, G)) return 0;
+
+// [Sp: K x nq doubles][slab table][X^T image: a tile per 64 frames]; a set (K = S G) then has
+// [Gt: the state posteriors, transposed per tile] behind it
+AccxLayout accx_layout(int cov, int64_t nframes, int D, int K, int S, int G, bool sets) {
+    AccxLayout l = {};
+    if (!supported_acc_x(D, K) || (sets && !supported_acc_sets(cov, D, S, G))) return l;
+    const int nslab = nslabx_of(cov, D);
     const int64_t tiles = (nframes + kAxFT - 1) / kAxFT;
-    return up256(accx_workspace_bytes(cov, nframes, D, S * G)) +
-           (size_t)tiles * acc_sets_spad(S, G) * kAxFT * sizeof(float) + 1024;
+    l.tab = up256((size_t)K * nslab * 4 * sizeof(double));
+    l.Xt = l.tab + up256((size_t)nslab * sizeof(int)) + 1024;
+    l.bytes = l.Xt + (size_t)tiles * xt_pieces(D) * kPiece;
+    if (sets) {
+        l.Gt = up256(l.bytes);
+        l.bytes = l.Gt + (size_t)tiles * acc_sets_spad(S, G) * kAxFT * sizeof(float) + 1024;
+    }
+    return l;
+}
+size_t accx_workspace_bytes(int cov, int64_t nframes, int D, int K) {
+    return accx_layout(cov, nframes, D, K, 1, K, false).bytes;
+}
+size_t accxs_workspace_bytes(int cov, int64_t nframes, int D, int S, int G) {
+    return accx_layout(cov, nframes, D, S * G, S, G, true).bytes;
 }
 
-int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, const void* Rimg,
-                      double* acc, void* ws, size_t ws_bytes, hipStream_t s, int S, int G,
-                      const float* SR) {
-    if (!supported_acc_x(D, K) || ws_bytes < accx_workspace_bytes(cov, nframes, D, K))
-        return BEER_EINVAL;
-    if (SR && (S * G != K || !supported_acc_sets(cov, D, S, G) ||
-               ws_bytes < accxs_workspace_bytes(cov, nframes, D, S, G)))
-        return BEER_EINVAL;
-    const int nslab = nslabx_of(cov, D), nq = nslab * 4;
-    char* w = reinterpret_cast<char*>(ws);
-    double* Sp = reinterpret_cast<double*>(w);
-    w += up256((size_t)K * nq * sizeof(double));
-    int* tab = reinterpret_cast<int*>(w);
-    float* Xt = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) +
-                                         accx_base_workspace_bytes(cov, D, K));
-    hipError_t e = hipMemsetAsync(Sp, 0, (size_t)K * nq * sizeof(double), s);
-    if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(tabx_kernel, dim3(1), dim3(256), 0, s, cov, D, nslab, tab);
+AccxForm accx_form(int cov, int D, int K, int S, int G, bool sets) {
+    AccxForm f = {};
+    f.rc = BEER_EINVAL;
+    if (!supported_acc_x(D, K)) return f;
+    if (sets && (S * G != K || !supported_acc_sets(cov, D, S, G))) return f;
+    f.sr = sets;
+    if (sets)
+        while ((1 << f.lgG) < G) ++f.lgG;
+    f.nslab = nslabx_of(cov, D);
+    f.NX = xt_pieces(D);
+    const int ntiles = (f.nslab * 4 + 15) / 16;
+    f.NQ = accx_nq(ntiles);
+    f.gx = (ntiles + f.NQ * kAxWaves - 1) / (f.NQ * kAxWaves);
+    f.gy = (K + 16 * kAxMC - 1) / (16 * kAxMC);
+    // the E-step kernel left the X^T image behind the tiles (one mixture; the kernel of a set
+    // does not)
+    f.xt_reused = packed_has_xt(K) && !sets;
+    const size_t rbuf = 2 * (size_t)NP * kPackedPlaneWords * 4 + (sets ? 2 * 4096 : 0);
+    f.lds = 2 * (size_t)f.NX * kPiece + rbuf;
+    f.sx = f.lds > (size_t)beer::kMaxDynLds;                     // one X^T tile, two R buffers
+    if (f.sx) f.lds = (size_t)f.NX * kPiece + rbuf;
+    f.band = band_layout(cov, D);
+    f.rc = BEER_OK;
+    return f;
+}
+
+namespace {
+
+struct AccxArgs {                   // of accx_kernel
+    int64_t nframes, fpb;
+    int D, K, nslab, NX, gx, gy, gz, lgG, sx, band;
+    const float* Xt;
+    const unsigned* R;
+    const int* tab;
+    double* Sp;
+    const float* Gt;
+    dim3 grid;
+    size_t lds;
+    hipStream_t s;
+};
+
+template <bool SR, int NQ>
+int launch_accx(const AccxArgs& a) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accx_kernel<SR, NQ>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL((accx_kernel<SR, NQ>), a.grid, dim3(64 * kAxWaves), a.lds, a.s, a.nframes,
+                       a.D, a.K, a.nslab, a.NX, a.Xt, a.R, a.tab, a.fpb, a.Sp, a.gx, a.gy, a.gz,
+                       a.Gt, a.lgG, a.sx, a.band);
     BEER_LAUNCH_CHECK();
-    const int64_t tiles = (nframes + kAxFT - 1) / kAxFT;
-    const int NX = xt_pieces(D);
-    if (packed_has_xt(K) && !SR) {           // the E-step kernel left the image behind the tiles
-                                             // (one mixture; the kernel of a set does not)
-        Xt = reinterpret_cast<float*>(const_cast<char*>(reinterpret_cast<const char*>(Rimg)) +
-                                      packed_tiles_bytes(nframes, K));
-    } else {
-        hipLaunchKernelGGL(xt_image_kernel, dim3((unsigned)tiles), dim3(256), 0, s, nframes, D, NX,
-                           X, Xt);
-        BEER_LAUNCH_CHECK();
-    }
-    const int ntiles = (nq + 15) / 16;
-    float* Gt = nullptr;
-    int lgG = 0;
-    if (SR) {
-        Gt = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) +
-                                      up256(accx_workspace_bytes(cov, nframes, D, K)));
-        const int spad = acc_sets_spad(S, G);
-        hipLaunchKernelGGL(gt_image_kernel, dim3((unsigned)tiles, (unsigned)((spad + 63) / 64)),
-                           dim3(256), 0, s, nframes, S, spad, SR, Gt);
-        BEER_LAUNCH_CHECK();
-        while ((1 << lgG) < G) ++lgG;
-    }
-    const int NQ = accx_nq(ntiles);
-    const int gx = (ntiles + NQ * kAxWaves - 1) / (NQ * kAxWaves);
-    const int gy = (K + 16 * kAxMC - 1) / (16 * kAxMC);
-    // one workgroup per CU (120 KB of LDS, 512 registers per lane): whole rounds of 256
-    // workgroups, at most BEER_OPT_AX_MAXFRAMES frames each
-    const int chain = beer::option(BEER_OPT_AX_MAXFRAMES);
-    const int64_t max_z = (nframes + 511) / 512, min_z = (nframes + chain - 1) / chain;
-    const int64_t rounds = ((int64_t)gx * gy * min_z + 255) / 256;
-    int64_t gz = rounds * 256 / ((int64_t)gx * gy);
-    if (gz < min_z) gz = min_z;
-    if (gz > max_z) gz = max_z;
-    if (gz < 1) gz = 1;
-    int64_t fpb = (nframes + gz - 1) / gz;
-    fpb = (fpb + kAxFT - 1) / kAxFT * kAxFT;
-    gz = (nframes + fpb - 1) / fpb;
-    size_t lds = 2 * ((size_t)NX * kPiece + (size_t)NP * kPackedPlaneWords * 4) +
-                 (SR ? 2 * 4096 : 0);
-    const int sx = lds > (size_t)beer::kMaxDynLds ? 1 : 0;       // one X^T tile, two R buffers
-    if (sx) lds = (size_t)NX * kPiece + 2 * (size_t)NP * kPackedPlaneWords * 4 + (SR ? 2 * 4096 : 0);
-    const int64_t nyz = ((int64_t)gy * gz + 7) / 8 * 8;
-    const dim3 grid((unsigned)(nyz * gx));
-    const int band = band_layout(cov, D) ? 1 : 0;
-#define BEER_ACCX(SR_, NQ_)                                                                      \
-    do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accx_kernel<SR_, NQ_>),          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
-        hipLaunchKernelGGL((accx_kernel<SR_, NQ_>), grid, dim3(64 * kAxWaves), lds, s, nframes, \
-                           D, K, nslab, NX, Xt, reinterpret_cast<const unsigned*>(Rimg), tab,    \
-                           fpb, Sp, gx, gy, (int)gz, Gt, lgG, sx, band);                         \
-    } while (0)
-#define BEER_ACCX_NQ(SR_)                                                                        \
-    do {                                                                                         \
-        if (NQ == 6) BEER_ACCX(SR_, 6); else if (NQ == 7) BEER_ACCX(SR_, 7);                     \
-        else BEER_ACCX(SR_, 8);                                                                  \
-    } while (0)
-    if (SR) BEER_ACCX_NQ(true);
-    else BEER_ACCX_NQ(false);
-#undef BEER_ACCX_NQ
-#undef BEER_ACCX
-    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+constexpr struct { bool sr; int NQ; int (*launch)(const AccxArgs&); } kAccxRows[] = {
+    {true, 6, launch_accx<true, 6>},   {true, 7, launch_accx<true, 7>},
+    {true, 8, launch_accx<true, 8>},   {false, 6, launch_accx<false, 6>},
+    {false, 7, launch_accx<false, 7>}, {false, 8, launch_accx<false, 8>}};
+
+// Sp -> acc (+=), the epilogue of the packed and of the fused accumulation
+int unpackx(int cov, int D, int K, const double* Sp, double* acc, hipStream_t s) {
     const int64_t total = (int64_t)K * stats_dim(cov, D);
     hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
                        D, K, Sp, acc);
@@ -2577,21 +2565,70 @@ int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, co
     return BEER_OK;
 }
 
+}  // namespace
+
+int acc_bf16x3_packed(int cov, int64_t nframes, int D, int K, const float* X, const void* Rimg,
+                      double* acc, void* ws, size_t ws_bytes, hipStream_t s, int S, int G,
+                      const float* SR) {
+    const AccxForm f = accx_form(cov, D, K, S, G, SR != nullptr);
+    const AccxLayout l = accx_layout(cov, nframes, D, K, S, G, SR != nullptr);
+    if (f.rc != BEER_OK || ws_bytes < l.bytes) return BEER_EINVAL;
+    char* w = reinterpret_cast<char*>(ws);
+    double* Sp = reinterpret_cast<double*>(w + l.Sp);
+    int* tab = reinterpret_cast<int*>(w + l.tab);
+    hipError_t e = hipMemsetAsync(Sp, 0, (size_t)K * f.nslab * 4 * sizeof(double), s);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(tabx_kernel, dim3(1), dim3(256), 0, s, cov, D, f.nslab, tab);
+    BEER_LAUNCH_CHECK();
+    const int64_t tiles = (nframes + kAxFT - 1) / kAxFT;
+    const float* Xt;
+    if (f.xt_reused) {
+        Xt = reinterpret_cast<const float*>(reinterpret_cast<const char*>(Rimg) +
+                                            packed_tiles_bytes(nframes, K));
+    } else {
+        float* image = reinterpret_cast<float*>(w + l.Xt);
+        hipLaunchKernelGGL(xt_image_kernel, dim3((unsigned)tiles), dim3(256), 0, s, nframes, D, f.NX,
+                           X, image);
+        BEER_LAUNCH_CHECK();
+        Xt = image;
+    }
+    float* Gt = nullptr;
+    if (f.sr) {
+        Gt = reinterpret_cast<float*>(w + l.Gt);
+        const int spad = acc_sets_spad(S, G);
+        hipLaunchKernelGGL(gt_image_kernel, dim3((unsigned)tiles, (unsigned)((spad + 63) / 64)),
+                           dim3(256), 0, s, nframes, S, spad, SR, Gt);
+        BEER_LAUNCH_CHECK();
+    }
+    // one workgroup per CU (120 KB of LDS, 512 registers per lane): whole rounds of 256
+    // workgroups, at most BEER_OPT_AX_MAXFRAMES frames each
+    const int chain = beer::option(BEER_OPT_AX_MAXFRAMES);
+    const int64_t max_z = (nframes + 511) / 512, min_z = (nframes + chain - 1) / chain;
+    const int64_t rounds = ((int64_t)f.gx * f.gy * min_z + 255) / 256;
+    int64_t gz = rounds * 256 / ((int64_t)f.gx * f.gy);
+    if (gz < min_z) gz = min_z;
+    if (gz > max_z) gz = max_z;
+    if (gz < 1) gz = 1;
+    const FrameSplit z = frame_split(nframes, gz, kAxFT);
+    const int64_t nyz = ((int64_t)f.gy * z.gz + 7) / 8 * 8;
+    const AccxArgs a = {nframes, z.fpb, D, K, f.nslab, f.NX, f.gx, f.gy, (int)z.gz, f.lgG,
+                        f.sx ? 1 : 0, f.band ? 1 : 0, Xt, reinterpret_cast<const unsigned*>(Rimg),
+                        tab, Sp, Gt, dim3((unsigned)(nyz * f.gx)), f.lds, s};
+    for (const auto& r : kAccxRows)
+        if (r.sr == f.sr && r.NQ == f.NQ) {
+            const int rc = r.launch(a);
+            return rc != BEER_OK ? rc : unpackx(cov, D, K, Sp, acc, s);
+        }
+    return BEER_EINVAL;
+}
+
+// ---- fused accumulation (accf_kernel / accfi_kernel) -----------------------------------------
+
 // statistics per Gaussian small enough for a wave's register tile: diagonal and
 // isotropic covariances up to D = 64 (nq <= 160)
 bool supported_accf(int cov, int D, int S, int G) {
     return cov != BEER_FULL && D >= 1 && D <= 64 && S >= 1 && G >= 1 && G <= 256 &&
            nslab_of(cov, D) * 4 <= 160;
-}
-
-size_t accf_workspace_bytes(int cov, int D, int S, int G) {
-    if (!supported_accf(cov, D, S, G)) return 0;
-    const int Kreal = S * G;
-    G = accf_group_pad(S, G);
-    const int K = S * G, NTC = accf_ntc(cov, D), nk = nk16_of(cov, D);
-    const int nchunks = (K + 16 * NTC - 1) / (16 * NTC), nq = nslab_of(cov, D) * 4;
-    return p_image_bytes(nchunks, nk, NTC) + up256((size_t)(nk + 1) * 8 * sizeof(int)) + 1024 +
-           up256((size_t)Kreal * nq * sizeof(double));
 }
 
 // Frame fragment images (frame_image_kernel): diagonal / isotropic statistics of at most
@@ -2626,50 +2663,130 @@ int frame_image(int cov, int64_t nframes, int D, const float* X, void* image, hi
     return BEER_OK;
 }
 
+AccfForm accf_form(int cov, int D, int S, int G, bool have_image) {
+    AccfForm f = {};
+    f.rc = BEER_EINVAL;
+    if (!supported_accf(cov, D, S, G)) return f;
+    // component slots: groups padded to a multiple of 4 (one state per lane's 4
+    // components); the statistics image Sp stays in the components' own order
+    f.Gp = accf_group_pad(S, G);
+    f.NTC = accf_ntc(cov, D);
+    f.NQT = accf_nqt(cov, D);
+    f.XP = f.NQT == 6 ? 5 : 8;                  // D <= 40 <=> C4 <= 10 <=> nq <= 96
+    f.nchunks = (S * f.Gp + 16 * f.NTC - 1) / (16 * f.NTC);
+    // The states of every 64-component chunk fit a block of ns consecutive ones?
+    // (groups are padded to a multiple of 4: a lane's 4 components share their state)
+    auto reach = [&](int ns) {
+        for (int c = 0; c < f.nchunks; ++c) {
+            const int lo = c * 16 * f.NTC / f.Gp, hi = (c * 16 * f.NTC + 60) / f.Gp;
+            if ((hi < S ? hi : S - 1) - (lo < S ? lo : S - 1) > ns - 1) return false;
+        }
+        return true;
+    };
+    f.blk = S >= 4 && reach(4);
+    // ... over a frame image: a block of 4, or of 16 (groups of 4 .. 12 Gaussians)
+    f.ns_img = f.blk ? 4 : (reach(16) ? 16 : 0);
+    f.NKU = (nslab_of(cov, D) + 7) / 8;
+    f.use_image = have_image && f.ns_img && f.NTC == 4 && supported_frame_image(cov, D);
+    // waves per workgroup: 8 (two per SIMD) with 64-component chunks, 4 with 128
+    f.waves = f.use_image ? beer::option(BEER_OPT_ACCFI_WAVES)
+                          : ((f.NTC == 4 && f.NQT == 6) ? 8 : 4);
+    f.rc = BEER_OK;
+    return f;
+}
+
+// [P image | slab table | c0: the E-step's prefix][Sp: K x nq doubles]
+AccfLayout accf_layout(int cov, int D, int S, int G) {
+    AccfLayout l = {};
+    if (!supported_accf(cov, D, S, G)) return l;
+    const int NTC = accf_ntc(cov, D), nk = nk16_of(cov, D);
+    const int nchunks = (S * accf_group_pad(S, G) + 16 * NTC - 1) / (16 * NTC);
+    const PtabLayout p = ptab_layout(nchunks, nk, NTC);
+    l.tab = p.tab;
+    l.c0 = p.c0;
+    l.Sp = l.c0 + 1024;
+    l.bytes = l.Sp + up256((size_t)S * G * nslab_of(cov, D) * 4 * sizeof(double));
+    return l;
+}
+size_t accf_workspace_bytes(int cov, int D, int S, int G) { return accf_layout(cov, D, S, G).bytes; }
+
+namespace {
+
+struct AccfArgs {                   // of accf_kernel and accfi_kernel
+    int64_t nframes, fpb;
+    int D, K, S, G, Greal, nk, nslab;
+    const float* X;
+    const u4 *image, *P;
+    const int* tab;
+    const float *log_norm, *sr;
+    double* Sp;
+    const float* c0;
+    dim3 grid;
+    size_t lds;
+    hipStream_t s;
+};
+
+// every fragment that depends on the frames only comes from the caller's image
+template <int NKU, int W, int NS>
+int launch_accfi(const AccfArgs& a) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accfi_kernel<NKU, W, NS>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL((accfi_kernel<NKU, W, NS>), a.grid, dim3(64 * W), a.lds, a.s, a.nframes, a.K,
+                       a.S, a.G, a.Greal, a.nk, a.nslab, a.image, a.P, a.log_norm, a.sr, a.fpb, a.Sp,
+                       a.c0);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+template <int NQT, int W, bool BLK>
+int launch_accf(const AccfArgs& a) {
+    constexpr int XP = NQT == 6 ? 5 : 8;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accf_kernel<4, NQT, true, W, XP, BLK>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL((accf_kernel<4, NQT, true, W, XP, BLK>), a.grid, dim3(64 * W), a.lds, a.s,
+                       a.nframes, a.D, a.K, a.S, a.G, a.Greal, a.nk, a.nslab, a.X, a.P, a.tab,
+                       a.log_norm, a.sr, a.fpb, a.Sp, a.c0);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+constexpr struct AccfiRow { int NKU, W, NS; int (*launch)(const AccfArgs&); } kAccfiRows[] = {
+    {1, 8, 4, launch_accfi<1, 8, 4>},   {2, 8, 4, launch_accfi<2, 8, 4>},
+    {3, 8, 4, launch_accfi<3, 8, 4>},   {4, 8, 4, launch_accfi<4, 8, 4>},
+    {1, 8, 16, launch_accfi<1, 8, 16>}, {2, 8, 16, launch_accfi<2, 8, 16>},
+    {3, 8, 16, launch_accfi<3, 8, 16>}, {4, 8, 16, launch_accfi<4, 8, 16>},
+    {1, 4, 4, launch_accfi<1, 4, 4>},   {2, 4, 4, launch_accfi<2, 4, 4>},
+    {3, 4, 4, launch_accfi<3, 4, 4>},   {4, 4, 4, launch_accfi<4, 4, 4>},
+    {1, 4, 16, launch_accfi<1, 4, 16>}, {2, 4, 16, launch_accfi<2, 4, 16>},
+    {3, 4, 16, launch_accfi<3, 4, 16>}, {4, 4, 16, launch_accfi<4, 4, 16>}};
+constexpr struct { int NQT; bool blk; int (*launch)(const AccfArgs&); } kAccfRows[] = {
+    {6, true, launch_accf<6, 8, true>},   {6, false, launch_accf<6, 8, false>},
+    {9, true, launch_accf<9, 4, true>},   {9, false, launch_accf<9, 4, false>},
+    {10, true, launch_accf<10, 4, true>}, {10, false, launch_accf<10, 4, false>}};
+
+}  // namespace
+
 int acc_fused_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float* X,
                      const float* expT, const float* logw, const float* log_norm,
                      const float* sr, const void* image, double* acc, void* ws, size_t ws_bytes,
                      hipStream_t s) {
-    if (!supported_accf(cov, D, S, G) || ws_bytes < accf_workspace_bytes(cov, D, S, G))
-        return BEER_EINVAL;
-    // component slots: groups padded to a multiple of 4 (one state per lane's 4
-    // components); the statistics image Sp stays in the components' own order
-    const int Greal = G, Kreal = S * G;
-    G = accf_group_pad(S, G);
-    const int K = S * G, NTC = accf_ntc(cov, D), NQT = accf_nqt(cov, D), nk = nk16_of(cov, D);
-    const int nchunks = (K + 16 * NTC - 1) / (16 * NTC), kpad = nchunks * NTC * 16;
+    const AccfForm f = accf_form(cov, D, S, G, image != nullptr);
+    const AccfLayout l = accf_layout(cov, D, S, G);
+    if (f.rc != BEER_OK || ws_bytes < l.bytes) return BEER_EINVAL;
+    const int Kreal = S * G, K = S * f.Gp, NTC = f.NTC, nk = nk16_of(cov, D);
+    const int nchunks = f.nchunks, kpad = nchunks * NTC * 16;
     const int nslab = nslab_of(cov, D), nq = nslab * 4;
     char* w = reinterpret_cast<char*>(ws);
-    void* P = w;
-    w += p_image_bytes(nchunks, nk, NTC);
-    int* tab = reinterpret_cast<int*>(w);
-    w += up256((size_t)(nk + 1) * 8 * sizeof(int));
-    float* c0 = reinterpret_cast<float*>(w);
-    w += 1024;
-    double* Sp = reinterpret_cast<double*>(w);
+    void* P = w + l.P;
+    int* tab = reinterpret_cast<int*>(w + l.tab);
+    float* c0 = reinterpret_cast<float*>(w + l.c0);
+    double* Sp = reinterpret_cast<double*>(w + l.Sp);
     hipError_t e = hipMemsetAsync(Sp, 0, (size_t)Kreal * nq * sizeof(double), s);
     if (e != hipSuccess) return -(int)e;
     hipLaunchKernelGGL(const_max_kernel, dim3(1), dim3(256), 0, s, cov, D, Kreal, expT, logw, c0);
     hipLaunchKernelGGL(packx_kernel, dim3(kpad), dim3(256),
                        (size_t)stats_dim(cov, D) * sizeof(float), s, cov, D, Kreal, NTC, expT, logw,
-                       reinterpret_cast<unsigned short*>(P), tab, Greal, G, c0, 0);
+                       reinterpret_cast<unsigned short*>(P), tab, G, f.Gp, c0, 0);
     BEER_LAUNCH_CHECK();
-    // The states of every 64-component chunk fit a block of 4 consecutive ones?
-    // (groups are padded to a multiple of 4: a lane's 4 components share their state)
-    auto reach = [&](int ns) {
-        for (int c = 0; c < nchunks; ++c) {
-            const int lo = c * 16 * NTC / G, hi = (c * 16 * NTC + 60) / G;
-            if ((hi < S ? hi : S - 1) - (lo < S ? lo : S - 1) > ns - 1) return false;
-        }
-        return true;
-    };
-    const bool blk = S >= 4 && reach(4);
-    // ... over a frame image: a block of 4, or of 16 (groups of 4 .. 12 Gaussians)
-    const int ns_img = blk ? 4 : (reach(16) ? 16 : 0);
-    const int nk_used = (nslab + 7) / 8;
-    // waves per workgroup: 8 (two per SIMD) with 64-component chunks, 4 with 128
-    const bool use_image = image && ns_img && NTC == 4 && supported_frame_image(cov, D);
-    const int waves = use_image ? beer::option(BEER_OPT_ACCFI_WAVES) : ((NTC == 4 && NQT == 6) ? 8 : 4);
+    const int waves = f.waves;
     // frames per workgroup: <= kAfMaxFramesPerWave per wave, about one workgroup of
     // 8 waves (two of 4) per CU and round
     const int rounds = beer::option(BEER_OPT_ACCF_ROUNDS);
@@ -2684,64 +2801,30 @@ int acc_fused_bf16x3(int cov, int64_t nframes, int D, int S, int G, const float*
     if (gz > max_z) gz = max_z;
     if (gz < min_z) gz = min_z;
     if (gz < 1) gz = 1;
-    int64_t fpb = (nframes + gz - 1) / gz;
-    fpb = (fpb + 32 * waves - 1) / (32 * waves) * (32 * waves);
-    gz = (nframes + fpb - 1) / fpb;
-    const size_t lds = (size_t)nk_used * NTC * kBlockU4 * 16 + (size_t)(nk + 1) * 8 * sizeof(int) +
-                       (size_t)2 * NQT * 64 * sizeof(int) +
-                       (size_t)waves * (32 * ld16_of(D) + (D + 2) * kAfXS + (blk ? 256 : 0)) *
-                           sizeof(float);
-    const dim3 grid(xcd_grid(gz, nchunks, nchunks));
-    if (use_image) {
-        // every fragment that depends on the frames only comes from the caller's image
-        const size_t lds_i = (size_t)nk_used * NTC * kBlockU4 * 16 +
-                             (size_t)waves * 64 * ns_img * sizeof(float);
-        const size_t lds_red = (size_t)waves * 16 * 64 * sizeof(float);
-        const size_t lds_f = lds_i > lds_red ? lds_i : lds_red;
-#define BEER_ACCFI(NKU_, W_, NS_)                                                                \
-    do {                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(accfi_kernel<NKU_, W_, NS_>),    \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds); \
-        hipLaunchKernelGGL((accfi_kernel<NKU_, W_, NS_>), grid, dim3(64 * W_), lds_f, s, nframes, \
-                           K, S, G, Greal, nk, nslab, reinterpret_cast<const u4*>(image),        \
-                           reinterpret_cast<const u4*>(P), log_norm, sr, fpb, Sp, c0);           \
-    } while (0)
-#define BEER_ACCFI_K(W_, NS_)                                                                    \
-    do {                                                                                         \
-        if (nk_used == 1) BEER_ACCFI(1, W_, NS_); else if (nk_used == 2) BEER_ACCFI(2, W_, NS_); \
-        else if (nk_used == 3) BEER_ACCFI(3, W_, NS_); else BEER_ACCFI(4, W_, NS_);              \
-    } while (0)
-        if (waves == 8) { if (ns_img == 4) BEER_ACCFI_K(8, 4); else BEER_ACCFI_K(8, 16); }
-        else { if (ns_img == 4) BEER_ACCFI_K(4, 4); else BEER_ACCFI_K(4, 16); }
-#undef BEER_ACCFI_K
-#undef BEER_ACCFI
-        BEER_LAUNCH_CHECK();
-        const int64_t total_i = (int64_t)Kreal * stats_dim(cov, D);
-        hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total_i + 255) / 256)), dim3(256), 0, s,
-                           cov, D, Kreal, Sp, acc);
-        BEER_LAUNCH_CHECK();
-        return BEER_OK;
+    const FrameSplit z = frame_split(nframes, gz, 32 * waves);
+    const size_t lds_p = (size_t)f.NKU * NTC * kBlockU4 * 16;         // the chunk's parameters
+    AccfArgs a = {nframes, z.fpb, D, K, S, f.Gp, G, nk, nslab, X,
+                  reinterpret_cast<const u4*>(image), reinterpret_cast<const u4*>(P), tab, log_norm,
+                  sr, Sp, c0, dim3(xcd_grid(z.gz, nchunks, nchunks)), 0, s};
+    int rc = BEER_EINVAL;
+    // (both kernels add their waves' sums up through the start of the LDS at the end: at
+    // D <= 2 that region is larger than everything the main loop keeps there)
+    const size_t lds_red = (size_t)waves * 16 * 64 * sizeof(float);
+    if (f.use_image) {
+        const size_t lds_i = lds_p + (size_t)waves * 64 * f.ns_img * sizeof(float);
+        a.lds = lds_i > lds_red ? lds_i : lds_red;
+        for (const AccfiRow& r : kAccfiRows)
+            if (r.NKU == f.NKU && r.W == (waves == 8 ? 8 : 4) && r.NS == (f.ns_img == 4 ? 4 : 16))
+                rc = r.launch(a);
+    } else {
+        a.lds = lds_p + (size_t)(nk + 1) * 8 * sizeof(int) + (size_t)2 * f.NQT * 64 * sizeof(int) +
+                (size_t)waves * (32 * ld16_of(D) + (D + 2) * kAfXS + (f.blk ? 256 : 0)) *
+                    sizeof(float);
+        if (a.lds < lds_red) a.lds = lds_red;
+        for (const auto& r : kAccfRows)
+            if (r.NQT == f.NQT && r.blk == f.blk) rc = r.launch(a);
     }
-#define BEER_ACCF(NTC_, NQT_, W_, BLK_)                                                          \
-    do {                                                                                         \
-        constexpr int XP_ = NQT_ == 6 ? 5 : 8;      /* D <= 40 <=> C4 <= 10 <=> nq <= 96 */       \
-        (void)hipFuncSetAttribute(                                                               \
-            reinterpret_cast<const void*>(accf_kernel<NTC_, NQT_, true, W_, XP_, BLK_>),         \
-            hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);                               \
-        hipLaunchKernelGGL((accf_kernel<NTC_, NQT_, true, W_, XP_, BLK_>), grid, dim3(64 * W_),  \
-                           lds, s, nframes, D, K, S, G, Greal, nk, nslab, X,                     \
-                           reinterpret_cast<const u4*>(P), tab, log_norm, sr, fpb, Sp, c0);      \
-    } while (0)
-    if (NQT == 6) { if (blk) BEER_ACCF(4, 6, 8, true); else BEER_ACCF(4, 6, 8, false); }
-    else if (NQT == 9) { if (blk) BEER_ACCF(4, 9, 4, true); else BEER_ACCF(4, 9, 4, false); }
-    else { if (blk) BEER_ACCF(4, 10, 4, true); else BEER_ACCF(4, 10, 4, false); }
-#undef BEER_ACCF
-    BEER_LAUNCH_CHECK();
-    const int64_t total = (int64_t)Kreal * stats_dim(cov, D);
-    hipLaunchKernelGGL(unpackx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
-                       D, Kreal, Sp, acc);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return rc != BEER_OK ? rc : unpackx(cov, D, Kreal, Sp, acc, s);
 }
 
 #endif  // BEER_KERNEL_PROBE

@@ -24,6 +24,18 @@ bool supported_acc_x(int D, int K);
 size_t estep_workspace_bytes(size_t elem, int cov, int D, int S, int G);
 size_t acc_workspace_bytes(int cov, int D, int K, size_t elem = 4);
 
+// The frames of a launch over gz workgroups (or rows of workgroups): whole tiles per
+// workgroup, and no workgroup without frames.  Every accumulation launcher ends its own
+// choice of gz with this.
+struct FrameSplit {
+    int64_t gz, fpb;
+};
+inline FrameSplit frame_split(int64_t nframes, int64_t gz, int tile) {
+    int64_t fpb = (nframes + gz - 1) / gz;
+    fpb = (fpb + tile - 1) / tile * tile;
+    return {(nframes + fpb - 1) / fpb, fpb};
+}
+
 // fp32 models on the bf16 matrix pipes (estep_bf16.hip): every fp32 operand is held
 // exactly as three bf16 pieces, the six leading partial products of every
 // multiplication, fp32 accumulation.
@@ -57,6 +69,66 @@ struct LlhxForm {                    // llhx_kernel / lnfi_kernel of estep_bf16.
 };
 LlhxForm llhx_form(int cov, int D, int S, int G, bool resps, bool packed, bool image,
                    size_t ws_bytes);
+
+// The launch forms of the accumulation families, decided on the host like the E-step's: the
+// launchers dispatch on them, beer_accumulate_route (estep.hip) reports them.  rc is
+// BEER_EINVAL where the launcher refuses the shape.  The *_layout functions give the byte
+// offsets of the pieces of a family's workspace and their total (0: shape not supported):
+// the size queries return `bytes`, the launchers take their pointers from the same offsets.
+struct AccForm {                     // acc_kernel<T, NQ, HAS_SR> of estep_mfma.hip
+    int rc;
+    int NQ;                          // statistic tiles per wave: 1 / 2 / 4
+    bool has_sr;
+    int gx, gy;
+};
+AccForm acc_form(size_t elem, int cov, int D, int K, bool has_sr);
+struct AccLayout {
+    size_t Sp, tab, bytes;
+};
+AccLayout acc_layout(size_t elem, int cov, int D, int K);
+
+struct AccxForm {                    // accx_kernel<SR, NQ> of estep_bf16.hip
+    int rc;
+    int NQ;                          // statistic tiles per wave: 6 / 7 / 8
+    bool sr;                         // state posteriors multiplied in (`sets`)
+    int lgG;
+    bool sx;                         // D > 118 (sets: > 103): one X^T tile in LDS, not two
+    bool band;
+    bool xt_reused;                  // 129 .. 256 components of one mixture: X^T behind the tiles
+    int nslab, NX, gx, gy;
+    size_t lds;
+};
+AccxForm accx_form(int cov, int D, int K, int S, int G, bool sets);
+struct AccxLayout {
+    size_t Sp, tab, Xt, Gt, bytes;
+};
+AccxLayout accx_layout(int cov, int64_t T, int D, int K, int S, int G, bool sets);
+
+struct AccfForm {                    // accf_kernel / accfi_kernel of estep_bf16.hip
+    int rc;
+    int Gp;                          // slots per group (a multiple of 4)
+    int NTC, NQT, XP, nchunks;
+    bool blk;                        // the states of every chunk: 4 consecutive ones
+    int ns_img;                      // ... over a frame image: 4, 16, or 0 (no image kernel)
+    bool use_image;                  // accfi_kernel<NKU, waves, ns_img>
+    int waves, NKU;
+};
+AccfForm accf_form(int cov, int D, int S, int G, bool have_image);
+struct AccfLayout {
+    size_t P, tab, c0, Sp, bytes;
+};
+AccfLayout accf_layout(int cov, int D, int S, int G);
+
+struct AccdForm {                    // accd_kernel<NJ2, NC> of acc_diag.hip
+    int rc;
+    int NJ2, NC;
+    bool partial;                    // partial sums per chain + accd_reduce_kernel; else fp64 atomics
+};
+AccdForm accd_form(int cov, int64_t T, int D, int K, size_t ws_bytes);
+struct AccdLayout {
+    size_t part, cpart, bytes;
+};
+AccdLayout accd_layout(int cov, int64_t T, int D, int K);
 
 int unpack_resps(int64_t T, int K, const void* packed, float* resps, hipStream_t s);
 // comp_resps [T, S*G] (x state_resps [T, S], nullable) -> packed tiles

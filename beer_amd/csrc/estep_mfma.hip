@@ -463,51 +463,58 @@ int estep_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const 
 }
 
 template <typename T>
+struct AccArgs {                    // of acc_kernel: shape, inputs, slab table, statistics image
+    int64_t nframes, fpb;
+    int D, K, G, S, nslab;
+    const T *X, *R, *SR;
+    const int* tab;
+    double* Sp;
+    dim3 grid;
+    size_t lds;
+    hipStream_t s;
+};
+
+template <typename T, int NQ, bool HAS_SR>
+int launch_acc(const AccArgs<T>& a) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(acc_kernel<T, NQ, HAS_SR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL((acc_kernel<T, NQ, HAS_SR>), a.grid, dim3(kThreads), a.lds, a.s, a.nframes,
+                       a.D, a.K, a.G, a.S, a.nslab, a.X, a.R, a.SR, a.tab, a.fpb, a.Sp);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T>
 int acc_impl(int cov, int64_t nframes, int D, int S, int G, const T* X, const T* R, const T* SR,
              double* acc, void* ws, size_t ws_bytes, hipStream_t s) {
     const int K = S * G;
-    if (!supported_acc(D, K, sizeof(T)) || ws_bytes < acc_workspace_bytes(cov, D, K, sizeof(T)))
-        return BEER_EINVAL;
+    const AccForm f = acc_form(sizeof(T), cov, D, K, SR != nullptr);
+    const AccLayout l = acc_layout(sizeof(T), cov, D, K);
+    if (f.rc != BEER_OK || ws_bytes < l.bytes) return BEER_EINVAL;
     const int nslab = nslab_of(cov, D), nq = nslab * 4;
-    double* Sp = reinterpret_cast<double*>(ws);
-    int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) +
-                                      align_up<T>((size_t)K * nq * sizeof(double)));
+    double* Sp = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + l.Sp);
+    int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + l.tab);
     hipLaunchKernelGGL(tab_kernel, dim3(1), dim3(256), 0, s, cov, D, tab);
     BEER_LAUNCH_CHECK();
     hipError_t e = hipMemsetAsync(Sp, 0, (size_t)K * nq * sizeof(double), s);
     if (e != hipSuccess) return -(int)e;
-    const int ntiles = (nq + 15) / 16;
-    const int NQ = ntiles > 8 ? 4 : (ntiles > 4 ? 2 : 1);       // q tiles per wave
-    const int gx = (ntiles + NQ * (kThreads / 64) - 1) / (NQ * (kThreads / 64));
-    const int gy = (K + 16 * kAccMC - 1) / (16 * kAccMC);
-    int64_t gz = (1024 + (int64_t)gx * gy - 1) / ((int64_t)gx * gy);
+    int64_t gz = (1024 + (int64_t)f.gx * f.gy - 1) / ((int64_t)f.gx * f.gy);
     const int64_t max_z = (nframes + 1023) / 1024;
     if (gz > max_z) gz = max_z;
     if (gz < 1) gz = 1;
-    int64_t fpb = (nframes + gz - 1) / gz;
-    fpb = (fpb + kAccFT - 1) / kAccFT * kAccFT;
-    gz = (nframes + fpb - 1) / fpb;
+    const FrameSplit z = frame_split(nframes, gz, kAccFT);
     const size_t lds = 2 * ((size_t)(kAccFT * D + 2 + 3) / 4 * 4 + (size_t)kAccFT * 16 * kAccMC) *
                        sizeof(T);
-    const dim3 grid(gx, gy, (unsigned)gz);
-#define BEER_ACC(NQ_, SR_)                                                                      \
-    do {                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(acc_kernel<T, NQ_, SR_>),       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);        \
-        hipLaunchKernelGGL((acc_kernel<T, NQ_, SR_>), grid, dim3(kThreads), lds, s, nframes, D, \
-                           K, G, S, nslab, X, R, SR, tab, fpb, Sp);                             \
-    } while (0)
-    if (SR) {
-        if (NQ == 4) BEER_ACC(4, true);
-        else if (NQ == 2) BEER_ACC(2, true);
-        else BEER_ACC(1, true);
-    } else {
-        if (NQ == 4) BEER_ACC(4, false);
-        else if (NQ == 2) BEER_ACC(2, false);
-        else BEER_ACC(1, false);
-    }
-#undef BEER_ACC
-    BEER_LAUNCH_CHECK();
+    const AccArgs<T> a = {nframes, z.fpb, D, K, G, S, nslab, X, R, SR, tab, Sp,
+                          dim3(f.gx, f.gy, (unsigned)z.gz), lds, s};
+    static constexpr struct { int NQ; bool has_sr; int (*launch)(const AccArgs<T>&); } kForms[] = {
+        {4, true, launch_acc<T, 4, true>},   {2, true, launch_acc<T, 2, true>},
+        {1, true, launch_acc<T, 1, true>},   {4, false, launch_acc<T, 4, false>},
+        {2, false, launch_acc<T, 2, false>}, {1, false, launch_acc<T, 1, false>}};
+    int rc = BEER_EINVAL;
+    for (const auto& k : kForms)
+        if (k.NQ == f.NQ && k.has_sr == f.has_sr) rc = k.launch(a);
+    if (rc != BEER_OK) return rc;
     const int64_t total = (int64_t)K * stats_dim(cov, D);
     hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cov,
                        D, K, Sp, acc);
@@ -563,11 +570,31 @@ size_t estep_workspace_bytes(size_t elem, int cov, int D, int S, int G) {
            (size_t)nslab * sizeof(int) + 256;
 }
 
-size_t acc_workspace_bytes(int cov, int D, int K, size_t elem) {
-    if (!supported_acc(D, K, elem)) return 0;
+// q tiles of 16 statistics; NQ of them per wave, the workgroup's 4 waves side by side
+AccForm acc_form(size_t elem, int cov, int D, int K, bool has_sr) {
+    AccForm f = {};
+    f.rc = BEER_EINVAL;
+    if (!supported_acc(D, K, elem)) return f;
+    const int ntiles = (nslab_of(cov, D) * 4 + 15) / 16;
+    f.NQ = ntiles > 8 ? 4 : (ntiles > 4 ? 2 : 1);
+    f.has_sr = has_sr;
+    f.gx = (ntiles + f.NQ * (kThreads / 64) - 1) / (f.NQ * (kThreads / 64));
+    f.gy = (K + 16 * kAccMC - 1) / (16 * kAccMC);
+    f.rc = BEER_OK;
+    return f;
+}
+
+// [Sp: K x nq doubles][slab table]
+AccLayout acc_layout(size_t elem, int cov, int D, int K) {
+    AccLayout l = {};
+    if (!supported_acc(D, K, elem)) return l;
     const int nslab = nslab_of(cov, D);
-    return (size_t)(((size_t)K * nslab * 4 * sizeof(double) + 255) / 256 * 256) +
-           (size_t)nslab * sizeof(int) + 256;
+    l.tab = align_up<char>((size_t)K * nslab * 4 * sizeof(double));
+    l.bytes = l.tab + (size_t)nslab * sizeof(int) + 256;
+    return l;
+}
+size_t acc_workspace_bytes(int cov, int D, int K, size_t elem) {
+    return acc_layout(elem, cov, D, K).bytes;
 }
 
 int estep_f32(int cov, int64_t T, int D, int S, int G, const float* X, const float* expT,

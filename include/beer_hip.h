@@ -472,6 +472,48 @@ int beer_frame_image(int cov, int64_t T, int D, const float* X, void* image,
 int beer_estep_route(int entry, int dtype, int cov, int D, int S, int G, unsigned args,
                      size_t workspace_bytes);
 
+/* The same for the accumulation entry points (host only), built from the launchers' own
+ * decisions (estep.hip: accumulate_plan; estep_mfma.hip: acc_form; estep_bf16.hip: accx_form,
+ * accf_form; acc_diag.hip: accd_form); it reads BEER_OPT_ACCFI_WAVES as accf_form does.
+ *   entry            BEER_ACC_PLAIN: beer_normal_accumulate; BEER_ACC_PACKED:
+ *                    beer_normal_accumulate_packed (K = S G), with BEER_ARG_STATE_RESPS
+ *                    beer_mixtureset_accumulate_packed; BEER_ACC_FUSED:
+ *                    beer_mixtureset_accumulate_fused
+ *   dtype            BEER_F32 / BEER_F64, | BEER_EXACT (PLAIN only: the others are float32)
+ *   args             BEER_ARG_RESPS: comp_resps / packed_resps; BEER_ARG_STATE_RESPS;
+ *                    BEER_ARG_IMAGE: the frame image of the fused entry point
+ *   workspace_bytes  0: no workspace
+ * BEER_EINVAL exactly where the entry point refuses the call (its other pointers given), an
+ * empty batch included; else family | form:
+ *   BEER_ACC_GENERIC     accumulate_kernel<T, COV>
+ *   BEER_ACC_EXACT_F32 / _F64 (acc_kernel<T, NQ, HAS_SR>)   | NQ (1 / 2 / 4) | BEER_ACC_SR
+ *   BEER_ACC_DIAG  (accd_kernel<NJ2, NC>)   | NJ2 (1 .. 4) | NC (1 / 2) << 4 | BEER_ACC_D_PARTIAL
+ *   BEER_ACC_ACCX  (accx_kernel<SR, NQ>)    | NQ (6 / 7 / 8) | BEER_ACC_SR | BEER_ACC_X_*
+ *   BEER_ACC_ACCF  (accf_kernel<4, NQT, true, W, XP, BLK>)
+ *                        | NQT (6 / 9 / 10) | BEER_ACC_F_BLK | W (8 / 4) << 21
+ *   BEER_ACC_ACCF | BEER_ACC_F_IMAGE (accfi_kernel<NKU, W, NS>)
+ *                        | NKU (1 .. 4) << 4 | NS (4 / 16) << 16 | W << 21 */
+#define BEER_ACC_PLAIN 0
+#define BEER_ACC_PACKED 1
+#define BEER_ACC_FUSED 2
+#define BEER_ARG_STATE_RESPS 128u
+#define BEER_ARG_IMAGE 256u
+#define BEER_ACC_GENERIC 0x10000000
+#define BEER_ACC_EXACT_F32 0x20000000
+#define BEER_ACC_EXACT_F64 0x30000000
+#define BEER_ACC_DIAG 0x40000000
+#define BEER_ACC_ACCX 0x50000000
+#define BEER_ACC_ACCF 0x60000000
+#define BEER_ACC_FAMILY(route) ((route) & 0x70000000)
+#define BEER_ACC_SR 0x100               /* state posteriors multiplied in by the kernel */
+#define BEER_ACC_D_PARTIAL 0x200        /* partial sums per chain + accd_reduce_kernel */
+#define BEER_ACC_X_SX 0x200             /* D > 118 (sets: > 103): one X^T tile in LDS */
+#define BEER_ACC_X_XT_REUSED 0x400      /* X^T image read from behind the packed tiles */
+#define BEER_ACC_F_BLK 0x200            /* the states of every chunk: 4 consecutive ones */
+#define BEER_ACC_F_IMAGE 0x400          /* accfi_kernel: fragments from the frame image */
+int beer_accumulate_route(int entry, int dtype, int cov, int64_t T, int D, int S, int G,
+                          unsigned args, size_t workspace_bytes);
+
 /* Mixture-weight statistics from the accumulated Gaussian statistics: the
  * zero-order count is N_k = -2 * acc[k, Q-2]; out[s,g] = N_{s,g} for
  * g < G-1 and out[s,G-1] = sum_g N_{s,g} -- the "last column <- row sum"
