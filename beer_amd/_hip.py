@@ -195,6 +195,47 @@ def accumulate_route(entry, dtype_code_, cov, T, D, S, G, args, workspace_bytes)
     return lib().beer_accumulate_route(entry, dtype_code_, cov, T, D, S, G, args, workspace_bytes)
 
 
+# BEER_DENSE_* of include/beer_hip.h: what `beer_dense_route` takes and returns
+DENSE_LLH, DENSE_BACKWARD, DENSE_ACCUMULATE = 0, 1, 2
+DENSE_PLAIN, DENSE_GEMM3 = 0x10000000, 0x20000000
+DENSE_T64x128, DENSE_T128x64, DENSE_T128x128 = 1, 2, 3
+DENSE_AK, DENSE_BK = 0x10, 0x20
+
+
+def dense_family(route):
+    'BEER_DENSE_FAMILY: the kernel family of a `beer_dense_route` value.'
+    return route & 0x70000000
+
+
+def dense_chain(route):
+    'BEER_DENSE_CHAIN: frames a workgroup of the matrix-core accumulation sums in float32.'
+    return (route >> 8 & 0xFF) * 32
+
+
+def dense_route(op, dtype_code_, T, Q, K):
+    '`beer_dense_route`: the kernel and tile a statistics-in product runs on (host only).'
+    return lib().beer_dense_route(op, dtype_code_, T, Q, K)
+
+
+# BEER_SGRAD_* of include/beer_hip.h: what `beer_frames_llh_backward_route` returns
+SGRAD_GENERIC, SGRAD_FULL, SGRAD_DIAG, SGRAD_CHUNKED = 0x10000000, 0x20000000, 0x30000000, 0x40000000
+
+
+def sgrad_family(route):
+    'BEER_SGRAD_FAMILY: the kernel family of a `beer_frames_llh_backward_route` value.'
+    return route & 0x70000000
+
+
+def sgrad_form(route):
+    'BEER_SGRAD_FORM: NKB, NJ2 or the frames per chunk of a `beer_frames_llh_backward_route` value.'
+    return route & 0x0FFFFFFF
+
+
+def frames_llh_backward_route(dtype_code_, cov, T, D, K, workspace_bytes):
+    '`beer_frames_llh_backward_route`: the kernels a gradient w.r.t. the frames runs (host only).'
+    return lib().beer_frames_llh_backward_route(dtype_code_, cov, T, D, K, workspace_bytes)
+
+
 BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
 BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
 
@@ -262,6 +303,8 @@ SIGNATURES = {
                                       c_z, c_p],
     'beer_estep_route': [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_uint, c_z],  # (host only: no stream)
     'beer_accumulate_route': [c_i, c_i, c_i, c_l, c_i, c_i, c_i, ctypes.c_uint, c_z],
+    'beer_dense_route': [c_i, c_i, c_l, c_i, c_i],                  # (host only: no stream)
+    'beer_frames_llh_backward_route': [c_i, c_i, c_l, c_i, c_i, c_z],
     'beer_pack_resps': [c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_weights_from_acc': [c_i, c_i, c_i, c_p, c_p, c_p],
     'beer_tied_lognorm': [c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],

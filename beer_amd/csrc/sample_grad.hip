@@ -462,6 +462,18 @@ inline size_t sg_chunk_bytes(int dtype, int cov, int64_t T_, int D) {
            (dtype == BEER_F64 ? 8 : 4);
 }
 
+// Which kernels a call runs (BEER_SGRAD_* of beer_hip.h): beer_frames_llh_backward and
+// beer_frames_llh_backward_route both ask here.  `ws`: a workspace was given.
+inline int sg_route(int dtype, int cov, int64_t T_, int D, int K, bool ws, size_t ws_bytes) {
+    if (sg_fast(dtype, cov, T_, D, K) && ws && ws_bytes >= sg_image_bytes(D, K))
+        return BEER_SGRAD_FULL | sg_blocks(D);
+    if (sd_fast(dtype, cov, T_, D, K) && ws && ws_bytes >= sd_image_bytes(D, K))
+        return BEER_SGRAD_DIAG | sd_tiles(D);
+    if (T_ >= kSgMinFrames && ws && ws_bytes >= sg_chunk_bytes(dtype, cov, T_, D))
+        return BEER_SGRAD_CHUNKED | (int)sg_chunk_frames(dtype, cov, T_, D);
+    return BEER_SGRAD_GENERIC;
+}
+
 template <typename T>
 int sgrad_generic_launch(int cov, int64_t T_, int D, int K, const void* X, const void* W,
                          const void* g, const void* E, void* out, void* stream) {
@@ -516,6 +528,13 @@ size_t beer_frames_llh_backward_workspace_bytes(int dtype, int cov, int64_t T, i
     return sg_chunk_bytes(dtype, cov, T, D);
 }
 
+int beer_frames_llh_backward_route(int dtype, int cov, int64_t T, int D, int K,
+                                   size_t workspace_bytes) {
+    BEER_REQUIRE(T >= 0 && D >= 1 && K >= 1 && cov >= 0 && cov <= 2);
+    BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
+    return sg_route(dtype, cov, T, D, K, workspace_bytes > 0, workspace_bytes);
+}
+
 int beer_frames_llh_backward(int dtype, int cov, int64_t T, int D, int K, const void* X,
                              const void* weights, const void* grad, const void* exp_stats,
                              void* out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -523,8 +542,9 @@ int beer_frames_llh_backward(int dtype, int cov, int64_t T, int D, int K, const 
     BEER_REQUIRE(dtype == BEER_F32 || dtype == BEER_F64);
     if (T == 0) return BEER_OK;
     BEER_REQUIRE(X && weights && exp_stats && out);
-    if (sg_fast(dtype, cov, T, D, K) && workspace && workspace_bytes >= sg_image_bytes(D, K)) {
-        if (sg_blocks(D) == 1)
+    const int route = sg_route(dtype, cov, T, D, K, workspace != nullptr, workspace_bytes);
+    if (BEER_SGRAD_FAMILY(route) == BEER_SGRAD_FULL) {
+        if (BEER_SGRAD_FORM(route) == 1)
             return sgrad_fast_launch<1>(T, D, K, (const float*)X, (const float*)weights,
                                         (const float*)grad, (const float*)exp_stats, (float*)out,
                                         (char*)workspace, as_stream(stream));
@@ -532,12 +552,12 @@ int beer_frames_llh_backward(int dtype, int cov, int64_t T, int D, int K, const 
                                     (const float*)grad, (const float*)exp_stats, (float*)out,
                                     (char*)workspace, as_stream(stream));
     }
-    if (sd_fast(dtype, cov, T, D, K) && workspace && workspace_bytes >= sd_image_bytes(D, K)) {
+    if (BEER_SGRAD_FAMILY(route) == BEER_SGRAD_DIAG) {
 #define BEER_SD(NJ2_)                                                                            \
     return sgrad_diag_launch<NJ2_>(cov, T, D, K, (const float*)X, (const float*)weights,         \
                                    (const float*)grad, (const float*)exp_stats, (float*)out,     \
                                    (char*)workspace, as_stream(stream))
-        switch (sd_tiles(D)) {
+        switch (BEER_SGRAD_FORM(route)) {
             case 2: BEER_SD(2);
             case 3: BEER_SD(3);
             case 4: BEER_SD(4);
@@ -545,8 +565,8 @@ int beer_frames_llh_backward(int dtype, int cov, int64_t T, int D, int K, const 
         }
 #undef BEER_SD
     }
-    if (T >= kSgMinFrames && workspace && workspace_bytes >= sg_chunk_bytes(dtype, cov, T, D)) {
-        const int64_t chunk = sg_chunk_frames(dtype, cov, T, D);
+    if (BEER_SGRAD_FAMILY(route) == BEER_SGRAD_CHUNKED) {
+        const int64_t chunk = BEER_SGRAD_FORM(route);
         const size_t elem = dtype == BEER_F64 ? 8 : 4;
         const int Q = stats_dim(cov, D);
         for (int64_t c0 = 0; c0 < T; c0 += chunk) {

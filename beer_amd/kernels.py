@@ -543,6 +543,14 @@ def dense_accumulate(stats, comp_resps, state_resps, S, G, acc=None):
         comp_resps, state_resps, G = state_resps, None, 1
     if comp_resps is None:
         comp_resps = torch.ones(T, K, dtype=st.dtype, device=st.device)
+    # the library reads K columns of the weights and K / G of the state posteriors
+    if tuple(comp_resps.shape) != (T, K) or \
+            (state_resps is not None and tuple(state_resps.shape) != (T, K // G)):
+        raise ValueError(f'weights {tuple(comp_resps.shape)} / state posteriors '
+                         f'{None if state_resps is None else tuple(state_resps.shape)} for '
+                         f'{T} frames, {S} x {G} components')
+    if tuple(acc.shape) != (K, Q):
+        raise ValueError(f'accumulator {tuple(acc.shape)} for {K} components of {Q} statistics')
     cr = _hip.on_device(comp_resps.detach(), st.dtype)
     sr = None if state_resps is None else _hip.on_device(state_resps.detach(), st.dtype)
     _hip.call('beer_dense_accumulate', _hip.dtype_code(st.dtype), T, K, Q, G, _hip.ptr(cr),

@@ -982,6 +982,31 @@ int beer_dense_accumulate(int dtype, int64_t T, int K, int Q, int G,
                           const void* weights, const void* state_resps,
                           const void* stats, double* acc, void* stream);
 
+/* Which kernel the three entry points above run for a shape (host only: no pointer, no
+ * stream, nothing launched), from the launchers' own decision (dense.hip: dense_form).
+ *   op      BEER_DENSE_LLH: beer_dense_llh; BEER_DENSE_BACKWARD: beer_dense_llh_backward;
+ *           BEER_DENSE_ACCUMULATE: beer_dense_accumulate (K = S G; any G)
+ *   dtype   BEER_F32 / BEER_F64
+ * BEER_EINVAL for another op or dtype, T < 0, Q < 1 or K < 1; else family | form:
+ *   BEER_DENSE_PLAIN   gemm_kernel<T, TC, ATOMIC> (float64 accumulation)
+ *   BEER_DENSE_GEMM3   gemm3_kernel<.., AK, BK, ATOMIC> | BEER_DENSE_T64x128 / _T128x64 /
+ *                      _T128x128 | BEER_DENSE_AK | BEER_DENSE_BK; BEER_DENSE_ACCUMULATE:
+ *                      | (frames a workgroup sums in float32) / 32 << 8, BEER_DENSE_CHAIN
+ * Every form is held against the oracle in tests/test_gpu_vae_prior_routes.py. */
+#define BEER_DENSE_LLH 0
+#define BEER_DENSE_BACKWARD 1
+#define BEER_DENSE_ACCUMULATE 2
+#define BEER_DENSE_PLAIN 0x10000000
+#define BEER_DENSE_GEMM3 0x20000000
+#define BEER_DENSE_FAMILY(route) ((route) & 0x70000000)
+#define BEER_DENSE_T64x128 1
+#define BEER_DENSE_T128x64 2
+#define BEER_DENSE_T128x128 3
+#define BEER_DENSE_AK 0x10              /* A contiguous along the inner dimension */
+#define BEER_DENSE_BK 0x20              /* B contiguous along the inner dimension */
+#define BEER_DENSE_CHAIN(route) (((route) >> 8 & 0xFF) * 32)
+int beer_dense_route(int op, int dtype, int64_t T, int Q, int K);
+
 /* out[t] = sum_k a[t,k] * b[t,k]  (exp_llh = (pc_llhs * resps).sum(-1)). */
 int beer_rowdot(int dtype, int64_t T, int K, const void* a, const void* b,
                 void* out, void* stream);
@@ -1030,6 +1055,23 @@ int beer_suffstats_backward(int dtype, int cov, int64_t T, int ns, int D,
  * gradient fits it.  T < 4096 (the query returns 0), or workspace
  * NULL: one thread per output, float64 accumulation. */
 size_t beer_frames_llh_backward_workspace_bytes(int dtype, int cov, int64_t T, int D, int K);
+/* Which kernels beer_frames_llh_backward runs (host only), from its own decision
+ * (sample_grad.hip: sg_route).  workspace_bytes: 0 = no workspace.  BEER_EINVAL where the
+ * entry point refuses the call; else family | form:
+ *   BEER_SGRAD_GENERIC   sgrad_generic_kernel<T>
+ *   BEER_SGRAD_FULL      sgrad_kernel<NKB>          | NKB (1 / 2)
+ *   BEER_SGRAD_DIAG      sgrad_diag_kernel<NJ2>     | NJ2 (2 / 3 / 4 / 8)
+ *   BEER_SGRAD_CHUNKED   beer_dense_llh_backward + beer_suffstats_backward per chunk
+ *                                                   | frames per chunk (BEER_SGRAD_FORM)
+ * Every form is held against the oracle in tests/test_gpu_vae_prior_routes.py. */
+#define BEER_SGRAD_GENERIC 0x10000000
+#define BEER_SGRAD_FULL 0x20000000
+#define BEER_SGRAD_DIAG 0x30000000
+#define BEER_SGRAD_CHUNKED 0x40000000
+#define BEER_SGRAD_FAMILY(route) ((route) & 0x70000000)
+#define BEER_SGRAD_FORM(route) ((route) & 0x0FFFFFFF)
+int beer_frames_llh_backward_route(int dtype, int cov, int64_t T, int D, int K,
+                                   size_t workspace_bytes);
 int beer_frames_llh_backward(int dtype, int cov, int64_t T, int D, int K, const void* X,
                              const void* weights, const void* grad, const void* exp_stats,
                              void* out, void* workspace, size_t workspace_bytes,
