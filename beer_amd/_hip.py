@@ -153,6 +153,20 @@ def fb_family(route):
     return route & 0xF000
 
 
+# BEER_SAMPLE_* of include/beer_hip.h: what `beer_hmm_sample_route` returns
+SAMPLE_ARCS_LDS, SAMPLE_QUAD = 0x100, 0x200
+
+
+def sample_chunk(route):
+    'BEER_SAMPLE_CHUNK: the frames the backward draw stages into LDS at a time.'
+    return route & 0xFF
+
+
+def sample_waves(route):
+    'BEER_SAMPLE_WAVES: the samples of one utterance per workgroup of the backward draw.'
+    return (route >> 12) & 0xF
+
+
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
 ESTEP_PLAIN, ESTEP_PACKED, ESTEP_IMAGE = 0, 1, 2
 ARG_PC_LLH, ARG_LOG_NORM, ARG_RESPS, ARG_LLH_SUM, ARG_LABELS, ARG_SCALED, ARG_LOG_WEIGHTS = \
@@ -329,6 +343,8 @@ SIGNATURES = {
                                    c_p, c_p, c_i, c_p, c_p],
     'beer_hmm_bigram_route': [c_i, c_p, ctypes.c_int32, ctypes.c_int32],  # (host only: no stream)
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],
+    'beer_hmm_sample_paths': [c_i, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_i, c_p],
+    'beer_hmm_sample_route': [c_i, c_p, ctypes.c_int32],           # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],

@@ -556,12 +556,18 @@ class train:
 
 
 class decode:
-    'print the most likely path of all the utterances of a dataset'
+    '''print the most likely path of all the utterances of a dataset, or (--nsamples) paths
+    drawn from the posterior'''
 
     @staticmethod
     def setup(parser):
         parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
         parser.add_argument('--per-frame', action='store_true')
+        parser.add_argument('--nsamples', type=int, default=None,
+                            help='print that many paths drawn from the posterior per '
+                                 'utterance, as "<uttid>-<k>", instead of the most likely one')
+        parser.add_argument('--seed', type=int, default=0,
+                            help='seed of the random draws (with --nsamples)')
         parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
         parser.add_argument('-u', '--utts', help='utterances to decode ("-" for stdin)')
         parser.add_argument('model', help='hmm based model')
@@ -574,6 +580,20 @@ class decode:
         alis = _load_alis(args.alis)
         feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
         use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        if args.nsamples is not None:
+            if args.nsamples < 1:
+                raise SystemExit('--nsamples: at least 1')
+            generator = torch.Generator(device=_device())
+            generator.manual_seed(args.seed)
+            draws = beer.sample_paths_batch(model, feats, inference_graphs=use,
+                                            scale=args.acoustic_scale, nsamples=args.nsamples,
+                                            generator=generator) if kept else []
+            for uttid, paths in zip(kept, draws):
+                for k, path in enumerate(paths.cpu().numpy(), start=1):
+                    phones = phones_of_path(path, model.start_pdf, args.per_frame)
+                    print(f'{uttid}-{k}', ' '.join(phones))
+            logger.info(f'successfully drew {args.nsamples} paths for {len(kept)} utterances.')
+            return
         paths = beer.decode_batch(model, feats, inference_graphs=use, scale=args.acoustic_scale) \
             if kept else []
         for uttid, path in zip(kept, paths):

@@ -13,7 +13,7 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'scatter', 'gather_columns', 'scatter_columns', 'segment_sum', 'fused_ok',
            'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space', 'bigram_ok',
            'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
-           'last_frame_sum']
+           'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms']
 
 
 class HmmBatch:
@@ -500,6 +500,71 @@ def viterbi(batch, pc_llhs, map_pdf=False):
     _hip.call('beer_hmm_viterbi', _hip.dtype_code(batch.dtype), batch.ref(),
               _hip.ptr(pc_llhs), _hip.ptr(bt), _hip.ptr(path), 1 if map_pdf else 0)
     return path
+
+
+def check_sample(sample, n_frames, viterbi=False, state_path=None):
+    '''The `sample` argument of the training entry points, checked on the host before any
+    device work: None (False: no draw), True (uniforms from the device's default generator)
+    or the float64 tensor of `n_frames` uniforms.'''
+    if sample is None or sample is False:
+        return None
+    if viterbi or state_path is not None:
+        raise ValueError('sample: a drawn path excludes viterbi=True and state_path=')
+    if sample is True:
+        return True
+    if not torch.is_tensor(sample) or sample.dtype != torch.float64:
+        raise ValueError('sample: True or a float64 tensor of one uniform in [0, 1) per frame')
+    if sample.numel() != n_frames:
+        raise ValueError(f'sample: {sample.numel()} uniforms for {n_frames} frames')
+    return sample
+
+
+def sample_uniforms(sample):
+    'The `uniforms` argument of `sample_paths` for a checked `sample` (True: drawn there).'
+    return None if sample is True else sample.reshape(1, -1)
+
+
+def sample_route(batch, nsamples=1):
+    '''beer_hmm_sample_route: the forms `sample_paths` runs on (frame chunk, arcs in LDS, four
+    lanes per state in the forward pass, samples per workgroup); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_sample_route(_hip.dtype_code(batch.dtype), batch.ref(),
+                                             int(nsamples))
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'sample_paths: {nsamples} samples on graphs of up to {batch.struct.max_states} '
+            "states: at least one sample, and two fp64 trellis rows in the CU's 160 KB of LDS "
+            '(about 10000 states)')
+    return route
+
+
+def sample_paths(batch, pc_llhs, uniforms=None, nsamples=1, generator=None, map_pdf=False,
+                 return_trellis=False):
+    '''`nsamples` state paths per utterance drawn from the posterior, int64 [nsamples, n_frames]
+    (state indices, or pdf ids with `map_pdf`): forward filtering, backward sampling
+    (`beer_hmm_sample_paths`).  `uniforms`: float64 [nsamples, n_frames] in [0, 1), one per
+    sample and frame; default torch.rand on the device with `generator`.  `return_trellis`: also
+    the normalised log-space forward values, fp64 packed like `pc_llhs`.'''
+    dev = batch.device
+    if uniforms is None:
+        nsamples = int(nsamples)
+        if nsamples < 1:
+            raise ValueError('sample_paths: at least one sample')
+        uniforms = torch.rand(nsamples, batch.n_frames, dtype=torch.float64, device=dev,
+                              generator=generator)
+    else:
+        if not torch.is_tensor(uniforms) or uniforms.dtype != torch.float64 or \
+                uniforms.dim() != 2 or uniforms.shape[0] < 1 or \
+                uniforms.shape[1] != batch.n_frames:
+            raise ValueError('sample_paths: uniforms are float64 [nsamples, n_frames]')
+        nsamples = uniforms.shape[0]
+        uniforms = _hip.on_device(uniforms)
+    sample_route(batch, nsamples)
+    alpha = torch.empty(batch.n_elems, dtype=torch.float64, device=dev)
+    path = torch.empty(nsamples, batch.n_frames, dtype=torch.int64, device=dev)
+    _hip.call('beer_hmm_sample_paths', _hip.dtype_code(batch.dtype), batch.ref(),
+              _hip.ptr(pc_llhs), _hip.ptr(uniforms), nsamples, _hip.ptr(alpha), _hip.ptr(path),
+              1 if map_pdf else 0)
+    return (path, alpha) if return_trellis else path
 
 
 def path_posteriors(batch, path, want_xi=False):

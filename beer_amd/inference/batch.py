@@ -31,7 +31,8 @@ from ..models.vae import VAE
 from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
-__all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'ShardStatics']
+__all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
+           'ShardStatics']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
 # three sub-batches are in flight, so a sub-batch may take an eighth of what is free on
@@ -343,7 +344,7 @@ def _emission_estep(groups, stats, dtype, for_accumulate=False):
 
 
 def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths, max_frames,
-               frame_images=None, statics=None):
+               frame_images=None, statics=None, sample=None):
     emissions = model._emissions()
     groups = _groups(emissions)
     S_total = sum(S for _, S, _ in groups)
@@ -389,6 +390,8 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                     if isinstance(grp, TiedMixtureSet) or (G > 1 and not kernels.fused_accumulate_ok(
                         FrameStats(X, _normalset(grp).cov_type), S, G, _normalset(grp).cov_type)))
     bpf = (K_scratch + 2 * S_total) * X.element_size() + max_S * (3 * X.element_size() + 8)
+    if sample is not None:
+        bpf += 16                                 # the uniform and the drawn state of a frame
     if bigram:
         model.declare_block()
         bpf += 16 * len(model.start_pdf)          # the u / v rows the bigram counts come from
@@ -443,7 +446,7 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
             if not all(a is b for a, b in zip(images, images_of(uniq))):
                 statics.items.pop(bkey)
                 batch, _, uniq, images = statics.entry(skey, bkey, make_batch)
-        hard = viterbi or state_paths is not None
+        hard = viterbi or state_paths is not None or sample is not None
         if bigram and not hard:
             # the fused bigram kernel (the general path when the block does not qualify)
             sr, counts = hk.posteriors_bigram(batch, pc_all, scale,
@@ -477,7 +480,11 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         else:
             pc_llhs = hk.gather(batch, pc_all, scale)
             if hard:
-                if state_paths is None:
+                if sample is not None:
+                    # a path drawn from the posterior (forward filtering, backward sampling)
+                    path = hk.sample_paths(batch, pc_llhs, None if sample is True
+                                           else sample.reshape(1, -1)[:, f0:f1])[0]
+                elif state_paths is None:
                     path = hk.viterbi(batch, pc_llhs)
                 else:
                     path = torch.cat([torch.as_tensor(state_paths[u]).reshape(-1) for u in run])
@@ -579,7 +586,8 @@ def _vae_batch(model, X, lengths, datasize, nsamples, llh_weight, kl_weight):
 
 def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale=1.,
                     viterbi=False, state_paths=None, labels=None, max_frames=1 << 24,
-                    nsamples=1, llh_weight=1., kl_weight=1., frame_images=None, statics=None):
+                    nsamples=1, llh_weight=1., kl_weight=1., frame_images=None, statics=None,
+                    sample=False):
     '''ELBO + accumulated statistics of a shard of utterances, identical to the
     sum of per-utterance `evidence_lower_bound(model, utt, datasize=datasize,
     inference_graph=..., scale=..., viterbi=...)` calls.
@@ -592,6 +600,9 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
             (alignment graphs); None = the model's own graph.
         scale: acoustic scale (HMM only).
         viterbi / state_paths: hard-alignment training branches (HMM only).
+        sample: True, or a float64 tensor of one uniform in [0, 1) per packed frame (HMM
+            only): every utterance is trained on a state path drawn from its posterior
+            (`hk.sample_paths`), through the branch `state_paths` takes.
         labels: optional int64 [sum T_u] component labels (Mixture only; the outer
             components of a nested one).
         nsamples, llh_weight, kl_weight: `VAE.expected_log_likelihood`
@@ -603,6 +614,18 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
         statics: optional `ShardStatics` (Mixture, HMM): what depends on the utterance
             lengths and `datasize` only, kept by the caller across iterations.
     '''
+    if sample is not None and sample is not False:
+        # (refused on the host, before the frames go to the device)
+        packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+            isinstance(utterances[0], torch.Tensor)
+        if not packed:
+            utterances = list(utterances)
+        sample = hk.check_sample(sample, sum(int(n) for n in utterances[1]) if packed
+                                 else sum(len(u) for u in utterances), viterbi, state_paths)
+        if not isinstance(model, HMM):
+            raise ValueError('sample: HMM models only')
+    else:
+        sample = None
     X, lengths = pack_utterances(utterances)
     if any(T <= 0 for T in lengths):
         raise ValueError('empty utterance in the batch')
@@ -616,7 +639,8 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
         value_terms, acc = _mixture_batch(model, X, lengths, datasize, labels, max_frames, statics)
     elif isinstance(model, HMM):
         value_terms, acc = _hmm_batch(model, X, lengths, datasize, inference_graphs, scale,
-                                      viterbi, state_paths, max_frames, frame_images, statics)
+                                      viterbi, state_paths, max_frames, frame_images, statics,
+                                      sample)
     elif isinstance(model, VAE):
         value_terms, acc = _vae_batch(model, X, lengths, datasize, nsamples, llh_weight,
                                       kl_weight)
@@ -631,6 +655,31 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
 def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20):
     '''Viterbi pdf-id paths for a shard: list of int64 tensors, one per
     utterance (`HMM.decode`, beer/models/hmm.py:105-114, batched).'''
+    return _paths_batch(model, utterances, inference_graphs, scale, max_frames, 0,
+                        lambda batch, pc_llhs: hk.viterbi(batch, pc_llhs, map_pdf=True))
+
+
+def sample_paths_batch(model, utterances, inference_graphs=None, scale=1., nsamples=1,
+                       generator=None, max_frames=1 << 20):
+    '''`nsamples` pdf-id paths per utterance drawn from the posterior: list of int64
+    [nsamples, T_u] tensors, one per utterance (`HMM.sample_path`, batched).  `generator`: a
+    device torch.Generator for the uniforms.'''
+    nsamples = int(nsamples)
+    if nsamples < 1:
+        raise ValueError('sample_paths_batch: at least one sample')
+    # beside decode_batch's scratch: the fp64 trellis in place of the int32 back-pointers, and
+    # a uniform and a state per sample and frame
+    return _paths_batch(model, utterances, inference_graphs, scale, max_frames, 16 * nsamples,
+                        lambda batch, pc_llhs: hk.sample_paths(
+                            batch, pc_llhs, nsamples=nsamples, generator=generator, map_pdf=True),
+                        trellis_bytes=8)
+
+
+def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_bytes, search,
+                 trellis_bytes=4):
+    '''`search(batch, pc_llhs)` -> paths [..., n_frames] over sub-batches of the shard, split by
+    utterance along the last dimension.  Scratch per frame: decode_batch's, with `trellis_bytes`
+    per state for the search's own workspace and `extra_bytes` besides.'''
     X, lengths = pack_utterances(utterances)
     groups = _groups(model._emissions())
     S_total = sum(S for _, S, _ in groups)
@@ -645,7 +694,8 @@ def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=
             getattr(getattr(inference_graphs[0], '_set', None), 'is_bound', False):
         # graphs bound to learned transitions: E[ln a] on their arcs before the search
         model._bound_set(inference_graphs).refresh(X.dtype)
-    bpf = (K_max + S_total) * X.element_size() + max_S * (X.element_size() + 4)
+    bpf = (K_max + S_total) * X.element_size() + max_S * (X.element_size() + trellis_bytes) + \
+        extra_bytes
     for run in _sub_batches(lengths, bpf, max_frames):
         f0, f1 = off[run[0]], off[run[-1] + 1]
         stats = FrameStats(X[f0:f1], _normalset(groups[0][0]).cov_type)
@@ -662,6 +712,6 @@ def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=
                     uniq.append(g)
                 ids.append(seen[id(g)])
             batch = hk.HmmBatch(uniq, ids, run_lengths, X.dtype)
-        path = hk.viterbi(batch, hk.gather(batch, pc_all, scale), map_pdf=True)
-        paths += list(torch.split(path, run_lengths))
+        path = search(batch, hk.gather(batch, pc_all, scale))
+        paths += list(torch.split(path, run_lengths, dim=-1))
     return paths

@@ -13,7 +13,7 @@ import threading
 import torch
 
 from .. import _hip
-from ..hmm_kernels import segment_sum
+from ..hmm_kernels import check_sample, segment_sum
 
 __all__ = ['evidence_lower_bound', 'EvidenceLowerBoundInstance']
 
@@ -106,7 +106,7 @@ def evidence_lower_bound(model=None, minibatch_data=None, datasize=-1, **kwargs)
     `datasize` frames.  With only `datasize` returns an empty accumulator.
     Extra keyword arguments go to `model.expected_log_likelihood`
     (`labels` for Mixture; `inference_graph`, `viterbi`, `state_path`,
-    `scale` for HMM / PhoneLoop).'''
+    `sample`, `scale` for HMM / PhoneLoop).'''
     if model is None and minibatch_data is None and datasize > 0:
         return EvidenceLowerBoundInstance(0., {}, [], 0, datasize)
     if model is None or minibatch_data is None:
@@ -116,6 +116,10 @@ def evidence_lower_bound(model=None, minibatch_data=None, datasize=-1, **kwargs)
     if datasize <= 0:
         datasize = mb_datasize
     scale = datasize / float(mb_datasize)
+    if 'sample' in kwargs:
+        # (refused on the host, before the statistics go to the device)
+        check_sample(kwargs['sample'], mb_datasize, kwargs.get('viterbi', False),
+                     kwargs.get('state_path'))
     stats = model.sufficient_statistics(minibatch_data)
     exp_llh = model.expected_log_likelihood(stats, **kwargs)
     kl_div = torch.as_tensor(model.kl_div_posterior_prior())

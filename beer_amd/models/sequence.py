@@ -440,12 +440,15 @@ class HMM(DiscreteLatentModel):
         return self.modelset.sufficient_statistics(data)
 
     def expected_log_likelihood(self, stats, inference_graph=None, viterbi=False,
-                                state_path=None, scale=1., utt_lengths=None):
+                                state_path=None, scale=1., utt_lengths=None, sample=False):
         '''sum_s gamma_ts * scale * l_ts per frame (hmm.py:73-92).  Without an
         inference graph the model's own graph is used and the transition
         posteriors are kept (PhoneLoop needs them).  `utt_lengths` (not in
         the reference) treats the frames as that many consecutive utterances,
-        each decoded with the same graph, in one ragged batch.'''
+        each decoded with the same graph, in one ragged batch.  `sample` (not in the
+        reference): True, or a float64 tensor of one uniform per frame -- a state path is
+        drawn from the posterior (`hk.sample_paths`) and trained on as `state_path=` is.'''
+        sample = hk.check_sample(sample, len(stats), viterbi, state_path)
         trans_posts = inference_graph is None
         learned = self.transitions is not None
         # (alignment graphs of a learned model: bound ones only -- checked before any device work)
@@ -475,7 +478,7 @@ class HMM(DiscreteLatentModel):
         # an HMM shard (the per-state posteriors [T, n_states] are not kept then -- a phone
         # loop counts from the first-frame posteriors and hub flows the kernel sums)
         fused = utt_lengths is not None and not viterbi and state_path is None and \
-            hk.fused_ok(batch)
+            sample is None and hk.fused_ok(batch)
         need_counts = trans_posts and hasattr(self, 'start_pdf')
         if fused and need_counts:
             fused = getattr(getattr(batch.dgraphs[0], 'lowdeg', None), 'n_hubs', 0) >= 1
@@ -500,6 +503,8 @@ class HMM(DiscreteLatentModel):
             self.cache['scale'] = scale
             return self._with_gradient(stats, exp_llh, state_resps, emissions, dense)
         pc_llhs = hk.gather(batch, pc_all, scale)
+        if sample is not None:
+            state_path = hk.sample_paths(batch, pc_llhs, hk.sample_uniforms(sample))[0]
         if viterbi or state_path is not None:
             path = hk.viterbi(batch, pc_llhs) if state_path is None else state_path
             gamma, xi, g0 = hk.path_posteriors(batch, path, want_xi=trans_posts)
@@ -569,6 +574,20 @@ class HMM(DiscreteLatentModel):
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
         pc_llhs = hk.gather(batch, pc_all, scale)
         return hk.viterbi(batch, pc_llhs, map_pdf=True).cpu()
+
+    def sample_path(self, data, inference_graph=None, scale=1., nsamples=1, generator=None):
+        '''`nsamples` state paths drawn from the posterior, mapped to pdf ids: LongTensor
+        [nsamples, T] on the host.  `generator`: a device torch.Generator for the uniforms
+        (default: the device's global one).  Otherwise as `decode`.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        pc_llhs = hk.gather(batch, pc_all, scale)
+        return hk.sample_paths(batch, pc_llhs, nsamples=nsamples, generator=generator,
+                               map_pdf=True).cpu()
 
     def posteriors(self, data, inference_graph=None, scale=1.0):
         'State posteriors; `scale` multiplies the statistics (hmm.py:116-121).'
@@ -862,16 +881,18 @@ class BigramPhoneLoop(HMM):
         return xi[ends[:, None], starts[None, :]]
 
     def expected_log_likelihood(self, stats, inference_graph=None, viterbi=False,
-                                state_path=None, scale=1., utt_lengths=None):
-        '''As HMM.expected_log_likelihood; the free loop (no inference graph, no Viterbi,
-        summed transition posteriors) runs on the fused bigram kernel as a ragged batch of
-        one or of `utt_lengths` utterances.'''
+                                state_path=None, scale=1., utt_lengths=None, sample=False):
+        '''As HMM.expected_log_likelihood; the free loop (no inference graph, no Viterbi, no
+        drawn path, summed transition posteriors) runs on the fused bigram kernel as a ragged
+        batch of one or of `utt_lengths` utterances.'''
+        sample = hk.check_sample(sample, len(stats), viterbi, state_path)
         if inference_graph is not None or viterbi or state_path is not None or \
-                (reference_layout_enabled() and utt_lengths is None):
+                sample is not None or (reference_layout_enabled() and utt_lengths is None):
             self.cache.pop('bigram_counts', None)
             self.cache.pop('trans_resps', None)
             return super().expected_log_likelihood(stats, inference_graph, viterbi, state_path,
-                                                   scale, utt_lengths)
+                                                   scale, utt_lengths,
+                                                   sample=False if sample is None else sample)
         dense = kernels.is_dense(stats)
         emissions = self._emissions()
         pc_all = emissions.expected_log_likelihood(stats.detach())

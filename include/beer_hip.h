@@ -921,6 +921,53 @@ int beer_hmm_trans_posteriors(int dtype, int64_t T, int S, const double* alpha,
 int beer_hmm_viterbi(int dtype, const beer_batch* batch_h, const void* pc_llhs,
                      int32_t* bt_ws, int64_t* path, int map_pdf, void* stream);
 
+/* State paths drawn from the posterior p(s_0..s_{T-1} | x) of every utterance: forward
+ * filtering, backward sampling, `nsamples` >= 1 independent paths per utterance from one
+ * forward pass (two launches).
+ *   pc_llhs    packed per-state log-likelihoods, as for beer_hmm_viterbi
+ *   uniforms   [nsamples, n_frames] fp64 in [0, 1), frame index as in frame_off
+ *   alpha_ws   caller-provided, n_elems doubles with the layout of pc_llhs; on return the
+ *              normalised forward values in log space,
+ *                alpha_ws[llh_off[u] + t*S + j] = ln alpha_t(j) - ln sum_i alpha_t(i)
+ *              (-inf for unreachable states); arithmetic is fp64 whatever the dtype
+ *   path       [nsamples, n_frames] int64: the state index, or with `map_pdf` != 0 the pdf id
+ * The rule of a draw.  Last frame: weights w_j = exp(alpha_{T-1}(j) + final_j) over the states
+ * j = 0..S-1.  Frame t < T-1, given the drawn s_{t+1}: w_e = exp(alpha_t(src_e) + in_w_e) over
+ * the in-arcs e of s_{t+1} in CSR order (source ascending).  The chosen term is the first whose
+ * inclusive running sum exceeds u * total; if rounding leaves none, the last term of non-zero
+ * weight.  A term of weight 0 is never chosen, not even at u = 0.  Where total is 0 or not
+ * finite (an utterance the graph cannot explain) the row's first arc is taken -- state 0 at the
+ * last frame or where a row has no arc: deterministic, no NaN, no index out of range.
+ * EINVAL: nsamples < 1 or more than 4 * 65535, a dtype other than BEER_F32 / BEER_F64, more
+ * than 32767 states, or a graph whose two trellis rows do not fit a CU's LDS (about 10000
+ * states); checked before anything is launched. */
+int beer_hmm_sample_paths(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                          const double* uniforms, int32_t nsamples, double* alpha_ws,
+                          int64_t* path, int map_pdf, void* stream);
+
+/* The forms beer_hmm_sample_paths picks for this batch (host only: it reads max_states and
+ * max_arcs and launches nothing), built from the launcher's own expressions:
+ *   chunk | BEER_SAMPLE_ARCS_LDS | BEER_SAMPLE_QUAD | waves << 12
+ * With S = max_states, A = max_arcs, w = 4 / 8 bytes of the dtype, row = 8 S + 32 bytes (a
+ * trellis row and the uniforms of its frame):
+ *   chunk   frames of the trellis the draw stages into LDS at a time: 32 when 32 rows take at
+ *           most 32 KiB, else 8 when 8 rows do, else 2
+ *   BEER_SAMPLE_ARCS_LDS  both kernels keep the arc lists in LDS:
+ *           max(chunk * row, 16 S + 128) + 4 (S + 2 + A) + w A <= 64 KiB; else they are read
+ *           from global memory
+ *   BEER_SAMPLE_QUAD      the forward pass runs four lanes per state on 512 threads
+ *           (4 S <= 512); else one thread per state on 256 threads, strided beyond
+ *   waves   samples of one utterance per workgroup of the draw, one wave each: 1 when
+ *           nsamples == 1, else 4
+ * BEER_SAMPLE_CHUNK(route) and BEER_SAMPLE_WAVES(route) are the two numbers alone.  Whether a
+ * row is scanned by one lane (at most BEER_SEG terms) or by the wave is decided per row inside
+ * the kernel.  BEER_EINVAL exactly where beer_hmm_sample_paths refuses the batch. */
+#define BEER_SAMPLE_ARCS_LDS 0x100
+#define BEER_SAMPLE_QUAD 0x200
+#define BEER_SAMPLE_CHUNK(route) ((route) & 0xFF)
+#define BEER_SAMPLE_WAVES(route) (((route) >> 12) & 0xF)
+int beer_hmm_sample_route(int dtype, const beer_batch* batch_h, int32_t nsamples);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
