@@ -167,6 +167,20 @@ def sample_waves(route):
     return (route >> 12) & 0xF
 
 
+# BEER_EVIDENCE_* of include/beer_hip.h: what `beer_hmm_evidence_route` returns
+EVIDENCE_WAVE, EVIDENCE_BLOCK, EVIDENCE_ARCS_LDS, EVIDENCE_QUAD = 0x1000, 0x2000, 0x100, 0x200
+
+
+def evidence_family(route):
+    'BEER_EVIDENCE_FAMILY: the kernel form of a `beer_hmm_evidence_route` value.'
+    return route & 0xF000
+
+
+def evidence_spl(route):
+    'BEER_EVIDENCE_SPL: the states per lane of the one-wave form.'
+    return route & 0xF
+
+
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
 ESTEP_PLAIN, ESTEP_PACKED, ESTEP_IMAGE = 0, 1, 2
 ARG_PC_LLH, ARG_LOG_NORM, ARG_RESPS, ARG_LLH_SUM, ARG_LABELS, ARG_SCALED, ARG_LOG_WEIGHTS = \
@@ -345,6 +359,8 @@ SIGNATURES = {
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],
     'beer_hmm_sample_paths': [c_i, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_i, c_p],
     'beer_hmm_sample_route': [c_i, c_p, ctypes.c_int32],           # (host only: no stream)
+    'beer_hmm_log_evidence': [c_i, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_evidence_route': [c_i, c_p],                         # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],

@@ -602,6 +602,35 @@ class decode:
         logger.info(f'successfully decoded {len(kept)} utterances.')
 
 
+class score:
+    '''print the log-evidence ln p(x) of all the utterances of a dataset under the model (the
+    forward score, summed over all state paths): "<uttid> <log-evidence> <n_frames>"'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
+        parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('-u', '--utts', help='utterances to score ("-" for stdin)')
+        parser.add_argument('model', help='hmm based model')
+        parser.add_argument('dataset', help='data set')
+
+    @staticmethod
+    def main(args, logger):
+        model = _load(args.model).to(_device())
+        dataset = _load(args.dataset)
+        alis = _load_alis(args.alis)
+        feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
+        use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        values = beer.log_evidence_batch(model, feats, inference_graphs=use,
+                                         scale=args.acoustic_scale).cpu().tolist() if kept else []
+        total, n_frames = 0., 0
+        for uttid, value, utt in zip(kept, values, feats):
+            print(uttid, '%.6f' % value, len(utt))
+            total, n_frames = total + value, n_frames + len(utt)
+        logger.info(f'scored {len(kept)} utterances: total log-evidence {total:.3f}, '
+                    f'{total / max(n_frames, 1):.4f} per frame over {n_frames} frames.')
+
+
 class posteriors:
     'state / phone posteriors of all the utterances of a dataset'
     EPS = 1e-5
@@ -641,4 +670,4 @@ class posteriors:
 
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
-            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update]
+            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score]

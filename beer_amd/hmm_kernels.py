@@ -13,7 +13,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'scatter', 'gather_columns', 'scatter_columns', 'segment_sum', 'fused_ok',
            'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space', 'bigram_ok',
            'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
-           'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms']
+           'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms',
+           'log_evidence', 'evidence_route']
 
 
 class HmmBatch:
@@ -565,6 +566,32 @@ def sample_paths(batch, pc_llhs, uniforms=None, nsamples=1, generator=None, map_
               _hip.ptr(pc_llhs), _hip.ptr(uniforms), nsamples, _hip.ptr(alpha), _hip.ptr(path),
               1 if map_pdf else 0)
     return (path, alpha) if return_trellis else path
+
+
+def evidence_route(batch):
+    '''beer_hmm_evidence_route: the form `log_evidence` runs on (one wave per utterance with
+    1 / 2 / 4 states a lane, or one workgroup per utterance with its arcs in LDS and four lanes
+    per state or not); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_evidence_route(_hip.dtype_code(batch.dtype), batch.ref())
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'log_evidence: graphs of up to {batch.struct.max_states} states: two fp64 rows '
+            "must fit the CU's 160 KB of LDS (about 10000 states)")
+    return route
+
+
+def log_evidence(batch, pc_llhs, per_frame=False):
+    '''(utt [nutt] fp64, frame [n_frames] fp64 or None), on the device: ln p(x) of every
+    utterance under its graph, summed over all state paths, and with `per_frame` the terms
+    ln p(x_t | x_0 .. x_{t-1}) it is made of, without the final weights
+    (`beer_hmm_log_evidence`: the forward pass alone, no trellis).'''
+    dev = batch.device
+    evidence_route(batch)
+    utt = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    frame = torch.empty(batch.n_frames, dtype=torch.float64, device=dev) if per_frame else None
+    _hip.call('beer_hmm_log_evidence', _hip.dtype_code(batch.dtype), batch.ref(),
+              _hip.ptr(pc_llhs), _hip.ptr(utt), _hip.ptr(frame))
+    return utt, frame
 
 
 def path_posteriors(batch, path, want_xi=False):

@@ -32,7 +32,7 @@ from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
-           'ShardStatics']
+           'log_evidence_batch', 'ShardStatics']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
 # three sub-batches are in flight, so a sub-batch may take an eighth of what is free on
@@ -675,11 +675,50 @@ def sample_paths_batch(model, utterances, inference_graphs=None, scale=1., nsamp
                         trellis_bytes=8)
 
 
+def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_frame=False,
+                       max_frames=1 << 20):
+    '''ln p(x) of every utterance of a shard under the model, summed over all state paths:
+    float64 [nutt] on the device (`HMM.log_evidence`, batched); with `per_frame` also a list of
+    float64 [T_u] tensors, the terms ln p(x_t | x_0 .. x_{t-1}) of every utterance.'''
+    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+        isinstance(utterances[0], torch.Tensor)
+    if not packed:
+        utterances = list(utterances)
+    if inference_graphs is not None:
+        nutt = len(utterances[1]) if packed else len(utterances)
+        if len(inference_graphs) != nutt:
+            raise ValueError(f'log_evidence_batch: {len(inference_graphs)} inference graphs for '
+                             f'{nutt} utterances')
+    totals, frames = [], []
+    # decode_batch's scratch without the trellis; a float64 per frame besides
+    for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
+                                                       max_frames, 8 if per_frame else 0, 0):
+        utt, frame = hk.log_evidence(batch, pc_llhs, per_frame=per_frame)
+        totals.append(utt)
+        if per_frame:
+            frames += list(torch.split(frame, run_lengths))
+    total = torch.cat(totals) if totals else \
+        torch.zeros(0, dtype=torch.float64, device=_hip.require_device())
+    return (total, frames) if per_frame else total
+
+
 def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_bytes, search,
                  trellis_bytes=4):
     '''`search(batch, pc_llhs)` -> paths [..., n_frames] over sub-batches of the shard, split by
     utterance along the last dimension.  Scratch per frame: decode_batch's, with `trellis_bytes`
     per state for the search's own workspace and `extra_bytes` besides.'''
+    paths = []
+    for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
+                                                       max_frames, extra_bytes, trellis_bytes):
+        paths += list(torch.split(search(batch, pc_llhs), run_lengths, dim=-1))
+    return paths
+
+
+def _search_batches(model, utterances, inference_graphs, scale, max_frames, extra_bytes,
+                    trellis_bytes):
+    '''The sub-batches of a shard for a search over its utterances: yields (HmmBatch, gathered
+    pc_llhs, lengths) per sub-batch.  Scratch per frame: the emissions' E-step, the gathered
+    log-likelihoods, `trellis_bytes` per state and `extra_bytes` besides.'''
     X, lengths = pack_utterances(utterances)
     groups = _groups(model._emissions())
     S_total = sum(S for _, S, _ in groups)
@@ -687,7 +726,6 @@ def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_b
     off = [0]
     for T in lengths:
         off.append(off[-1] + T)
-    paths = []
     max_S = model.graph.n_states if inference_graphs is None \
         else max(g.n_states for g in inference_graphs)
     if inference_graphs is not None and len(inference_graphs) and \
@@ -712,6 +750,4 @@ def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_b
                     uniq.append(g)
                 ids.append(seen[id(g)])
             batch = hk.HmmBatch(uniq, ids, run_lengths, X.dtype)
-        path = search(batch, hk.gather(batch, pc_all, scale))
-        paths += list(torch.split(path, run_lengths, dim=-1))
-    return paths
+        yield batch, hk.gather(batch, pc_all, scale), run_lengths

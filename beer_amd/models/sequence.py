@@ -589,6 +589,20 @@ class HMM(DiscreteLatentModel):
         return hk.sample_paths(batch, pc_llhs, nsamples=nsamples, generator=generator,
                                map_pdf=True).cpu()
 
+    def log_evidence(self, data, inference_graph=None, scale=1., per_frame=False):
+        '''ln p(x_0 .. x_{T-1}) under the model's expected log-likelihoods and the graph's
+        (expected) log-transitions, summed over all state paths: a 0-d float64 tensor on the
+        device, or with `per_frame` (value, [T] float64 of ln p(x_t | x_0 .. x_{t-1})).  Not in
+        the reference, whose `lognorm` (graph.py:289-326) is this number.  Otherwise as `decode`.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        utt, frame = hk.log_evidence(batch, hk.gather(batch, pc_all, scale), per_frame=per_frame)
+        return (utt[0], frame) if per_frame else utt[0]
+
     def posteriors(self, data, inference_graph=None, scale=1.0):
         'State posteriors; `scale` multiplies the statistics (hmm.py:116-121).'
         graph = self.graph if inference_graph is None else inference_graph

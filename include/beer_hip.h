@@ -968,6 +968,66 @@ int beer_hmm_sample_paths(int dtype, const beer_batch* batch_h, const void* pc_l
 #define BEER_SAMPLE_WAVES(route) (((route) >> 12) & 0xF)
 int beer_hmm_sample_route(int dtype, const beer_batch* batch_h, int32_t nsamples);
 
+/* The log-evidence ln p(x_0 .. x_{T-1}) of every utterance under its graph, summed over all
+ * state paths: the forward pass alone, one launch, no trellis and no workspace.
+ *   pc_llhs         packed per-state log-likelihoods, as for beer_hmm_viterbi (read only)
+ *   utt_evidence    [nutt] fp64 whatever the dtype, written (=)
+ *   frame_evidence  nullable, [n_frames] fp64, written (=), frame index as in frame_off; with
+ *                   or without it `utt_evidence` is the same, bit for bit
+ * Definition, over the full in-CSR (hub and bigram arcs included, as beer_hmm_viterbi and
+ * beer_hmm_sample_paths read it), l_t(j) the log-likelihoods, w_ij the arcs' log-weights:
+ *   a_0(j) = init_j + l_0(j)
+ *   a_t(j) = l_t(j) + ln sum_i exp(â_{t-1}(i) + w_ij)
+ *   c_t    = ln sum_j exp(a_t(j)),    â_t = a_t - c_t
+ *   frame_evidence[frame_off[u] + t] = c_t            = ln p(x_t | x_0 .. x_{t-1}), no final term
+ *   utt_evidence[u] = sum_t c_t + ln sum_j exp(â_{T-1}(j) + final_j)
+ * which is the reference's `lognorm` (graph.py:289-326) and the logarithm of the sum, over all
+ * S^T state paths, of exp(path score).  Log space: maxima, differences, running sums and the
+ * per-utterance sum are fp64, exp / log of a difference to the maximum are in the model's
+ * precision; no range flags, no redo path.  (The one-wave form below works on scaled fp64
+ * probabilities and owns the hand-over: inside the kernel, an utterance in which a frame has no
+ * reachable state or a normaliser below 2^-800, or whose graph has an arc weight exp(w) the
+ * dtype cannot hold, is started again in log space; a state whose mass falls below 2^-1022 of
+ * its frame's total without that showing is lost, as in beer_hmm_forward_backward.)
+ * Edges.  -inf log-likelihoods and unreachable states are legal.  From the first frame at which
+ * no state is reachable, frame_evidence is -inf for the rest of the utterance and utt_evidence[u]
+ * is -inf.  When only the final term is unreachable the frames stay finite and utt_evidence[u] is
+ * -inf.  Inputs without NaN give no NaN, and no utterance sees another's values (NaN inputs are
+ * outside the contract).  T = 1 is legal; an utterance of no frames gets utt_evidence[u] = 0.
+ * EINVAL exactly where beer_hmm_sample_paths refuses the batch: a dtype other than BEER_F32 /
+ * BEER_F64, more than 32767 states, or a graph whose two fp64 rows (plus 128 bytes) do not fit a
+ * CU's 160 KiB of LDS (more than 10232 states); also a NULL pc_llhs or utt_evidence.  Everything
+ * is checked before anything is launched. */
+int beer_hmm_log_evidence(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                          double* utt_evidence, double* frame_evidence, void* stream);
+
+/* The form beer_hmm_log_evidence picks for this batch (host only: it reads max_states and
+ * max_arcs and launches nothing), built from the launcher's own expressions.  With
+ * S = max_states, A = max_arcs, w = 4 / 8 bytes of the dtype and
+ * arcs = 4 (S + 2 + A) + w A bytes (the in-CSR of the largest graph):
+ *   BEER_EVIDENCE_WAVE | SPL    one wave per utterance, four utterances per workgroup, SPL
+ *           states per lane -- 1 (S <= 64), 2 (S <= 128) or 4 (S <= 256) -- the normalised row
+ *           and the utterance's own arc lists in the wave's slice of LDS, no workgroup barrier
+ *           in the frame loop, utterances handed to waves longest first (batch->order); the wave
+ *           runs on scaled probabilities (one exponential per state and frame, none on an arc)
+ *           and starts an utterance that leaves fp64's range again in log space:
+ *           S <= 256 and 512 SPL + arcs <= 16 KiB
+ *   BEER_EVIDENCE_BLOCK | BEER_EVIDENCE_ARCS_LDS | BEER_EVIDENCE_QUAD    else: one workgroup per
+ *           utterance;
+ *           BEER_EVIDENCE_ARCS_LDS  the arc lists are kept in LDS: 16 S + 128 + arcs <= 64 KiB;
+ *                                   else they are read from global memory
+ *           BEER_EVIDENCE_QUAD      four lanes per state on 512 threads (4 S <= 512); else one
+ *                                   thread per state on 256 threads, strided beyond
+ * BEER_EVIDENCE_FAMILY(route) is the family alone, BEER_EVIDENCE_SPL(route) the states per lane
+ * of the wave form.  BEER_EINVAL exactly where beer_hmm_log_evidence refuses the batch. */
+#define BEER_EVIDENCE_WAVE 0x1000
+#define BEER_EVIDENCE_BLOCK 0x2000
+#define BEER_EVIDENCE_ARCS_LDS 0x100
+#define BEER_EVIDENCE_QUAD 0x200
+#define BEER_EVIDENCE_FAMILY(route) ((route) & 0xF000)
+#define BEER_EVIDENCE_SPL(route) ((route) & 0xF)
+int beer_hmm_evidence_route(int dtype, const beer_batch* batch_h);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
