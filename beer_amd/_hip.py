@@ -133,6 +133,11 @@ class CatMap(ctypes.Structure):
     _fields_ = [('arc_cat', c_p), ('last_cat', c_p), ('arc_off', c_p), ('state_off', c_p)]
 
 
+class ArcMap(ctypes.Structure):
+    'beer_arc_map of include/beer_hip.h.'
+    _fields_ = [('arc_cat', c_p), ('init_cat', c_p), ('arc_off', c_p), ('state_off', c_p)]
+
+
 class Bigram(ctypes.Structure):
     'beer_bigram of include/beer_hip.h.'
     _fields_ = [('n_states', ctypes.c_int32), ('n_phones', ctypes.c_int32),
@@ -179,6 +184,15 @@ def evidence_family(route):
 def evidence_spl(route):
     'BEER_EVIDENCE_SPL: the states per lane of the one-wave form.'
     return route & 0xF
+
+
+# BEER_ARCS_* of include/beer_hip.h: what `beer_hmm_arcs_route` returns
+ARCS_BLOCK, ARCS_ARCS_LDS, ARCS_FRAME_LDS, ARCS_UTT_LDS = 0x1000, 0x100, 0x200, 0x400
+
+
+def arcs_family(route):
+    'BEER_ARCS_FAMILY: the kernel form of a `beer_hmm_arcs_route` value.'
+    return route & 0xF000
 
 
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
@@ -361,6 +375,8 @@ SIGNATURES = {
     'beer_hmm_sample_route': [c_i, c_p, ctypes.c_int32],           # (host only: no stream)
     'beer_hmm_log_evidence': [c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_evidence_route': [c_i, c_p],                         # (host only: no stream)
+    'beer_hmm_arc_posteriors': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
+    'beer_hmm_arcs_route': [c_i, c_p, c_i, c_i],                   # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],
@@ -410,6 +426,7 @@ SIZE_QUERIES = {
     'beer_accumulate_packed_workspace_bytes': [c_i, c_l, c_i, c_i],
     'beer_mixtureset_accumulate_packed_workspace_bytes': [c_i, c_l, c_i, c_i, c_i],
     'beer_hmm_fb_scratch_doubles': [c_i, c_p, c_i],
+    'beer_hmm_arcs_scratch_doubles': [c_i, c_p],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
 }
 

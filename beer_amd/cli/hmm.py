@@ -631,6 +631,48 @@ class score:
                     f'{total / max(n_frames, 1):.4f} per frame over {n_frames} frames.')
 
 
+class boundaries:
+    '''write the unit-start posteriors of all the utterances of a dataset, "<outdir>/<uttid>.npy"
+    [T, n_units]: the probability that a unit begins at a frame (summed over the units: the
+    boundary posterior of the frame); --counts also prints the expected number of occurrences of
+    every unit, "<uttid> <count of unit 1> ... <count of unit U>"'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
+        parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('-u', '--utts', help='utterances to process ("-" for stdin)')
+        parser.add_argument('--counts', action='store_true',
+                            help='print the expected unit counts of every utterance')
+        parser.add_argument('model', help='phone-loop model')
+        parser.add_argument('dataset', help='data set')
+        parser.add_argument('outdir', help='output directory')
+
+    @staticmethod
+    def main(args, logger):
+        model = _load(args.model).to(_device())
+        dataset = _load(args.dataset)
+        alis = _load_alis(args.alis)
+        feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
+        use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        os.makedirs(args.outdir, exist_ok=True)
+        starts = beer.unit_starts_batch(model, feats, inference_graphs=use,
+                                        scale=args.acoustic_scale) if kept else []
+        # (the counts in float64 from the kernel's own sums, not from the written rows)
+        counts = beer.unit_counts_batch(model, feats, inference_graphs=use,
+                                        scale=args.acoustic_scale).cpu().numpy() \
+            if kept and args.counts else None
+        total = 0.
+        for n, (uttid, post) in enumerate(zip(kept, starts)):
+            post = post.cpu().numpy()
+            np.save(os.path.join(args.outdir, f'{uttid}.npy'), post)
+            total += float(post.sum(dtype=np.float64))
+            if counts is not None:
+                print(uttid, ' '.join('%.6f' % c for c in counts[n]))
+        logger.info(f'wrote the unit-start posteriors of {len(kept)} utterances: '
+                    f'{total / max(len(kept), 1):.2f} expected units per utterance.')
+
+
 class posteriors:
     'state / phone posteriors of all the utterances of a dataset'
     EPS = 1e-5
@@ -670,4 +712,4 @@ class posteriors:
 
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
-            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score]
+            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, boundaries]

@@ -279,6 +279,12 @@ class SparseGraph:
         return CompiledGraph(self.init_log_probs, self.final_log_probs, self.trans_log_probs,
                              [int(i) for i in self.pdf_id_mapping])
 
+    def out_arcs(self):
+        '''(sources, destinations), int32 host arrays: the arcs of the full out-CSR in the order
+        the kernels hold them, by (source, destination) (`CompiledGraph.out_arcs`).'''
+        src, dst, _ = self._arcs()
+        return src, dst
+
     def device_graph(self, dtype):
         blob, structs = self._set.device_image(dtype)
         return _ArenaDeviceGraph(structs[self._i], (self._set, blob))
@@ -848,6 +854,15 @@ class CompiledGraph(torch.nn.Module):
         state.pop('_bigram_rewritten', None)
         state.pop('_batch_cache', None)
         return state
+
+    def out_arcs(self):
+        '''(sources, destinations), int32 host arrays: the arcs of the full out-CSR in the order
+        the kernels hold them -- the finite entries of `trans_log_probs` in row-major order (hub
+        and bigram arcs are explicit in it).  What `arc_cat` of `hmm_kernels.arc_posteriors`
+        follows.'''
+        finite = self.trans_log_probs.detach().to('cpu') > -float('inf')
+        src, dst = torch.nonzero(finite, as_tuple=True)
+        return src.numpy().astype(np.int32), dst.numpy().astype(np.int32)
 
     def device_graph(self, dtype):
         '''CSR copy on the GPU in `dtype`, rebuilt when a buffer is replaced

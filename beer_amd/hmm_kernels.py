@@ -14,7 +14,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'posteriors_fused', 'trans_posteriors_dense', 'counting_log_space', 'bigram_ok',
            'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
            'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms',
-           'log_evidence', 'evidence_route']
+           'log_evidence', 'evidence_route', 'arc_posteriors', 'arcs_route',
+           'check_arc_categories']
 
 
 class HmmBatch:
@@ -42,6 +43,7 @@ class HmmBatch:
             head = np.ascontiguousarray(raw[:, :16]).view(np.int32)      # n_states, n_arcs, segs
             has_lowdeg = np.ascontiguousarray(raw[:, size - 8:]).view(np.int64).reshape(-1) != 0
             n_states = head[:, 0].tolist()
+            n_arcs = head[:, 1].tolist()
             max_arcs = int(head[:, 1].max())
             max_segs = int(head[:, 2:4].max())
             all_lowdeg = bool(has_lowdeg.all())
@@ -67,7 +69,8 @@ class HmmBatch:
             pdf_ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
             arr = (_hip.Graph * len(graphs))(*[dg.struct for dg in self.dgraphs])
             graph_bytes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            max_arcs = max([dg.n_arcs for dg in self.dgraphs] + [1])
+            n_arcs = [dg.n_arcs for dg in self.dgraphs]
+            max_arcs = max(n_arcs + [1])
             max_segs = max([max(dg.n_in_seg, dg.n_out_seg) for dg in self.dgraphs] + [1])
             all_lowdeg = bool(self.dgraphs) and \
                 all(getattr(dg, 'lowdeg', None) is not None for dg in self.dgraphs)
@@ -85,6 +88,7 @@ class HmmBatch:
         self.n_elems = int(llh_off[-1])
         self.frame_off_h, self.llh_off_h = frame_off, llh_off
         self.n_states = n_states
+        self.n_arcs = n_arcs                        # arcs of the full CSR of every distinct graph
         self.graph_ids = list(graph_ids)
         # longest utterance first: the waves of a workgroup of the one-wave kernels then
         # finish together, and a launch ends with its shortest utterances
@@ -592,6 +596,99 @@ def log_evidence(batch, pc_llhs, per_frame=False):
     _hip.call('beer_hmm_log_evidence', _hip.dtype_code(batch.dtype), batch.ref(),
               _hip.ptr(pc_llhs), _hip.ptr(utt), _hip.ptr(frame))
     return utt, frame
+
+
+def arcs_route(batch, n_cat, per_frame=True):
+    '''beer_hmm_arcs_route: the form `arc_posteriors` runs on (arcs in LDS or not, a frame's
+    bins in LDS or not, the utterance's bins in LDS or not); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_arcs_route(_hip.dtype_code(batch.dtype), batch.ref(), int(n_cat),
+                                           1 if per_frame else 0)
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'arc_posteriors: {n_cat} categories on graphs of up to {batch.struct.max_states} '
+            "states: at least one category, and two fp64 rows in the CU's 160 KB of LDS (about "
+            '10000 states)')
+    return route
+
+
+def check_arc_categories(n_arcs, n_states, arc_cat, init_cat, n_cat, per_frame=True,
+                         per_utt=False):
+    '''The category arguments of `arc_posteriors`, checked on the host before any device work:
+    `n_arcs` / `n_states` are the arc and state counts of the distinct graphs of a batch,
+    `arc_cat` / `init_cat` one integer array per graph (host or device) or, already concatenated,
+    one tensor each.  Returns (all arc categories, all init categories) as int32 tensors (on the
+    host unless the caller's were on the device).  ValueError: neither output asked for,
+    n_cat < 1, lengths that do not match the graphs, categories >= n_cat or < -1.'''
+    if not (per_frame or per_utt):
+        raise ValueError('arc_posteriors: neither per_frame nor per_utt is asked for')
+    n_cat = int(n_cat)
+    if n_cat < 1:
+        raise ValueError(f'arc_posteriors: {n_cat} categories')
+    out = []
+    for what, cats, counts in (('arc_cat', arc_cat, n_arcs), ('init_cat', init_cat, n_states)):
+        if torch.is_tensor(cats):
+            if cats.dim() != 1 or cats.numel() != sum(counts):
+                raise ValueError(f'arc_posteriors: {what} has {cats.numel()} entries, the graphs '
+                                 f'of the batch {sum(counts)}')
+            flat = cats
+        else:
+            cats = [torch.as_tensor(np.asarray(c.cpu() if torch.is_tensor(c) else c))
+                    for c in cats]
+            if len(cats) != len(counts):
+                raise ValueError(f'arc_posteriors: {len(cats)} {what} arrays for {len(counts)} '
+                                 'distinct graphs')
+            for i, (c, n) in enumerate(zip(cats, counts)):
+                if c.dim() != 1 or c.numel() != n:
+                    raise ValueError(f'arc_posteriors: {what} of graph {i} has {c.numel()} '
+                                     f'entries, the graph {n}')
+            flat = torch.cat(cats) if cats else torch.zeros(0, dtype=torch.int32)
+        if flat.dtype.is_floating_point or flat.dtype == torch.bool:
+            raise ValueError(f'arc_posteriors: {what} must be integers, not {flat.dtype}')
+        if flat.numel() and (int(flat.max()) >= n_cat or int(flat.min()) < -1):
+            raise ValueError(f'arc_posteriors: {what} outside [-1, {n_cat}): '
+                             f'{int(flat.min())} .. {int(flat.max())}')
+        out.append(flat.to(torch.int32).contiguous())
+    return tuple(out)
+
+
+def arc_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, per_frame=True, per_utt=False):
+    '''(frame_out [n_frames, n_cat] of the batch's dtype or None, utt_out [nutt, n_cat] fp64 or
+    None), on the device: the posterior of every arc at every frame folded into categories
+    (`beer_hmm_arc_posteriors`).  Row t >= 1 of an utterance holds, per category c, the sum of
+    P(s_{t-1} = i, s_t = j | x) over the arcs i -> j with `arc_cat` = c; row 0 the sum of
+    gamma_0(j) over the states with `init_cat` = c; `utt_out` the sum of an utterance's rows.
+    `arc_cat` follows the full out-CSR of every distinct graph of the batch (`out_arcs()` of the
+    graph classes gives its (src, dst) pairs), `init_cat` its states; both are one int array per
+    distinct graph or already concatenated tensors, with entries in [0, n_cat) or -1 (count
+    nothing).  An utterance whose evidence is -inf gets zeros.'''
+    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat,
+                                       per_frame, per_utt)
+    n_cat = int(n_cat)
+    dev = batch.device
+    arcs_route(batch, n_cat, per_frame)
+    if batch.nutt == 0:
+        return (torch.empty(0, n_cat, dtype=batch.dtype, device=dev) if per_frame else None,
+                torch.empty(0, n_cat, dtype=torch.float64, device=dev) if per_utt else None)
+    dcode = _hip.dtype_code(batch.dtype)
+    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+    if arcs.device.type != 'cuda':
+        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+    if inits.device.type != 'cuda':
+        host['inits'] = inits
+    up = _hip.upload(host, dev)
+    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
+                       up['state_off'].data_ptr())
+    extra = _hip.lib().beer_hmm_arcs_scratch_doubles(dcode, batch.ref())
+    ws = torch.empty(batch.n_frames + batch.n_elems + extra, dtype=torch.float64, device=dev)
+    frame = torch.empty(batch.n_frames, n_cat, dtype=batch.dtype, device=dev) \
+        if per_frame else None
+    utt = torch.empty(batch.nutt, n_cat, dtype=torch.float64, device=dev) if per_utt else None
+    _hip.call('beer_hmm_arc_posteriors', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              ctypes.byref(amap), n_cat, _hip.ptr(ws), _hip.ptr(frame), _hip.ptr(utt))
+    return frame, utt
 
 
 def path_posteriors(batch, path, want_xi=False):

@@ -26,13 +26,13 @@ from .. import _hip, hmm_kernels as hk, kernels
 from ..models.gaussians import NormalSet
 from ..models.mixtures import Mixture, MixtureSet, TiedMixtureSet
 from ..models.modelset import JointModelSet
-from ..models.sequence import HMM, BigramPhoneLoop, PhoneLoop
+from ..models.sequence import HMM, BigramPhoneLoop, PhoneLoop, unit_start_categories
 from ..models.vae import VAE
 from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
-           'log_evidence_batch', 'ShardStatics']
+           'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch', 'ShardStatics']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
 # three sub-batches are in flight, so a sub-batch may take an eighth of what is free on
@@ -702,6 +702,62 @@ def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_f
     return (total, frames) if per_frame else total
 
 
+def unit_starts_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20):
+    '''Unit-start posteriors of every utterance of a shard: a list of [T_u, n_units] tensors on
+    the device, the units in `model.start_pdf` order (`PhoneLoop.unit_starts`, batched).'''
+    return _unit_arcs_batch('unit_starts_batch', model, utterances, inference_graphs, scale,
+                            max_frames, True)
+
+
+def unit_counts_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20):
+    '''Expected number of occurrences of every unit in every utterance of a shard: float64
+    [nutt, n_units] on the device, the sums over the frames of `unit_starts_batch` -- a soft bag
+    of units.'''
+    return _unit_arcs_batch('unit_counts_batch', model, utterances, inference_graphs, scale,
+                            max_frames, False)
+
+
+def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame):
+    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+        isinstance(utterances[0], torch.Tensor)
+    if not packed:
+        utterances = list(utterances)
+    if inference_graphs is not None:
+        nutt = len(utterances[1]) if packed else len(utterances)
+        if len(inference_graphs) != nutt:
+            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
+                             'utterances')
+    if not hasattr(model, 'start_pdf'):
+        raise ValueError(f'{what}: a phone loop (a model with units), not '
+                         f'{type(model).__name__}')
+    n_units = len(model.start_pdf)
+    cats = {}                       # the categories of every distinct graph, built once per call
+
+    def categories(graph):
+        if id(graph) not in cats:
+            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+        return cats[id(graph)]
+
+    out = []
+    # decode_batch's scratch with the fp64 trellis in place of the back-pointers; a normaliser
+    # and the output row per frame besides (sized for float64)
+    row = 8 * n_units if per_frame else 0
+    for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
+                                                       max_frames, 8 + row, 8):
+        pairs = [categories(g) for g in batch.distinct_graphs]
+        frame, utt = hk.arc_posteriors(batch, pc_llhs, [p[0] for p in pairs],
+                                       [p[1] for p in pairs], n_units, per_frame=per_frame,
+                                       per_utt=not per_frame)
+        if per_frame:
+            out += list(torch.split(frame, run_lengths))
+        else:
+            out.append(utt)
+    if per_frame:
+        return out
+    return torch.cat(out) if out else \
+        torch.zeros(0, n_units, dtype=torch.float64, device=_hip.require_device())
+
+
 def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_bytes, search,
                  trellis_bytes=4):
     '''`search(batch, pc_llhs)` -> paths [..., n_frames] over sub-batches of the shard, split by
@@ -740,7 +796,8 @@ def _search_batches(model, utterances, inference_graphs, scale, max_frames, extr
         pc_all, _ = _emission_estep(groups, stats, X.dtype)
         run_lengths = [lengths[u] for u in run]
         if inference_graphs is None:
-            batch = hk.HmmBatch([model.graph], [0] * len(run), run_lengths, X.dtype)
+            uniq = [model.graph]
+            batch = hk.HmmBatch(uniq, [0] * len(run), run_lengths, X.dtype)
         else:
             uniq, ids, seen = [], [], {}
             for u in run:
@@ -750,4 +807,5 @@ def _search_batches(model, utterances, inference_graphs, scale, max_frames, extr
                     uniq.append(g)
                 ids.append(seen[id(g)])
             batch = hk.HmmBatch(uniq, ids, run_lengths, X.dtype)
+        batch.distinct_graphs = uniq
         yield batch, hk.gather(batch, pc_all, scale), run_lengths

@@ -5,6 +5,7 @@ The per-utterance methods below drive the same ragged-batch kernels as the
 batched accumulator (beer_amd/inference/batch.py) with a batch of one.
 """
 
+import numpy as np
 import torch
 
 from .. import _hip, hmm_kernels as hk, kernels
@@ -603,6 +604,28 @@ class HMM(DiscreteLatentModel):
         utt, frame = hk.log_evidence(batch, hk.gather(batch, pc_all, scale), per_frame=per_frame)
         return (utt[0], frame) if per_frame else utt[0]
 
+    def arc_posteriors(self, data, arc_cat, init_cat, n_cat, inference_graph=None, scale=1.,
+                       per_frame=True):
+        '''The posteriors of the graph's arcs folded into `n_cat` categories
+        (`hmm_kernels.arc_posteriors`): with `per_frame` a [T, n_cat] tensor on the device whose
+        row t >= 1 holds, per category, the sum of P(s_{t-1} = i, s_t = j | x) over the arcs
+        i -> j of that category and whose row 0 holds gamma_0 by `init_cat`; without it their
+        sum over the frames, [n_cat] float64.  `arc_cat` follows `graph.out_arcs()`, `init_cat`
+        the graph's states; entries are in [0, n_cat) or -1 (count nothing).  Not in the
+        reference.  Otherwise as `decode`.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        src, _ = graph.out_arcs()
+        cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
+                                       per_frame, not per_frame)
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        frame, utt = hk.arc_posteriors(batch, hk.gather(batch, pc_all, scale), *cats, n_cat,
+                                       per_frame=per_frame, per_utt=not per_frame)
+        return frame if per_frame else utt[0]
+
     def posteriors(self, data, inference_graph=None, scale=1.0):
         'State posteriors; `scale` multiplies the statistics (hmm.py:116-121).'
         graph = self.graph if inference_graph is None else inference_graph
@@ -615,8 +638,45 @@ class HMM(DiscreteLatentModel):
         return gamma.view(len(stats), -1)
 
 
+def unit_start_categories(graph, start_pdf, end_pdf):
+    '''(arc_cat, init_cat), int32 host arrays over `graph.out_arcs()` and the graph's states, of
+    the unit-start posteriors, the units numbered in `start_pdf` order: an arc i -> j with
+    i != j whose destination's pdf id is `start_pdf[u]` has category u, every other arc -1;
+    state j has the category of the unit whose pdf ids `start_pdf[u] .. end_pdf[u]` (the unit's
+    first and LAST pdf) hold its own, -1 when there is none.  Works on the model's graph and on
+    alignment graphs (a unit that is repeated in a transcription is one category).'''
+    pdf = np.arange(graph.n_states, dtype=np.int64) if graph.pdf_id_mapping is None else \
+        np.asarray([int(i) for i in graph.pdf_id_mapping], dtype=np.int64)
+    src, dst = graph.out_arcs()
+    firsts = np.asarray([int(start_pdf[u]) for u in start_pdf], dtype=np.int64)
+    lasts = np.asarray([int(end_pdf[u]) for u in start_pdf], dtype=np.int64)
+    top = int(max(pdf.max(initial=0), lasts.max(initial=0))) + 1
+    unit_of_first = np.full(top, -1, dtype=np.int32)
+    unit_of_first[firsts] = np.arange(len(firsts), dtype=np.int32)
+    unit_of_pdf = np.full(top, -1, dtype=np.int32)
+    for u, (a, b) in enumerate(zip(firsts, lasts)):
+        unit_of_pdf[a:b + 1] = u
+    arc_cat = np.where(np.asarray(src) != np.asarray(dst), unit_of_first[pdf[dst]], -1)
+    return arc_cat.astype(np.int32), unit_of_pdf[pdf].astype(np.int32)
+
+
+def _unit_starts(model, data, inference_graph=None, scale=1.):
+    '''Unit-start posteriors [T, n_units] on the device, the units in `start_pdf` order: entry
+    (t, u) is the probability that unit u BEGINS at frame t -- for t >= 1 that a path enters
+    the unit's first state from another state, for t = 0 that it starts inside the unit.
+    `.sum(1)` is the boundary posterior of a frame, `.sum(0)` the expected number of
+    occurrences of every unit (the soft counterparts of `decode`'s boundaries and unit counts).
+    A unit that can be entered at a state other than its first is not covered: such entries are
+    not counted.  Otherwise as `decode`.'''
+    graph = model.graph if inference_graph is None else inference_graph
+    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+    return model.arc_posteriors(data, arc_cat, init_cat, len(model.start_pdf),
+                                inference_graph=inference_graph, scale=scale)
+
+
 class PhoneLoop(HMM):
     'Phone-loop HMM with a prior over the phone (unigram) weights.'
+    unit_starts = _unit_starts
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
@@ -792,6 +852,7 @@ class BigramPhoneLoop(HMM):
     (`beer_hmm_posteriors_bigram`, csrc/hmm_bigram.hip) and counts the block's
     transition posteriors only -- no first-frame term, unlike the unigram loop
     (phoneloop.py:174-186).'''
+    unit_starts = _unit_starts
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,

@@ -1028,6 +1028,99 @@ int beer_hmm_log_evidence(int dtype, const beer_batch* batch_h, const void* pc_l
 #define BEER_EVIDENCE_SPL(route) ((route) & 0xF)
 int beer_hmm_evidence_route(int dtype, const beer_batch* batch_h);
 
+/* The categories of beer_hmm_arc_posteriors: device arrays over the graphs of the batch, graph g
+ * of `beer_batch.graphs` at its own offsets:
+ *   arc_cat    category of every arc in the graph's out-CSR order over the FULL CSR (by source,
+ *              destinations ascending: `out_ptr` / `out_dst`; hub and bigram arcs are explicit in
+ *              it, as beer_hmm_sample_paths and beer_hmm_log_evidence read them): arc a of graph g
+ *              at arc_cat[arc_off[g] + a]
+ *   init_cat   category of every state's posterior at the FIRST frame: state j of graph g at
+ *              init_cat[state_off[g] + j]
+ * Every entry lies in [0, n_cat) or is -1, "count nothing"; the caller answers for that range
+ * (an entry >= n_cat writes out of bounds).  Not beer_cat_map, which describes the low-degree
+ * image and counts the LAST frame. */
+typedef struct {
+    const int32_t* arc_cat;
+    const int32_t* init_cat;
+    const int64_t* arc_off;    /* [n_graphs] */
+    const int64_t* state_off;  /* [n_graphs] */
+} beer_arc_map;
+
+/* Arc posteriors by category: forward-backward over a ragged batch, every arc's posterior at
+ * every frame folded into the caller's categories and kept per frame, summed per utterance, or
+ * both.  One launch, one workgroup per utterance.
+ *   pc_llhs    packed per-state log-likelihoods, as for beer_hmm_viterbi (read only)
+ *   map        the categories (above); n_cat >= 1 their number
+ *   ws         caller-provided fp64 scratch of n_frames + n_elems +
+ *              beer_hmm_arcs_scratch_doubles() doubles (n_elems: the elements of pc_llhs).  On
+ *              return ws[frame_off[u] + t] = c_t, the normalisers of beer_hmm_log_evidence, and
+ *              ws[n_frames + llh_off[u] + t*S + j] = â_t(j), its normalised forward values in
+ *              log space (-inf: unreachable), up to the frame at which an utterance died
+ *   frame_out  nullable, [n_frames, n_cat] of dtype, written (=), frame index as in frame_off
+ *   utt_out    nullable, [nutt, n_cat] fp64 whatever the dtype, written (=)
+ * Definition.  For utterance u of T frames, gamma and xi the exact posteriors under pc_llhs and
+ * the graph's init / arc / final weights (the recursion beer_hmm_log_evidence documents, and its
+ * backward counterpart):
+ *   frame_out[frame_off[u], c]     = sum over the states j with init_cat[j] = c of gamma_0(j)
+ *   frame_out[frame_off[u] + t, c] = sum over the arcs e = (i -> j) with arc_cat[e] = c of
+ *                                    P(s_{t-1} = i, s_t = j | x),              t = 1 .. T - 1
+ *   utt_out[u, c] = sum_t of those rows
+ * Row t says how frame t was entered: a row sums to 1 when no category is -1.  With
+ * arc_cat[e] = dst(e), init_cat[j] = j, n_cat = S the rows are gamma; with one category per arc
+ * and init_cat = -1 they are the sparse per-frame xi.
+ * Arithmetic.  Maxima, differences, sums, the trellis and the bins are fp64; exp / log are in
+ * the model's precision.  The backward pass walks the out-row of every source once per frame:
+ * an arc's posterior is exp(â_{t-1}(i) + w_ij + l_t(j) + b_t(j) - c_t), one exponential per arc
+ * and frame, the sum over the row is gamma_{t-1}(i) and b_{t-1}(i) = ln gamma_{t-1}(i) -
+ * â_{t-1}(i) after the row sums have been normalised to 1 (they are 1 but for rounding).  Bins
+ * are summed with atomic adds, whose order is not fixed: the last bits can differ between runs.
+ * Edges.  -inf log-likelihoods and unreachable states are legal.  An utterance whose evidence is
+ * -inf (a frame with nothing reachable, an unreachable final) gets zeros in all its rows and in
+ * utt_out.  Inputs without NaN give no NaN.  T = 1 is legal (the init row alone); an utterance of
+ * no frames writes nothing to frame_out and zeros to utt_out.  pc_llhs is not modified.
+ * EINVAL, checked before anything is launched: where beer_hmm_sample_paths refuses the batch (a
+ * dtype other than BEER_F32 / BEER_F64, more than 32767 states, a graph whose two fp64 rows plus
+ * 128 bytes do not fit a CU's 160 KiB of LDS); n_cat < 1; a NULL map or map member; frame_out
+ * and utt_out both NULL; with utterances in the batch a NULL pc_llhs or ws.  n_cat has no upper
+ * limit: bins that do not fit LDS are the output rows themselves. */
+int beer_hmm_arc_posteriors(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                            const beer_arc_map* map, int n_cat, double* ws, void* frame_out,
+                            double* utt_out, void* stream);
+
+/* Doubles `ws` of beer_hmm_arc_posteriors must hold BESIDES one per frame (the normalisers) and
+ * one per element of pc_llhs (the trellis), which the host-side descriptor does not know: 0 for
+ * the one form there is, and for a batch the launch refuses. */
+size_t beer_hmm_arcs_scratch_doubles(int dtype, const beer_batch* batch_h);
+
+/* The form beer_hmm_arc_posteriors picks (host only: it reads max_states and max_arcs and
+ * launches nothing), built from the launcher's own plan; `want_frames` != 0: frame_out is
+ * given.  With S = max_states, A = max_arcs, w = 4 / 8 bytes of the dtype, rows = 16 S + 128
+ * bytes (two fp64 rows and the reduction scratch), arcs = 4 (S + 2 + 2 A) + w (A + 1) bytes (the
+ * out-CSR of the largest graph with its categories; the in-CSR of the forward pass is staged in
+ * the same place first); a bin is 8 bytes:
+ *   BEER_ARCS_BLOCK        one workgroup of 256 threads per utterance, a thread per state,
+ *                          strided beyond (the only family)
+ *   BEER_ARCS_ARCS_LDS     the arc lists and categories are kept in LDS: rows + arcs <= 64 KiB;
+ *                          else they are read from global memory
+ *   BEER_ARCS_FRAME_LDS    a frame's bins are fp64 in LDS, summed with LDS atomic adds and
+ *                          written as a row once per frame: want_frames, n_cat <= 1024 and
+ *                          rows <= 96 KiB (6136 states); else (with want_frames) the rows of
+ *                          frame_out are zeroed and take global atomic adds in the dtype
+ *   BEER_ARCS_UTT_LDS      the utterance's bins, when utt_out is given, are fp64 in LDS:
+ *                          n_cat <= 4096 and rows <= 96 KiB; else the row of utt_out is zeroed
+ *                          and added to in place.  With BEER_ARCS_FRAME_LDS the thread that
+ *                          writes bin c of a row adds it to bin c of the utterance; without it
+ *                          every arc's posterior is a second atomic add
+ * (the launch takes at most 64 + 8 + 32 KiB of LDS with the arcs in it, 96 + 8 + 32 KiB without).
+ * BEER_ARCS_FAMILY(route) is the family alone.  BEER_EINVAL exactly where
+ * beer_hmm_arc_posteriors refuses the batch and n_cat. */
+#define BEER_ARCS_BLOCK 0x1000
+#define BEER_ARCS_ARCS_LDS 0x100
+#define BEER_ARCS_FRAME_LDS 0x200
+#define BEER_ARCS_UTT_LDS 0x400
+#define BEER_ARCS_FAMILY(route) ((route) & 0xF000)
+int beer_hmm_arcs_route(int dtype, const beer_batch* batch_h, int n_cat, int want_frames);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
