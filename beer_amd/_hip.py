@@ -186,6 +186,20 @@ def evidence_spl(route):
     return route & 0xF
 
 
+# BEER_NBEST_* of include/beer_hip.h: the largest k and what `beer_hmm_nbest_route` returns
+NBEST_MAX, NBEST_ARCS_LDS = 16, 0x100
+
+
+def nbest_chunk(route):
+    'BEER_NBEST_CHUNK: the frames of back-pointers the back-trace stages into LDS at a time.'
+    return route & 0xFF
+
+
+def nbest_list(k):
+    'BEER_NBEST_LIST: the list entries a thread keeps in registers for this k.'
+    return 1 if k <= 1 else (2 if k <= 2 else (4 if k <= 4 else (8 if k <= 8 else 16)))
+
+
 # BEER_ARCS_* of include/beer_hip.h: what `beer_hmm_arcs_route` returns
 ARCS_BLOCK, ARCS_ARCS_LDS, ARCS_FRAME_LDS, ARCS_UTT_LDS = 0x1000, 0x100, 0x200, 0x400
 
@@ -371,6 +385,8 @@ SIGNATURES = {
                                    c_p, c_p, c_i, c_p, c_p],
     'beer_hmm_bigram_route': [c_i, c_p, ctypes.c_int32, ctypes.c_int32],  # (host only: no stream)
     'beer_hmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_p],
+    'beer_hmm_viterbi_nbest': [c_i, c_p, c_p, ctypes.c_int32, c_p, c_p, c_p, c_i, c_p],
+    'beer_hmm_nbest_route': [c_i, c_p, ctypes.c_int32],            # (host only: no stream)
     'beer_hmm_sample_paths': [c_i, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_i, c_p],
     'beer_hmm_sample_route': [c_i, c_p, ctypes.c_int32],           # (host only: no stream)
     'beer_hmm_log_evidence': [c_i, c_p, c_p, c_p, c_p, c_p],

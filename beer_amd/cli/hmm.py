@@ -13,6 +13,7 @@ import torch
 import yaml
 
 import beer_amd as beer
+from beer_amd import _hip
 from . import compat
 
 # ---------------------------------------------------------------------------
@@ -568,18 +569,75 @@ class decode:
                                  'utterance, as "<uttid>-<k>", instead of the most likely one')
         parser.add_argument('--seed', type=int, default=0,
                             help='seed of the random draws (with --nsamples)')
+        parser.add_argument('--nbest', type=int, default=None,
+                            help='print the N best STATE paths per utterance, best first, as '
+                                 '"<uttid>-<r>" (N <= 16).  They are paths over the states: many '
+                                 'of them differ only by a boundary frame and spell the same '
+                                 'units (see --distinct)')
+        parser.add_argument('--scores', default=None,
+                            help='with --nbest: write "<uttid>-<r> <score>" lines to this file')
+        parser.add_argument('--distinct', action='store_true',
+                            help='with --nbest: among the N state paths keep the best-scoring '
+                                 'one of each unit sequence and renumber (may print fewer than N)')
         parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
         parser.add_argument('-u', '--utts', help='utterances to decode ("-" for stdin)')
         parser.add_argument('model', help='hmm based model')
         parser.add_argument('dataset', help='data set')
 
     @staticmethod
+    def check(args):
+        'The option errors, raised before a model or a data set is read.'
+        if args.nbest is not None:
+            if args.nsamples is not None:
+                raise SystemExit('--nbest and --nsamples exclude each other')
+            if not 1 <= args.nbest <= _hip.NBEST_MAX:
+                raise SystemExit(f'--nbest: 1 .. {_hip.NBEST_MAX}')
+        elif args.scores is not None or args.distinct:
+            raise SystemExit('--scores and --distinct go with --nbest')
+
+    @staticmethod
+    def nbest_lines(uttid, paths, scores, start_pdf, per_frame=False, distinct=False):
+        '''The lines of one utterance under --nbest: [(label, units, score)], best first.  Ranks
+        without a path are skipped; `distinct` keeps the first (best) path of every unit
+        sequence and renumbers.'''
+        out, seen = [], set()
+        for path, value in zip(np.asarray(paths), np.asarray(scores, dtype=np.float64)):
+            if path.size and path[0] < 0:
+                continue
+            if distinct:
+                units = tuple(phones_of_path(path, start_pdf))
+                if units in seen:
+                    continue
+                seen.add(units)
+            phones = phones_of_path(path, start_pdf, per_frame)
+            out.append((f'{uttid}-{len(out) + 1}', phones, float(value)))
+        return out
+
+    @staticmethod
     def main(args, logger):
+        decode.check(args)
         model = _load(args.model).to(_device())
         dataset = _load(args.dataset)
         alis = _load_alis(args.alis)
         feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
         use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        if args.nbest is not None:
+            paths, scores = beer.decode_nbest_batch(
+                model, feats, args.nbest, inference_graphs=use, scale=args.acoustic_scale) \
+                if kept else ([], np.zeros((0, args.nbest)))
+            scores = scores.cpu().numpy() if kept else scores
+            score_lines, n = [], 0
+            for uttid, p, s in zip(kept, paths, scores):
+                for label, phones, value in decode.nbest_lines(
+                        uttid, p.cpu().numpy(), s, model.start_pdf, args.per_frame, args.distinct):
+                    print(label, ' '.join(phones))
+                    score_lines.append(f'{label} {value:.6f}\n')
+                    n += 1
+            if args.scores is not None:
+                with open(args.scores, 'w') as f:
+                    f.writelines(score_lines)
+            logger.info(f'successfully decoded {n} paths of {len(kept)} utterances.')
+            return
         if args.nsamples is not None:
             if args.nsamples < 1:
                 raise SystemExit('--nsamples: at least 1')

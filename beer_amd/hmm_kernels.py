@@ -15,7 +15,7 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
            'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms',
            'log_evidence', 'evidence_route', 'arc_posteriors', 'arcs_route',
-           'check_arc_categories']
+           'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest']
 
 
 class HmmBatch:
@@ -505,6 +505,45 @@ def viterbi(batch, pc_llhs, map_pdf=False):
     _hip.call('beer_hmm_viterbi', _hip.dtype_code(batch.dtype), batch.ref(),
               _hip.ptr(pc_llhs), _hip.ptr(bt), _hip.ptr(path), 1 if map_pdf else 0)
     return path
+
+
+def check_nbest(k, what):
+    'k of an n-best search, checked on the host before any device work.'
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f'{what}: k is an integer, not {k!r}')
+    if not 1 <= k <= _hip.NBEST_MAX:
+        raise ValueError(f'{what}: k = {k} is outside 1 .. {_hip.NBEST_MAX}')
+    return int(k)
+
+
+def nbest_route(batch, k):
+    '''beer_hmm_nbest_route: the form `viterbi_nbest` runs on (the frames of back-pointers the
+    back-trace stages at a time, arcs in LDS or not); HipInvalid where it refuses.'''
+    k = check_nbest(k, 'nbest_route')
+    route = _hip.lib().beer_hmm_nbest_route(_hip.dtype_code(batch.dtype), batch.ref(), k)
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'viterbi_nbest: {k} paths on graphs of up to {batch.struct.max_states} states: at '
+            'most 32767 states, and two score columns [S][k] with two frames of back-pointers '
+            "[S][k] in the CU's 160 KB of LDS")
+    return route
+
+
+def viterbi_nbest(batch, pc_llhs, k, map_pdf=False):
+    '''The `k` best state paths of every utterance and their scores (`beer_hmm_viterbi_nbest`):
+    (paths int64 [k, n_frames] -- state indices, or pdf ids with `map_pdf` --, scores float64
+    [nutt, k]) on the device, best first.  Ranks beyond the number of finite-score paths of an
+    utterance have the score -inf and a path of -1.'''
+    k = check_nbest(k, 'viterbi_nbest')
+    nbest_route(batch, k)
+    dev = batch.device
+    bt = torch.empty(k * batch.n_elems, dtype=torch.int32, device=dev)
+    paths = torch.empty(k, batch.n_frames, dtype=torch.int64, device=dev)
+    scores = torch.empty(batch.nutt, k, dtype=torch.float64, device=dev)
+    _hip.call('beer_hmm_viterbi_nbest', _hip.dtype_code(batch.dtype), batch.ref(),
+              _hip.ptr(pc_llhs), k, _hip.ptr(bt), _hip.ptr(paths), _hip.ptr(scores),
+              1 if map_pdf else 0)
+    return paths, scores
 
 
 def check_sample(sample, n_frames, viterbi=False, state_path=None):

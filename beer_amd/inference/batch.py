@@ -32,7 +32,8 @@ from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
-           'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch', 'ShardStatics']
+           'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch', 'ShardStatics',
+           'decode_nbest_batch']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
 # three sub-batches are in flight, so a sub-batch may take an eighth of what is free on
@@ -673,6 +674,25 @@ def sample_paths_batch(model, utterances, inference_graphs=None, scale=1., nsamp
                         lambda batch, pc_llhs: hk.sample_paths(
                             batch, pc_llhs, nsamples=nsamples, generator=generator, map_pdf=True),
                         trellis_bytes=8)
+
+
+def decode_nbest_batch(model, utterances, k, inference_graphs=None, scale=1.,
+                       max_frames=1 << 20):
+    '''The `k` best state paths of every utterance of a shard as pdf ids, and their scores
+    (`HMM.decode_nbest`, batched): (list of int64 [k, T_u] tensors, float64 [nutt, k]) on the
+    device, best first; ranks without a path of finite score hold -1 and -inf.'''
+    k = hk.check_nbest(k, 'decode_nbest_batch')
+    scores = []
+
+    def search(batch, pc_llhs):
+        paths, batch_scores = hk.viterbi_nbest(batch, pc_llhs, k, map_pdf=True)
+        scores.append(batch_scores)
+        return paths
+
+    # decode_batch's scratch with k back-pointers per state, and the k paths of a frame besides
+    paths = _paths_batch(model, utterances, inference_graphs, scale, max_frames, 8 * k, search,
+                         trellis_bytes=4 * k)
+    return paths, torch.cat(scores)
 
 
 def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_frame=False,

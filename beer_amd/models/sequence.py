@@ -576,6 +576,24 @@ class HMM(DiscreteLatentModel):
         pc_llhs = hk.gather(batch, pc_all, scale)
         return hk.viterbi(batch, pc_llhs, map_pdf=True).cpu()
 
+    def decode_nbest(self, data, k, inference_graph=None, scale=1.):
+        '''The `k` best STATE paths mapped to pdf ids and their scores, best first: (LongTensor
+        [k, T], float64 [k]) on the host.  The score of a path is the sum of its (scaled)
+        log-likelihoods and the graph's initial, arc and final log-weights, in the model's
+        precision; row 0 is `decode`'s path whenever its score is finite.  Ranks beyond the
+        number of paths of finite score have the score -inf and a row of -1.  Not in the
+        reference.  Otherwise as `decode`.'''
+        k = hk.check_nbest(k, 'decode_nbest')
+        graph = self.graph if inference_graph is None else inference_graph
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        pc_llhs = hk.gather(batch, pc_all, scale)
+        paths, scores = hk.viterbi_nbest(batch, pc_llhs, k, map_pdf=True)
+        return paths.cpu(), scores[0].cpu()
+
     def sample_path(self, data, inference_graph=None, scale=1., nsamples=1, generator=None):
         '''`nsamples` state paths drawn from the posterior, mapped to pdf ids: LongTensor
         [nsamples, T] on the host.  `generator`: a device torch.Generator for the uniforms

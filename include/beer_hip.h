@@ -921,6 +921,61 @@ int beer_hmm_trans_posteriors(int dtype, int64_t T, int S, const double* alpha,
 int beer_hmm_viterbi(int dtype, const beer_batch* batch_h, const void* pc_llhs,
                      int32_t* bt_ws, int64_t* path, int map_pdf, void* stream);
 
+/* N-best Viterbi: the k best state paths of every utterance, with their scores.
+ *   pc_llhs    packed per-state log-likelihoods, as for beer_hmm_viterbi (read only)
+ *   k          1 <= k <= BEER_NBEST_MAX
+ *   bt_ws      caller-provided int32 scratch, k * n_elems of them (n_elems: the elements of
+ *              pc_llhs); its content is opaque
+ *   paths      [k, n_frames] int64, frame index as in frame_off: row r holds the r-th best path of
+ *              every utterance -- state indices, or with `map_pdf` != 0 pdf ids
+ *   scores     [nutt, k] fp64 whatever the dtype: the value computed in the dtype, widened exactly
+ * Definition.  For an utterance of T frames on a graph of S states a path is p_0 .. p_{T-1}.  All
+ * arithmetic is done in the dtype of pc_llhs, in exactly the order beer_hmm_viterbi uses:
+ *   omega_0[j] = llh[0,j] + init[j]
+ *   candidate c = omega_{t-1}[i][r] + w_ij,  then omega_t[j][q] = llh[t,j] + c
+ *   final candidate omega_{T-1}[j][r] + final[j]
+ * At every cell (t, j) the k best candidates over (source i, rank r) are kept, at the end the k
+ * best over (state j, rank r).  Order of the candidates: the larger score first; on equal scores
+ * the smaller source (or final) state first, then the smaller rank.  Should a row of the in-CSR
+ * hold parallel arcs i -> j, the arc's position in the row decides before the rank (rows are
+ * sorted by source, so the position refines the source order).  In exact arithmetic this orders
+ * the paths by (score descending, then the lexicographic order of the REVERSED path); the k
+ * results are pairwise distinct paths by construction.
+ * A candidate of score -inf is not a path.  Where fewer than k paths of finite score exist the
+ * remaining ranks get the score -inf and path rows filled with -1, under `map_pdf` too.  An
+ * utterance of no frames gets k scores of -inf.
+ * Whenever the best score is finite, rank 0 is the path beer_hmm_viterbi returns, element for
+ * element.  When no path is finite the two differ: beer_hmm_viterbi returns the path of its
+ * default arguments (source 0 wherever nothing is reachable), this entry only -inf and -1.  NaN
+ * inputs are undefined, as for beer_hmm_viterbi.
+ * EINVAL, checked before anything is launched: k outside 1 .. BEER_NBEST_MAX, a dtype other than
+ * BEER_F32 / BEER_F64, a NULL batch, more than 32767 states (a back-pointer packs
+ * source << 4 | rank), an LDS need (below) beyond a CU's 160 KiB; a NULL pointer argument with a
+ * batch that has utterances. */
+#define BEER_NBEST_MAX 16
+int beer_hmm_viterbi_nbest(int dtype, const beer_batch* batch_h, const void* pc_llhs, int32_t k,
+                           int32_t* bt_ws, int64_t* paths, double* scores, int map_pdf,
+                           void* stream);
+
+/* The form beer_hmm_viterbi_nbest picks for this batch and k (host only: it reads max_states and
+ * max_arcs and launches nothing), built from the launcher's own plan:
+ *   chunk | BEER_NBEST_ARCS_LDS
+ * One workgroup per utterance, a thread per state (min(256, S rounded up to 64) threads, strided
+ * beyond 256 states); a thread keeps BEER_NBEST_LIST(k) list entries in registers.  With
+ * S = max_states, A = max_arcs, w = 4 / 8 bytes of the dtype and row = 4 S k bytes (the
+ * back-pointers of one frame):
+ *   chunk   frames of back-pointers the back-trace stages into LDS at a time: 32 when 32 rows
+ *           take at most 16 KiB (S k <= 128), else 8 when 8 rows do (S k <= 512), else 2
+ *   base  = 2 S k w + 64 + chunk * row    two score columns [S][k], the k walks, the chunk
+ *   BEER_NBEST_ARCS_LDS  the arc lists are kept in LDS: base + 4 (S + 2 + A) + w A <= 64 KiB;
+ *           else they are read from global memory
+ * BEER_EINVAL exactly where beer_hmm_viterbi_nbest refuses: the argument errors above, and
+ * base > 160 KiB.  BEER_NBEST_CHUNK(route) is the chunk alone. */
+#define BEER_NBEST_ARCS_LDS 0x100
+#define BEER_NBEST_CHUNK(route) ((route) & 0xFF)
+#define BEER_NBEST_LIST(k) ((k) <= 1 ? 1 : ((k) <= 2 ? 2 : ((k) <= 4 ? 4 : ((k) <= 8 ? 8 : 16))))
+int beer_hmm_nbest_route(int dtype, const beer_batch* batch_h, int32_t k);
+
 /* State paths drawn from the posterior p(s_0..s_{T-1} | x) of every utterance: forward
  * filtering, backward sampling, `nsamples` >= 1 independent paths per utterance from one
  * forward pass (two launches).
