@@ -209,6 +209,15 @@ def arcs_family(route):
     return route & 0xF000
 
 
+# BEER_MAXMARG_* of include/beer_hip.h: what `beer_hmm_maxmarg_route` returns
+MAXMARG_BLOCK, MAXMARG_ARCS_LDS, MAXMARG_BINS_LDS = 0x1000, 0x100, 0x200
+
+
+def maxmarg_family(route):
+    'BEER_MAXMARG_FAMILY: the kernel form of a `beer_hmm_maxmarg_route` value.'
+    return route & 0xF000
+
+
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
 ESTEP_PLAIN, ESTEP_PACKED, ESTEP_IMAGE = 0, 1, 2
 ARG_PC_LLH, ARG_LOG_NORM, ARG_RESPS, ARG_LLH_SUM, ARG_LABELS, ARG_SCALED, ARG_LOG_WEIGHTS = \
@@ -393,6 +402,8 @@ SIGNATURES = {
     'beer_hmm_evidence_route': [c_i, c_p],                         # (host only: no stream)
     'beer_hmm_arc_posteriors': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
     'beer_hmm_arcs_route': [c_i, c_p, c_i, c_i],                   # (host only: no stream)
+    'beer_hmm_max_marginals': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_maxmarg_route': [c_i, c_p, c_i, c_i, c_i, c_i],      # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],
@@ -443,6 +454,7 @@ SIZE_QUERIES = {
     'beer_mixtureset_accumulate_packed_workspace_bytes': [c_i, c_l, c_i, c_i, c_i],
     'beer_hmm_fb_scratch_doubles': [c_i, c_p, c_i],
     'beer_hmm_arcs_scratch_doubles': [c_i, c_p],
+    'beer_hmm_maxmarg_scratch_doubles': [c_i, c_p],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
 }
 

@@ -731,6 +731,56 @@ class boundaries:
                     f'{total / max(len(kept), 1):.2f} expected units per utterance.')
 
 
+def lattice_entries(margins, beam):
+    '''(frame int32, unit int32, margin float64) of the entries of a [T, n_units] array of
+    unit-start max-marginals that lie within `beam` of the best path, sorted by frame and then
+    by unit.'''
+    margins = np.asarray(margins, dtype=np.float64)
+    frame, unit = np.nonzero(margins >= -beam)             # (row-major: by frame, then by unit)
+    return frame.astype(np.int32), unit.astype(np.int32), margins[frame, unit]
+
+
+class lattice:
+    '''write the unit-start lattice of all the utterances of a dataset, "<outdir>/<uttid>.npz":
+    every (frame, unit) at which the unit can begin on a path whose score is within --beam of the
+    best path's, with the score lost ("margin", 0 on the Viterbi segmentation), the Viterbi
+    "score" and the "units"; prints "<uttid> <score> <n_entries> <n_frames>"'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
+        parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('-u', '--utts', help='utterances to process ("-" for stdin)')
+        parser.add_argument('--beam', default=10., type=float,
+                            help='keep what is within this score of the best path (default 10)')
+        parser.add_argument('model', help='phone-loop model')
+        parser.add_argument('dataset', help='data set')
+        parser.add_argument('outdir', help='output directory')
+
+    @staticmethod
+    def main(args, logger):
+        if not (args.beam >= 0. and np.isfinite(args.beam)):
+            raise SystemExit(f'--beam: a finite number >= 0, not {args.beam}')
+        model = _load(args.model).to(_device())
+        dataset = _load(args.dataset)
+        alis = _load_alis(args.alis)
+        feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
+        use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        os.makedirs(args.outdir, exist_ok=True)
+        scores, margins = beer.unit_start_margins_batch(
+            model, feats, inference_graphs=use, scale=args.acoustic_scale) if kept else ([], [])
+        units = np.asarray([str(u) for u in model.start_pdf])
+        total = 0
+        for uttid, score, margin in zip(kept, scores.cpu().tolist() if kept else [], margins):
+            frame, unit, value = lattice_entries(margin.cpu().numpy(), args.beam)
+            np.savez(os.path.join(args.outdir, f'{uttid}.npz'), frame=frame, unit=unit,
+                     margin=value, score=np.float64(score), units=units)
+            print(uttid, '%.6f' % score, len(frame), len(margin))
+            total += len(frame)
+        logger.info(f'wrote the unit-start lattices of {len(kept)} utterances within a beam of '
+                    f'{args.beam:g}: {total / max(len(kept), 1):.1f} entries per utterance.')
+
+
 class posteriors:
     'state / phone posteriors of all the utterances of a dataset'
     EPS = 1e-5
@@ -770,4 +820,5 @@ class posteriors:
 
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
-            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, boundaries]
+            mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, lattice,
+            boundaries]

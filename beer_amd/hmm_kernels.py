@@ -15,7 +15,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'posteriors_bigram', 'lowdeg_arcs', 'forward_backward_counts', 'path_counts',
            'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms',
            'log_evidence', 'evidence_route', 'arc_posteriors', 'arcs_route',
-           'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest']
+           'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest',
+           'max_marginals', 'maxmarg_route']
 
 
 class HmmBatch:
@@ -728,6 +729,74 @@ def arc_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, per_frame=True, per
     _hip.call('beer_hmm_arc_posteriors', dcode, batch.ref(), _hip.ptr(pc_llhs),
               ctypes.byref(amap), n_cat, _hip.ptr(ws), _hip.ptr(frame), _hip.ptr(utt))
     return frame, utt
+
+
+def maxmarg_route(batch, n_cat=0, states=True, per_frame=False, per_utt=False):
+    '''beer_hmm_maxmarg_route: the form `max_marginals` runs on (arcs in LDS or not, the bins in
+    LDS or in the output rows); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_maxmarg_route(_hip.dtype_code(batch.dtype), batch.ref(),
+                                              int(n_cat), 1 if states else 0,
+                                              1 if per_frame else 0, 1 if per_utt else 0)
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'max_marginals: {n_cat} categories on graphs of up to {batch.struct.max_states} '
+            'states: at least one output, at least one category for the outputs by category, '
+            "and two fp64 rows in the CU's 160 KB of LDS (about 10000 states)")
+    return route
+
+
+def max_marginals(batch, pc_llhs, arc_cat=None, init_cat=None, n_cat=0, states=True,
+                  per_frame=False, per_utt=False):
+    '''(best [nutt] fp64, state [n_elems] of the batch's dtype or None, frame [n_frames, n_cat]
+    of the batch's dtype or None, utt [nutt, n_cat] fp64 or None), on the device: the Viterbi
+    max-marginals (`beer_hmm_max_marginals`).  `best` is the score of the best path; `state`,
+    packed like `pc_llhs`, holds for every frame and state the score of the best path through
+    it minus `best` (0 on the Viterbi path, -inf where no path passes); row t >= 1 of `frame`
+    holds, per category c, the maximum of the same quantity over the arcs i -> j entering frame
+    t with `arc_cat` = c, row 0 that of the states with `init_cat` = c, `utt` the maximum over an
+    utterance's rows; a category with no member holds -inf.  The categories are those of
+    `arc_posteriors` and are needed for `per_frame` / `per_utt` only.  An utterance without a
+    path of finite score has best = -inf and -inf everywhere.'''
+    cats = per_frame or per_utt
+    if not (states or cats):
+        raise ValueError('max_marginals: none of states, per_frame and per_utt is asked for')
+    if cats and (arc_cat is None or init_cat is None):
+        raise ValueError('max_marginals: per_frame / per_utt need arc_cat and init_cat')
+    arcs = inits = None
+    if arc_cat is not None or init_cat is not None:
+        if arc_cat is None or init_cat is None:
+            raise ValueError('max_marginals: arc_cat and init_cat come together')
+        arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat,
+                                           True, False)
+    n_cat = int(n_cat) if arcs is not None else 0
+    dev = batch.device
+    maxmarg_route(batch, n_cat, states, per_frame, per_utt)
+    best = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    state = torch.empty(batch.n_elems, dtype=batch.dtype, device=dev) if states else None
+    frame = torch.empty(batch.n_frames, n_cat, dtype=batch.dtype, device=dev) \
+        if per_frame else None
+    utt = torch.empty(batch.nutt, n_cat, dtype=torch.float64, device=dev) if per_utt else None
+    if batch.nutt == 0:
+        return best, state, frame, utt
+    dcode = _hip.dtype_code(batch.dtype)
+    amap = None
+    if arcs is not None:
+        arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+        state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+        host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+        if arcs.device.type != 'cuda':
+            host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+        if inits.device.type != 'cuda':
+            host['inits'] = inits
+        up = _hip.upload(host, dev)
+        arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+        amap = ctypes.byref(_hip.ArcMap(arcs.data_ptr(), inits.data_ptr(),
+                                        up['arc_off'].data_ptr(), up['state_off'].data_ptr()))
+    extra = _hip.lib().beer_hmm_maxmarg_scratch_doubles(dcode, batch.ref())
+    ws = torch.empty(max(batch.n_elems + extra, 1), dtype=torch.float64, device=dev)
+    _hip.call('beer_hmm_max_marginals', dcode, batch.ref(), _hip.ptr(pc_llhs), amap, n_cat,
+              _hip.ptr(ws), _hip.ptr(state), _hip.ptr(frame), _hip.ptr(utt), _hip.ptr(best))
+    return best, state, frame, utt
 
 
 def path_posteriors(batch, path, want_xi=False):

@@ -32,7 +32,8 @@ from ..stats import FrameStats
 from .objectives import EvidenceLowerBoundInstance
 
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
-           'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch', 'ShardStatics',
+           'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch',
+           'unit_start_margins_batch', 'ShardStatics',
            'decode_nbest_batch']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
@@ -737,7 +738,18 @@ def unit_counts_batch(model, utterances, inference_graphs=None, scale=1., max_fr
                             max_frames, False)
 
 
-def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame):
+def unit_start_margins_batch(model, utterances, inference_graphs=None, scale=1.,
+                             max_frames=1 << 20):
+    '''The Viterbi score and the unit-start max-marginals of every utterance of a shard:
+    (float64 [nutt], list of [T_u, n_units] tensors) on the device, the units in
+    `model.start_pdf` order (`PhoneLoop.unit_start_margins`, batched): entry (t, u) is the score
+    lost against the best path by forcing unit u to begin at frame t.'''
+    return _unit_arcs_batch('unit_start_margins_batch', model, utterances, inference_graphs,
+                            scale, max_frames, True, margins=True)
+
+
+def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame,
+                     margins=False):
     packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
         isinstance(utterances[0], torch.Tensor)
     if not packed:
@@ -758,20 +770,29 @@ def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frame
             cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
         return cats[id(graph)]
 
-    out = []
+    out, bests = [], []
     # decode_batch's scratch with the fp64 trellis in place of the back-pointers; a normaliser
     # and the output row per frame besides (sized for float64)
     row = 8 * n_units if per_frame else 0
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 + row, 8):
         pairs = [categories(g) for g in batch.distinct_graphs]
-        frame, utt = hk.arc_posteriors(batch, pc_llhs, [p[0] for p in pairs],
-                                       [p[1] for p in pairs], n_units, per_frame=per_frame,
-                                       per_utt=not per_frame)
+        if margins:
+            best, _, frame, utt = hk.max_marginals(batch, pc_llhs, [p[0] for p in pairs],
+                                                   [p[1] for p in pairs], n_units, states=False,
+                                                   per_frame=True)
+            bests.append(best)
+        else:
+            frame, utt = hk.arc_posteriors(batch, pc_llhs, [p[0] for p in pairs],
+                                           [p[1] for p in pairs], n_units, per_frame=per_frame,
+                                           per_utt=not per_frame)
         if per_frame:
             out += list(torch.split(frame, run_lengths))
         else:
             out.append(utt)
+    if margins:
+        return (torch.cat(bests) if bests else
+                torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
     if per_frame:
         return out
     return torch.cat(out) if out else \

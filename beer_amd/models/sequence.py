@@ -644,6 +644,43 @@ class HMM(DiscreteLatentModel):
                                        per_frame=per_frame, per_utt=not per_frame)
         return frame if per_frame else utt[0]
 
+    def max_marginals(self, data, inference_graph=None, scale=1.):
+        '''(best, [T, S]) on the device: the score of the Viterbi path (0-d float64) and, for
+        every frame and state, the score of the best path through it minus `best`
+        (`hmm_kernels.max_marginals`): 0 along `decode`'s path, negative off it, -inf where no
+        path passes.  Not in the reference.  Otherwise as `decode`.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        best, state, _, _ = hk.max_marginals(batch, hk.gather(batch, pc_all, scale))
+        return best[0], state.view(len(stats), -1)
+
+    def arc_max_marginals(self, data, arc_cat, init_cat, n_cat, inference_graph=None, scale=1.,
+                          per_frame=True):
+        '''(best, max-marginals of the graph's arcs folded into `n_cat` categories), on the
+        device (`hmm_kernels.max_marginals`): with `per_frame` a [T, n_cat] tensor whose row
+        t >= 1 holds, per category, the score of the best path that enters frame t on an arc of
+        that category, minus `best`, and whose row 0 holds the same for the states by
+        `init_cat`; without it their maximum over the frames, [n_cat] float64.  -inf: no such
+        path.  The categories are those of `arc_posteriors`.  Not in the reference.  Otherwise
+        as `decode`.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        src, _ = graph.out_arcs()
+        cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
+                                       per_frame, not per_frame)
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emissions().expected_log_likelihood(stats)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        best, _, frame, utt = hk.max_marginals(batch, hk.gather(batch, pc_all, scale), *cats,
+                                               n_cat, states=False, per_frame=per_frame,
+                                               per_utt=not per_frame)
+        return best[0], (frame if per_frame else utt[0])
+
     def posteriors(self, data, inference_graph=None, scale=1.0):
         'State posteriors; `scale` multiplies the statistics (hmm.py:116-121).'
         graph = self.graph if inference_graph is None else inference_graph
@@ -692,9 +729,23 @@ def _unit_starts(model, data, inference_graph=None, scale=1.):
                                 inference_graph=inference_graph, scale=scale)
 
 
+def _unit_start_margins(model, data, inference_graph=None, scale=1.):
+    '''(best, [T, n_units]) on the device, the units in `start_pdf` order: the Viterbi score and
+    the unit-start max-marginals -- entry (t, u) is the score lost against the best path by
+    forcing unit u to BEGIN at frame t (for t >= 1: to enter the unit's first state from another
+    state; for t = 0: to start inside the unit).  0 on the Viterbi segmentation, -inf where
+    impossible; everything `>= -beam` is the unit-start lattice of that beam.  The max-product
+    twin of `unit_starts`, with its categories.  Otherwise as `decode`.'''
+    graph = model.graph if inference_graph is None else inference_graph
+    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+    return model.arc_max_marginals(data, arc_cat, init_cat, len(model.start_pdf),
+                                   inference_graph=inference_graph, scale=scale)
+
+
 class PhoneLoop(HMM):
     'Phone-loop HMM with a prior over the phone (unigram) weights.'
     unit_starts = _unit_starts
+    unit_start_margins = _unit_start_margins
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
@@ -871,6 +922,7 @@ class BigramPhoneLoop(HMM):
     transition posteriors only -- no first-frame term, unlike the unigram loop
     (phoneloop.py:174-186).'''
     unit_starts = _unit_starts
+    unit_start_margins = _unit_start_margins
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,

@@ -1176,6 +1176,85 @@ size_t beer_hmm_arcs_scratch_doubles(int dtype, const beer_batch* batch_h);
 #define BEER_ARCS_FAMILY(route) ((route) & 0xF000)
 int beer_hmm_arcs_route(int dtype, const beer_batch* batch_h, int n_cat, int want_frames);
 
+/* Viterbi max-marginals: for every frame and state, and for every arc folded into the caller's
+ * categories, the score of the best path forced through it minus the score of the best path.
+ * The max-product twin of beer_hmm_arc_posteriors: 0 on the Viterbi path, negative off it,
+ * -inf where no path passes.  One launch, one workgroup per utterance, no exponential.
+ *   pc_llhs    packed per-state log-likelihoods, as for beer_hmm_viterbi (read only)
+ *   map        nullable, the categories as beer_hmm_arc_posteriors reads them (beer_arc_map);
+ *              n_cat >= 1 their number.  NULL is legal when frame_out and utt_out are NULL
+ *   ws         caller-provided fp64 scratch of n_elems + beer_hmm_maxmarg_scratch_doubles()
+ *              doubles (n_elems: the elements of pc_llhs); its content on return is unspecified
+ *   state_out  nullable, [n_elems] of dtype, packed like pc_llhs, written (=): mm
+ *   frame_out  nullable, [n_frames, n_cat] of dtype, written (=), frame index as in frame_off
+ *   utt_out    nullable, [nutt, n_cat] fp64 whatever the dtype, written (=)
+ *   best       [nutt] fp64, written (=): the Viterbi score
+ * Definition, over the full CSR (hub and bigram arcs included), l = pc_llhs, init / w / final
+ * the graph's weights, for utterance u of T frames:
+ *   d_0(j)     = l_0(j) + init_j
+ *   d_t(j)     = max_i (d_{t-1}(i) + w_ij) + l_t(j)                      t = 1 .. T-1
+ *   e_{T-1}(j) = final_j
+ *   e_t(i)     = max_j (w_ij + (l_{t+1}(j) + e_{t+1}(j)))                t = T-2 .. 0
+ *   best[u]    = max_j (d_{T-1}(j) + final_j)
+ *   mm_t(j)    = (d_t(j) + e_t(j)) - best[u]                              -> state_out
+ *   am_t(i->j) = (((d_{t-1}(i) + w_ij) + l_t(j)) + e_t(j)) - best[u]     t >= 1
+ *   frame_out[frame_off[u], c]     = max over the states j with init_cat[j] = c of mm_0(j)
+ *   frame_out[frame_off[u] + t, c] = max over the arcs e with arc_cat[e] = c of am_t(e)
+ *   utt_out[u, c] = max over t of those rows: the relative score of the best path that uses
+ *                   category c anywhere
+ * A category with no member at a frame holds -inf.  Arithmetic is fp64 whatever the dtype
+ * (float32 inputs are upcast on load) and the additions are made in exactly the bracketed
+ * order: rounding is monotone, so max_i am_t(i->j) == mm_t(j) bit for bit.  Folding is by
+ * maximum (integer atomic max on order-preserving keys): the outputs are the same bits on every
+ * run.  best and d + e associate the same sums differently: where the sums are not exact, mm on
+ * the best path is 0 only up to that rounding and can be a few ulps of the score ABOVE 0.
+ * Edges.  -inf log-likelihoods and unreachable states are legal and give -inf.  An utterance
+ * with best = -inf gets -inf in all its outputs, never NaN; inputs without NaN give no NaN.
+ * T = 1 is legal.  An utterance of no frames gets best = -inf and utt_out = -inf ("no frame, no
+ * path", as beer_hmm_viterbi_nbest has it) and nothing in the per-frame outputs.  pc_llhs is
+ * not modified; no utterance sees another's values.
+ * EINVAL, checked before anything is launched: where beer_hmm_sample_paths refuses the batch (a
+ * dtype other than BEER_F32 / BEER_F64, more than 32767 states, a graph whose two fp64 rows plus
+ * 128 bytes do not fit a CU's 160 KiB of LDS); n_cat < 1 with a map; a NULL map member;
+ * frame_out or utt_out without a map; all three outputs NULL; with utterances in the batch a
+ * NULL best, pc_llhs or ws.  n_cat has no upper limit. */
+int beer_hmm_max_marginals(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                           const beer_arc_map* map, int n_cat, double* ws, void* state_out,
+                           void* frame_out, double* utt_out, double* best, void* stream);
+
+/* Doubles `ws` of beer_hmm_max_marginals must hold BESIDES one per element of pc_llhs (the
+ * trellis): 0 for the one form there is -- what a thread holds between two frames lives in a
+ * register or in the trellis itself -- and for a batch the launch refuses. */
+size_t beer_hmm_maxmarg_scratch_doubles(int dtype, const beer_batch* batch_h);
+
+/* The form beer_hmm_max_marginals picks (host only: it reads max_states and max_arcs and
+ * launches nothing), built from the launcher's own plan; want_state / want_frames / want_utt
+ * != 0: that output is given.  With S = max_states, A = max_arcs, w = 4 / 8 bytes of the dtype,
+ * cats = want_frames or want_utt, rows = 16 S + 128 bytes (two fp64 rows and the reduction
+ * scratch), arcs = 4 (S + 2 + A) + w (A + 1) bytes, plus 4 A with cats (the out-CSR of the
+ * largest graph, with its categories when they are read; the in-CSR of the forward pass is
+ * staged in the same place first); a bin is 8 bytes:
+ *   BEER_MAXMARG_BLOCK     one workgroup of 256 threads per utterance, a thread per state,
+ *                          strided beyond (the only family)
+ *   BEER_MAXMARG_ARCS_LDS  the arc lists (and categories) are kept in LDS:
+ *                          rows + arcs <= 64 KiB; else they are read from global memory
+ *   BEER_MAXMARG_BINS_LDS  the bins of a frame (with want_frames) and of the utterance (with
+ *                          want_utt) are 64-bit keys in LDS under LDS integer atomic max, a
+ *                          frame's written as a row once per frame by the threads that also
+ *                          own the utterance's: cats, n_cat <= 2048 and rows <= 96 KiB (6136
+ *                          states); else (with cats) the output rows themselves hold keys of
+ *                          their dtype, take global integer atomic max and are decoded in
+ *                          place at the end
+ * (the launch takes at most 64 + 32 KiB of LDS with the arcs in it, 96 + 32 KiB without).
+ * BEER_MAXMARG_FAMILY(route) is the family alone.  BEER_EINVAL where beer_hmm_max_marginals
+ * refuses the batch, all three wants 0, or cats with n_cat < 1. */
+#define BEER_MAXMARG_BLOCK 0x1000
+#define BEER_MAXMARG_ARCS_LDS 0x100
+#define BEER_MAXMARG_BINS_LDS 0x200
+#define BEER_MAXMARG_FAMILY(route) ((route) & 0xF000)
+int beer_hmm_maxmarg_route(int dtype, const beer_batch* batch_h, int n_cat, int want_state,
+                           int want_frames, int want_utt);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
