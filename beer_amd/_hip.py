@@ -138,6 +138,13 @@ class ArcMap(ctypes.Structure):
     _fields_ = [('arc_cat', c_p), ('init_cat', c_p), ('arc_off', c_p), ('state_off', c_p)]
 
 
+class SegMap(ctypes.Structure):
+    'beer_seg_map of include/beer_hip.h.'
+    _fields_ = [('mem_ptr', c_p), ('members', c_p), ('mem_init', c_p), ('in_ptr', c_p),
+                ('in_src', c_p), ('in_arc', c_p), ('ent_ptr', c_p), ('ent_src', c_p),
+                ('ent_arc', c_p), ('max_closure', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class Bigram(ctypes.Structure):
     'beer_bigram of include/beer_hip.h.'
     _fields_ = [('n_states', ctypes.c_int32), ('n_phones', ctypes.c_int32),
@@ -216,6 +223,20 @@ MAXMARG_BLOCK, MAXMARG_ARCS_LDS, MAXMARG_BINS_LDS = 0x1000, 0x100, 0x200
 def maxmarg_family(route):
     'BEER_MAXMARG_FAMILY: the kernel form of a `beer_hmm_maxmarg_route` value.'
     return route & 0xF000
+
+
+# BEER_SEGMENTS_* of include/beer_hip.h: what `beer_hmm_segments_route` returns
+SEGMENTS_BLOCK, SEGMENTS_ARCS_LDS, SEGMENTS_BINS_LDS = 0x1000, 0x100, 0x200
+
+
+def segments_family(route):
+    'BEER_SEGMENTS_FAMILY: the kernel form of a `beer_hmm_segments_route` value.'
+    return route & 0xF000
+
+
+def segments_team(route):
+    'BEER_SEGMENTS_TEAM: the lanes of a team of the expand kernel.'
+    return 1 << (route & 0xF)
 
 
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
@@ -404,6 +425,10 @@ SIGNATURES = {
     'beer_hmm_arcs_route': [c_i, c_p, c_i, c_i],                   # (host only: no stream)
     'beer_hmm_max_marginals': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_maxmarg_route': [c_i, c_p, c_i, c_i, c_i, c_i],      # (host only: no stream)
+    'beer_hmm_segment_trellis': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_segment_margins': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i,
+                                 c_p, c_p],
+    'beer_hmm_segments_route': [c_i, c_p, c_i, c_i],               # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],
@@ -455,6 +480,7 @@ SIZE_QUERIES = {
     'beer_hmm_fb_scratch_doubles': [c_i, c_p, c_i],
     'beer_hmm_arcs_scratch_doubles': [c_i, c_p],
     'beer_hmm_maxmarg_scratch_doubles': [c_i, c_p],
+    'beer_hmm_segments_scratch_doubles': [c_i, c_p],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
 }
 

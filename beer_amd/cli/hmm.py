@@ -744,7 +744,10 @@ class lattice:
     '''write the unit-start lattice of all the utterances of a dataset, "<outdir>/<uttid>.npz":
     every (frame, unit) at which the unit can begin on a path whose score is within --beam of the
     best path's, with the score lost ("margin", 0 on the Viterbi segmentation), the Viterbi
-    "score" and the "units"; prints "<uttid> <score> <n_entries> <n_frames>"'''
+    "score" and the "units"; prints "<uttid> <score> <n_entries> <n_frames>".  --segments also
+    stores the unit segments within the beam, "seg_unit" from frame "seg_start" to frame "seg_end"
+    with the score lost "seg_margin", sorted by (start, unit, end), and appends their number to
+    the printed line'''
 
     @staticmethod
     def setup(parser):
@@ -753,6 +756,10 @@ class lattice:
         parser.add_argument('-u', '--utts', help='utterances to process ("-" for stdin)')
         parser.add_argument('--beam', default=10., type=float,
                             help='keep what is within this score of the best path (default 10)')
+        parser.add_argument('--segments', action='store_true',
+                            help='also store the unit segments (unit, start, end) within the beam')
+        parser.add_argument('--max-dur', default=100, type=int,
+                            help='with --segments: the longest segment, in frames (default 100)')
         parser.add_argument('model', help='phone-loop model')
         parser.add_argument('dataset', help='data set')
         parser.add_argument('outdir', help='output directory')
@@ -761,6 +768,8 @@ class lattice:
     def main(args, logger):
         if not (args.beam >= 0. and np.isfinite(args.beam)):
             raise SystemExit(f'--beam: a finite number >= 0, not {args.beam}')
+        if args.max_dur < 1:
+            raise SystemExit(f'--max-dur: at least 1 frame, not {args.max_dur}')
         model = _load(args.model).to(_device())
         dataset = _load(args.dataset)
         alis = _load_alis(args.alis)
@@ -769,16 +778,28 @@ class lattice:
         os.makedirs(args.outdir, exist_ok=True)
         scores, margins = beer.unit_start_margins_batch(
             model, feats, inference_graphs=use, scale=args.acoustic_scale) if kept else ([], [])
+        segments = beer.unit_segments_batch(
+            model, feats, beam=args.beam, max_dur=args.max_dur, inference_graphs=use,
+            scale=args.acoustic_scale)[1] if kept and args.segments else [None] * len(kept)
         units = np.asarray([str(u) for u in model.start_pdf])
-        total = 0
-        for uttid, score, margin in zip(kept, scores.cpu().tolist() if kept else [], margins):
+        total = n_segments = 0
+        for uttid, score, margin, segs in zip(kept, scores.cpu().tolist() if kept else [], margins,
+                                              segments):
             frame, unit, value = lattice_entries(margin.cpu().numpy(), args.beam)
+            more, tail = {}, ()
+            if segs is not None:
+                more = dict(zip(('seg_start', 'seg_end', 'seg_unit', 'seg_margin'),
+                                (v.cpu().numpy() for v in segs)))
+                tail = (len(more['seg_start']),)
+                n_segments += tail[0]
             np.savez(os.path.join(args.outdir, f'{uttid}.npz'), frame=frame, unit=unit,
-                     margin=value, score=np.float64(score), units=units)
-            print(uttid, '%.6f' % score, len(frame), len(margin))
+                     margin=value, score=np.float64(score), units=units, **more)
+            print(uttid, '%.6f' % score, len(frame), len(margin), *tail)
             total += len(frame)
         logger.info(f'wrote the unit-start lattices of {len(kept)} utterances within a beam of '
-                    f'{args.beam:g}: {total / max(len(kept), 1):.1f} entries per utterance.')
+                    f'{args.beam:g}: {total / max(len(kept), 1):.1f} entries per utterance' +
+                    (f', {n_segments / max(len(kept), 1):.1f} segments' if args.segments else '') +
+                    '.')
 
 
 class posteriors:

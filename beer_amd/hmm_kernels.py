@@ -16,7 +16,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'last_frame_sum', 'sample_paths', 'sample_route', 'check_sample', 'sample_uniforms',
            'log_evidence', 'evidence_route', 'arc_posteriors', 'arcs_route',
            'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest',
-           'max_marginals', 'maxmarg_route']
+           'max_marginals', 'maxmarg_route', 'SegmentMap', 'segment_map', 'segments_route',
+           'segment_margins', 'segments_within', 'check_segments']
 
 
 class HmmBatch:
@@ -31,6 +32,7 @@ class HmmBatch:
         self.nutt = len(lengths)
         lengths_t = torch.as_tensor(lengths, dtype=torch.int64)
         gid_t = torch.as_tensor(graph_ids, dtype=torch.int64)
+        self.source_graphs = list(graphs)
         gset = getattr(graphs[0], '_set', None) if len(graphs) > 1 else None
         if gset is not None and all(getattr(g, '_set', None) is gset for g in graphs):
             # graphs of one natively compiled GraphSet: their descriptors are rows
@@ -61,7 +63,6 @@ class HmmBatch:
             ld_info = (gset.max_degree, 0, 0)                   # alignment chains: no hub
         else:
             self.dgraphs = [g.device_graph(dtype) for g in graphs]
-            self.source_graphs = list(graphs)
             n_states = [dg.n_states for dg in self.dgraphs]
             parts = [np.asarray(g.pdf_id_mapping, dtype=np.int32)
                      if (with_pdf_ids and g.pdf_id_mapping is not None)
@@ -797,6 +798,216 @@ def max_marginals(batch, pc_llhs, arc_cat=None, init_cat=None, n_cat=0, states=T
     _hip.call('beer_hmm_max_marginals', dcode, batch.ref(), _hip.ptr(pc_llhs), amap, n_cat,
               _hip.ptr(ws), _hip.ptr(state), _hip.ptr(frame), _hip.ptr(utt), _hip.ptr(best))
     return best, state, frame, utt
+
+
+class SegmentMap:
+    '''beer_seg_map on the host: the closures of every (graph, category) as int32 numpy arrays
+    (`mem_ptr`, `members`, `mem_init`, `in_ptr`, `in_src`, `in_arc`, `ent_ptr`, `ent_src`,
+    `ent_arc`), `max_closure`, `n_cat` and `n_graphs`; `closure(g, c)` gives the member states of
+    one.  `struct(device)` uploads it once and returns the ctypes structure.'''
+    FIELDS = ('mem_ptr', 'members', 'mem_init', 'in_ptr', 'in_src', 'in_arc', 'ent_ptr',
+              'ent_src', 'ent_arc')
+
+    def __init__(self, n_graphs, n_cat, max_closure, **arrays):
+        self.n_graphs, self.n_cat, self.max_closure = n_graphs, n_cat, max_closure
+        for name in self.FIELDS:
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=np.int32))
+        self._dev = {}
+
+    def closure(self, g, c):
+        k = g * self.n_cat + c
+        return self.members[self.mem_ptr[k]:self.mem_ptr[k + 1]]
+
+    def struct(self, device):
+        hit = self._dev.get(device)
+        if hit is None:
+            # (an empty array still gets an address: no member of the structure is NULL)
+            up = _hip.upload({name: torch.from_numpy(getattr(self, name)) if
+                              getattr(self, name).size else torch.zeros(1, dtype=torch.int32)
+                              for name in self.FIELDS}, device)
+            hit = self._dev[device] = (_hip.SegMap(*[up[name].data_ptr() for name in self.FIELDS],
+                                                   self.max_closure, 0), up)
+        return hit[0]
+
+
+def _arcs_of(graph):
+    '(src, dst, n_states) of a graph object (`out_arcs()`, `n_states`) or of such a triple.'
+    if isinstance(graph, tuple):
+        src, dst, n_states = graph
+    else:
+        (src, dst), n_states = graph.out_arcs(), graph.n_states
+    return np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64), int(n_states)
+
+
+def segment_map(graphs, arc_cat, init_cat, n_cat):
+    '''The closures `segment_margins` walks, built on the host (no device needed): a
+    `SegmentMap`.  `graphs` are the distinct graphs of a batch (objects with `out_arcs()` and
+    `n_states`, or (src, dst, n_states) triples in out-CSR order), `arc_cat` / `init_cat` one
+    integer array per graph as for `arc_posteriors`.  The closure of category c in a graph is
+    the set of states reachable from the destinations of the arcs of category c and from the
+    states with `init_cat` = c through arcs of category -1 (a breadth-first search): on a phone
+    loop with `unit_start_categories` the unit's own states, on an alignment graph the union of
+    the instances of a repeated unit.'''
+    triples = [_arcs_of(g) for g in graphs]
+    arcs, inits = check_arc_categories([len(t[0]) for t in triples], [t[2] for t in triples],
+                                       arc_cat, init_cat, n_cat)
+    n_cat = int(n_cat)
+    arcs, inits = arcs.cpu().numpy(), inits.cpu().numpy()
+    counts = np.zeros(len(triples) * n_cat, dtype=np.int64)
+    parts = {name: [] for name in SegmentMap.FIELDS[1:]}
+    n_in = n_ent = a0 = s0 = 0
+    in_counts, ent_counts = [], []
+    for g, (src, dst, S) in enumerate(triples):
+        A = len(src)
+        acat, icat = arcs[a0:a0 + A], inits[s0:s0 + S]
+        a0, s0 = a0 + A, s0 + S
+        free = np.nonzero(acat == -1)[0]
+        fsrc, fdst = src[free], dst[free]
+        for c in np.union1d(acat[acat >= 0], icat[icat >= 0]):
+            enter = np.nonzero(acat == c)[0]
+            inside = np.zeros(S, dtype=bool)
+            inside[dst[enter]] = True
+            inside[icat == c] = True
+            while True:                                     # breadth-first over the -1 arcs
+                reach = fdst[inside[fsrc]]
+                if inside[reach].all():
+                    break
+                inside[reach] = True
+            members = np.nonzero(inside)[0]
+            local = np.full(S, -1, dtype=np.int64)
+            local[members] = np.arange(len(members))
+            counts[g * n_cat + c] = len(members)
+            parts['members'].append(members)
+            parts['mem_init'].append(icat[members] == c)
+            for name, arc_ids, source in (('in', free[inside[fsrc]], 'local'),
+                                          ('ent', enter, 'state')):
+                # a member's arcs together, in out-CSR order (the sort is stable)
+                arc_ids = arc_ids[np.argsort(local[dst[arc_ids]], kind='stable')]
+                per_member = np.bincount(local[dst[arc_ids]], minlength=len(members))
+                (in_counts if name == 'in' else ent_counts).append(per_member)
+                parts[name + '_src'].append(local[src[arc_ids]] if source == 'local'
+                                            else src[arc_ids])
+                parts[name + '_arc'].append(arc_ids)
+
+    def cat(chunks):
+        return np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int64)
+
+    def ptr(chunks):
+        return np.concatenate([[0], np.cumsum(cat(chunks))])
+
+    mem_ptr = np.concatenate([[0], np.cumsum(counts)])
+    in_ptr, ent_ptr = ptr(in_counts), ptr(ent_counts)
+    if max(mem_ptr[-1], in_ptr[-1], ent_ptr[-1]) >= 2 ** 31:
+        raise ValueError('segment_map: the closures of these categories hold more than 2^31 '
+                         'members or arcs')
+    return SegmentMap(len(triples), n_cat, int(counts.max(initial=0)), mem_ptr=mem_ptr,
+                      members=cat(parts['members']), mem_init=cat(parts['mem_init']),
+                      in_ptr=in_ptr, in_src=cat(parts['in_src']), in_arc=cat(parts['in_arc']),
+                      ent_ptr=ent_ptr, ent_src=cat(parts['ent_src']),
+                      ent_arc=cat(parts['ent_arc']))
+
+
+def segments_route(batch, n_cat, max_closure=0):
+    '''beer_hmm_segments_route: the form `segment_margins` runs on (the trellis kernel's arcs
+    and bins in LDS or not, and in the low bits the team size of the expand kernel,
+    `_hip.segments_team`); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_segments_route(_hip.dtype_code(batch.dtype), batch.ref(),
+                                               int(n_cat), int(max_closure))
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'segment_margins: {n_cat} categories with closures of up to {max_closure} states on '
+            f'graphs of up to {batch.struct.max_states} states: at least one category, two fp64 '
+            "rows of the graph in the CU's 160 KB of LDS (about 10000 states), and two fp64 rows "
+            'of the largest closure in 64 KB (4095 states)')
+    return route
+
+
+def check_segments(beam, max_dur, what='segment_margins'):
+    '(beam as a float, max_dur as an int); ValueError for a negative or NaN beam, max_dur < 1.'
+    beam = float(beam)
+    if not beam >= 0.:
+        raise ValueError(f'{what}: the beam is a number >= 0 (inf: everything), not {beam}')
+    if max_dur is not None:
+        if int(max_dur) != max_dur or max_dur < 1:
+            raise ValueError(f'{what}: max_dur is an integer >= 1, not {max_dur}')
+        max_dur = int(max_dur)
+    return beam, max_dur
+
+
+def _within(values, beam):
+    'values >= -beam, and finite (beam = inf keeps every finite cell).'
+    return (values >= -beam) & (values > -float('inf'))
+
+
+def segment_margins(batch, pc_llhs, arc_cat, init_cat, n_cat, beam, max_dur, seg_map=None):
+    '''(best [nutt] fp64, starts [n_frames, n_cat], entry_frame [n_entries] int64, entry_cat
+    [n_entries] int32, seg [n_entries, max_dur]) on the device, `starts` and `seg` of the batch's
+    dtype: the unit segment lattice (`beer_hmm_segment_trellis`, `beer_hmm_segment_margins`).
+    `best` and `starts` are `max_marginals`' best and per-frame rows, bit for bit.  The entries are
+    the cells (frame, category) of `starts` that are >= -beam, in row-major order (`beam` = inf:
+    every finite cell); seg[n, k] is the score of the best path on which category entry_cat[n]
+    begins at frame entry_frame[n] (indexed as in the batch's frame offsets) and lasts exactly k
+    more frames -- the next boundary, or the utterance's end, follows frame entry_frame[n] + k --
+    minus `best`; -inf where there is no such path or the segment would pass the utterance's end.
+    A segment ends where an arc of a category >= 0 is taken: the categories are those of
+    `arc_posteriors`.  `seg_map`: `segment_map` of the batch's distinct graphs and these
+    categories, built here when not given.  The entry selection is one `torch.nonzero`, which
+    waits for the device.  ValueError, before any device work: a negative or NaN beam,
+    max_dur < 1, bad categories.'''
+    beam, max_dur = check_segments(beam, max_dur)
+    if max_dur is None:
+        raise ValueError('segment_margins: max_dur is an integer >= 1, not None')
+    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat)
+    n_cat = int(n_cat)
+    if seg_map is None:
+        seg_map = segment_map(batch.source_graphs, arcs.cpu(), inits.cpu(), n_cat)
+    if seg_map.n_cat != n_cat or seg_map.n_graphs != len(batch.n_states):
+        raise ValueError(f'segment_margins: a segment map of {seg_map.n_graphs} graphs and '
+                         f'{seg_map.n_cat} categories for {len(batch.n_states)} and {n_cat}')
+    dev, dt = batch.device, batch.dtype
+    segments_route(batch, n_cat, seg_map.max_closure)
+    best = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    starts = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev)
+    if batch.nutt == 0:
+        return best, starts, torch.empty(0, dtype=torch.int64, device=dev), \
+            torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, max_dur, dtype=dt, device=dev)
+    dcode = _hip.dtype_code(dt)
+    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+    if arcs.device.type != 'cuda':
+        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+    if inits.device.type != 'cuda':
+        host['inits'] = inits
+    up = _hip.upload(host, dev)
+    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
+                       up['state_off'].data_ptr())
+    extra = _hip.lib().beer_hmm_segments_scratch_doubles(dcode, batch.ref())
+    trellis = torch.empty(2 * batch.n_elems + extra + 1, dtype=torch.float64, device=dev)
+    d, x, ws = trellis[:batch.n_elems], trellis[batch.n_elems:2 * batch.n_elems], \
+        trellis[2 * batch.n_elems:]
+    _hip.call('beer_hmm_segment_trellis', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              ctypes.byref(amap), n_cat, _hip.ptr(d), _hip.ptr(x), _hip.ptr(ws), _hip.ptr(starts),
+              _hip.ptr(best))
+    at = torch.nonzero(_within(starts, beam))               # (row-major; waits for the device)
+    entry_frame = at[:, 0].contiguous()
+    entry_cat = at[:, 1].to(torch.int32)
+    entry_off = torch.searchsorted(entry_frame, batch.bufs['frame_off'])
+    seg = torch.empty(len(at), max_dur, dtype=dt, device=dev)
+    _hip.call('beer_hmm_segment_margins', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              ctypes.byref(seg_map.struct(dev)), n_cat, _hip.ptr(d), _hip.ptr(x), _hip.ptr(best),
+              _hip.ptr(entry_frame), _hip.ptr(entry_cat), _hip.ptr(entry_off), len(at), max_dur,
+              _hip.ptr(seg))
+    return best, starts, entry_frame, entry_cat, seg
+
+
+def segments_within(entry_frame, entry_cat, seg, beam):
+    '''(start int64, end int64, unit int32, margin float64) of the cells of `segment_margins`'
+    `seg` that are >= -beam, sorted by (start, unit, end); the frames indexed as `entry_frame`.'''
+    at = torch.nonzero(_within(seg, float(beam)))
+    start = entry_frame[at[:, 0]]
+    return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
 
 
 def path_posteriors(batch, path, want_xi=False):

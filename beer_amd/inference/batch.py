@@ -33,7 +33,7 @@ from .objectives import EvidenceLowerBoundInstance
 
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
            'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch',
-           'unit_start_margins_batch', 'ShardStatics',
+           'unit_start_margins_batch', 'unit_segments_batch', 'ShardStatics',
            'decode_nbest_batch']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
@@ -746,6 +746,57 @@ def unit_start_margins_batch(model, utterances, inference_graphs=None, scale=1.,
     lost against the best path by forcing unit u to begin at frame t.'''
     return _unit_arcs_batch('unit_start_margins_batch', model, utterances, inference_graphs,
                             scale, max_frames, True, margins=True)
+
+
+def unit_segments_batch(model, utterances, beam=10., max_dur=None, inference_graphs=None,
+                        scale=1., max_frames=1 << 20):
+    '''The Viterbi score and the unit segment lattice of every utterance of a shard: (float64
+    [nutt], list of (start, end, unit, margin) per utterance) on the device
+    (`PhoneLoop.unit_segments`, batched): the segments within `beam` of the best path, frames
+    counted from the utterance's first, sorted by (start, unit, end).  `max_dur` None: the
+    length of the longest utterance of a sub-batch, which cuts nothing.'''
+    what = 'unit_segments_batch'
+    beam, max_dur = hk.check_segments(beam, max_dur, what)
+    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+        isinstance(utterances[0], torch.Tensor)
+    if not packed:
+        utterances = list(utterances)
+    if inference_graphs is not None:
+        nutt = len(utterances[1]) if packed else len(utterances)
+        if len(inference_graphs) != nutt:
+            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
+                             'utterances')
+    if not hasattr(model, 'start_pdf'):
+        raise ValueError(f'{what}: a phone loop (a model with units), not '
+                         f'{type(model).__name__}')
+    n_units = len(model.start_pdf)
+    cats = {}                       # the categories of every distinct graph, built once per call
+
+    def categories(graph):
+        if id(graph) not in cats:
+            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+        return cats[id(graph)]
+
+    out, bests = [], []
+    # decode_batch's scratch with two fp64 trellises (d and X) in place of the back-pointers; a
+    # row of start margins per frame besides (sized for float64).  The segment rows of the
+    # entries within the beam come on top: n_entries * max_dur values.
+    for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
+                                                       max_frames, 8 + 8 * n_units, 16):
+        pairs = [categories(g) for g in batch.distinct_graphs]
+        dur = max(max(run_lengths), 1) if max_dur is None else max_dur
+        best, _, frame, unit, seg = hk.segment_margins(
+            batch, pc_llhs, [p[0] for p in pairs], [p[1] for p in pairs], n_units, beam, dur)
+        bests.append(best)
+        start, end, unit, margin = hk.segments_within(frame, unit, seg, beam)
+        first = batch.bufs['frame_off']
+        utt = torch.searchsorted(first[1:].contiguous(), start, right=True)
+        counts = torch.bincount(utt, minlength=len(run_lengths)).tolist()
+        start, end = start - first[utt], end - first[utt]
+        out += list(zip(*(torch.split(v, counts) for v in
+                          (start.to(torch.int32), end.to(torch.int32), unit, margin))))
+    return (torch.cat(bests) if bests else
+            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
 
 
 def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame,

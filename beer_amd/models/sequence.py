@@ -742,10 +742,39 @@ def _unit_start_margins(model, data, inference_graph=None, scale=1.):
                                    inference_graph=inference_graph, scale=scale)
 
 
+def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, scale=1.):
+    '''(best, start, end, unit, margin) on the device: the Viterbi score (0-d float64) and the
+    unit segment lattice of the beam -- every (unit, start, end) such that some path on which the
+    unit BEGINS at frame `start` (as `unit_start_margins` has it) and the next unit begins at
+    frame `end` + 1 (or the utterance ends with frame `end`) scores within `beam` of the best
+    path; `margin` (float64, <= 0 up to rounding) is what the best such path loses against it.
+    `start`, `end`, `unit` are int32, the units numbered in `start_pdf` order; sorted by
+    (start, unit, end).  `max_dur`: the longest segment looked for, in frames (None: the
+    utterance's length); `beam` = inf keeps every possible segment.  The Viterbi segmentation
+    has margin 0.  Otherwise as `decode`.'''
+    beam, max_dur = hk.check_segments(beam, max_dur, 'unit_segments')
+    graph = model.graph if inference_graph is None else inference_graph
+    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+    n_units = len(model.start_pdf)
+    src, _ = graph.out_arcs()
+    cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_units)
+    stats = model.sufficient_statistics(data)
+    pc_all = model._emissions().expected_log_likelihood(stats)
+    if getattr(getattr(graph, '_set', None), 'is_bound', False):
+        model._bound_set(graph).refresh(pc_all.dtype)
+    batch = model._batch_of_one(graph, len(stats), pc_all.dtype)
+    best, _, frame, unit, seg = hk.segment_margins(
+        batch, hk.gather(batch, pc_all, scale), *cats, n_units, beam,
+        max(len(stats), 1) if max_dur is None else max_dur)
+    start, end, unit, margin = hk.segments_within(frame, unit, seg, beam)
+    return best[0], start.to(torch.int32), end.to(torch.int32), unit, margin
+
+
 class PhoneLoop(HMM):
     'Phone-loop HMM with a prior over the phone (unigram) weights.'
     unit_starts = _unit_starts
     unit_start_margins = _unit_start_margins
+    unit_segments = _unit_segments
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
@@ -923,6 +952,7 @@ class BigramPhoneLoop(HMM):
     (phoneloop.py:174-186).'''
     unit_starts = _unit_starts
     unit_start_margins = _unit_start_margins
+    unit_segments = _unit_segments
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,

@@ -1255,6 +1255,111 @@ size_t beer_hmm_maxmarg_scratch_doubles(int dtype, const beer_batch* batch_h);
 int beer_hmm_maxmarg_route(int dtype, const beer_batch* batch_h, int n_cat, int want_state,
                            int want_frames, int want_utt);
 
+/* The closures of beer_hmm_segment_margins: device arrays built on the host once per distinct
+ * graph (hmm_kernels.segment_map).  The closure of category c in graph g is the set of states
+ * reachable from the category's entry states -- the destinations of the arcs with arc_cat == c
+ * and the states with init_cat == c -- through arcs with arc_cat == -1; only these can carry r
+ * (below).  Closure k = g * n_cat + c holds the members mem_ptr[k] .. mem_ptr[k + 1] - 1, a
+ * member's LOCAL index is its position in its closure:
+ *   members    the member's state in its graph
+ *   mem_init   1 when init_cat of that state == c, else 0
+ *   in_ptr     [n_members + 1] the member's in-arcs with arc_cat == -1 (their sources are
+ *              members of the same closure): in_src the source's LOCAL index, in_arc the arc's
+ *              index in the graph's out-CSR (where its weight is read)
+ *   ent_ptr    [n_members + 1] the member's in-arcs with arc_cat == c: ent_src the source STATE
+ *              (any state of the graph), ent_arc the arc's index in the out-CSR
+ *   max_closure the largest number of members of a closure (0: no category has a member) */
+typedef struct {
+    const int32_t* mem_ptr;    /* [n_graphs * n_cat + 1] */
+    const int32_t* members;
+    const int32_t* mem_init;
+    const int32_t* in_ptr;
+    const int32_t* in_src;
+    const int32_t* in_arc;
+    const int32_t* ent_ptr;
+    const int32_t* ent_src;
+    const int32_t* ent_arc;
+    int32_t max_closure;
+    int32_t reserved;
+} beer_seg_map;
+
+/* Unit segment lattices: the max-marginal of a whole segment.  With the categories of
+ * beer_hmm_arc_posteriors / beer_hmm_max_marginals (beer_arc_map), for a path z_0 .. z_{T-1}:
+ * frame 0 is a boundary with label init_cat[z_0]; frame t >= 1 is a boundary with label
+ * arc_cat(z_{t-1} -> z_t) when that label is >= 0.  The path HAS THE SEGMENT (c, s, e) when s is a
+ * boundary with label c, no frame in s+1 .. e is a boundary, and e + 1 is a boundary or
+ * e = T - 1.  seg(c, s, e) is the maximum score over the paths that have the segment, minus
+ * best; -inf when there is none.  With d, e and best as in beer_hmm_max_marginals:
+ *   X_{T-1}(i) = final_i
+ *   X_t(i)     = max over arcs i->j with arc_cat >= 0 of (w_ij + (l_{t+1}(j) + e_{t+1}(j)))   t < T-1
+ *   r_s(j)     = d_0(j) if init_cat[j] == c else -inf                                         s = 0
+ *   r_s(j)     = max over arcs i->j with arc_cat == c of ((d_{s-1}(i) + w_ij) + l_s(j))       s >= 1
+ *   r_t(j)     = max over arcs i->j with arc_cat == -1 of ((r_{t-1}(i) + w_ij) + l_t(j))      t = s+1 ..
+ *   seg(c,s,e) = max_i (r_e(i) + X_e(i)) - best
+ * All of it fp64 whatever the dtype (float32 inputs are upcast on load), the additions in
+ * exactly the bracketed order, every fold a maximum: the same bits on every run.  On inputs
+ * whose sums are exact, max_e seg(c, s, e) is the start margin frame_out[s, c].
+ *
+ * beer_hmm_segment_trellis: one launch, one workgroup per utterance, the shape of
+ * beer_hmm_max_marginals.
+ *   map, n_cat the categories, n_cat >= 1
+ *   d, x       [n_elems] fp64 each, packed like pc_llhs, written (=): d_t(j) and X_t(i); an
+ *              utterance with best = -inf gets X = -inf
+ *   ws         fp64 scratch of beer_hmm_segments_scratch_doubles() doubles (NULL when that is 0)
+ *   frame_out  [n_frames, n_cat] of dtype, written (=): the start margins, with exactly the
+ *              meaning and the bits of beer_hmm_max_marginals' frame_out
+ *   best       [nutt] fp64, written (=); -inf for an utterance of no frames
+ * EINVAL where beer_hmm_max_marginals refuses the batch with frame_out given; a NULL map or map
+ * member; n_cat < 1; with utterances in the batch a NULL pc_llhs, d, x, frame_out or best, or a
+ * NULL ws where the scratch is not 0. */
+int beer_hmm_segment_trellis(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                             const beer_arc_map* map, int n_cat, double* d, double* x, double* ws,
+                             void* frame_out, double* best, void* stream);
+
+/* beer_hmm_segment_margins: expands a list of entries (frame, category) into their segment
+ * margins, from the trellises and best that beer_hmm_segment_trellis wrote for the same batch,
+ * pc_llhs and categories.
+ *   entry_frame [n_entries] the frame of the entry, indexed as in frame_off
+ *   entry_cat   [n_entries] its category
+ *   entry_off   [nutt + 1] the entries are sorted by utterance: those of utterance u are
+ *               entry_off[u] .. entry_off[u + 1] - 1
+ *   out         [n_entries, max_dur] of dtype, written (=): column k holds
+ *               seg(c, s, s + k); -inf where the segment is impossible or runs past the utterance
+ * A team of L lanes handles an entry (L: the smallest power of two in 4 .. 256 that is
+ * >= max_closure; lanes stride over larger closures), a workgroup of 256 threads holds 256 / L
+ * teams, each with two fp64 rows of max_closure (at least 1) doubles and two 8-byte key slots in
+ * LDS.  An entry whose category is outside [0, n_cat), whose frame is outside its utterance or
+ * whose utterance has best = -inf gets -inf in its row.
+ * EINVAL where beer_hmm_segment_trellis refuses the batch; a NULL seg map; max_closure < 0 or
+ * above max_states; (256 / L) (16 max(max_closure, 1) + 16) bytes above 64 KiB (max_closure >
+ * 4095); n_entries < 0; max_dur < 1; with entries and utterances a NULL member or argument. */
+int beer_hmm_segment_margins(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                             const beer_seg_map* seg_map, int n_cat, const double* d,
+                             const double* x, const double* best, const int64_t* entry_frame,
+                             const int32_t* entry_cat, const int64_t* entry_off,
+                             int64_t n_entries, int max_dur, void* out, void* stream);
+
+/* Doubles `ws` of beer_hmm_segment_trellis must hold: nutt * max_states where a thread owns
+ * several states (max_states > 256: e_{t-1} waits in the utterance's row, the d trellis being
+ * kept), else 0; 0 for a batch the launch refuses. */
+size_t beer_hmm_segments_scratch_doubles(int dtype, const beer_batch* batch_h);
+
+/* The form the two launches pick (host only), built from the launchers' own plan.  With rows,
+ * arcs (with the categories) and the thresholds of beer_hmm_maxmarg_route at want_frames:
+ *   BEER_SEGMENTS_BLOCK     the trellis kernel: one workgroup of 256 threads per utterance
+ *   BEER_SEGMENTS_ARCS_LDS  its arc lists and categories are kept in LDS: rows + arcs <= 64 KiB
+ *   BEER_SEGMENTS_BINS_LDS  its bins are 64-bit keys in LDS: n_cat <= 2048 and rows <= 96 KiB;
+ *                           else the rows of frame_out hold keys and are decoded at the end
+ *   BEER_SEGMENTS_TEAM(route)  the lanes L of a team of the expand kernel, 4 .. 256
+ * BEER_EINVAL exactly where beer_hmm_segment_trellis or, with this max_closure,
+ * beer_hmm_segment_margins refuses the batch and n_cat. */
+#define BEER_SEGMENTS_BLOCK 0x1000
+#define BEER_SEGMENTS_ARCS_LDS 0x100
+#define BEER_SEGMENTS_BINS_LDS 0x200
+#define BEER_SEGMENTS_FAMILY(route) ((route) & 0xF000)
+#define BEER_SEGMENTS_TEAM(route) (1 << ((route) & 0xF))
+int beer_hmm_segments_route(int dtype, const beer_batch* batch_h, int n_cat, int max_closure);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
