@@ -797,7 +797,7 @@ int beer_unpack_resps(int64_t T, int K, const void* packed_resps, float* resps, 
 }
 
 int beer_weights_from_acc(int S, int G, int Q, const double* acc, double* out, void* stream) {
-    BEER_REQUIRE(S >= 0 && G >= 1 && Q >= 3 && acc && out);
+    BEER_REQUIRE(S >= 0 && G >= 1 && Q >= 2 && acc && out);
     if (S == 0) return BEER_OK;
     hipLaunchKernelGGL(weights_from_acc_kernel, dim3(S), dim3(64), 0,
                        as_stream(stream), S, G, Q, acc, out);

@@ -2577,6 +2577,8 @@ int beer_hmm_path_posteriors(int dtype, const beer_batch* b, const int64_t* path
                              double* xi_sum, double* gamma0_sum, void* stream) {
     BEER_REQUIRE(b && b->nutt >= 0);
     if (b->nutt == 0) return BEER_OK;
+    // xi_sum [S, S] and gamma0_sum [S] are indexed with the utterance's own S: one graph
+    BEER_REQUIRE((!xi_sum && !gamma0_sum) || b->n_graphs == 1);
     BEER_DISPATCH(dtype, path_post_launch, b, path, gamma, xi_sum, gamma0_sum, stream);
 }
 

@@ -256,7 +256,7 @@ def extract(signals, conf=None, as_numpy=True):
                      add_energy=cfg['add_energy'], extra_cols=orders)
     if orders:
         _deltas(buf, batch.frame_off, batch.nutt, base, [cfg['delta_winlen']] * orders)
-    if cfg['utt_mnorm']:
+    if cfg['utt_mnorm'] and batch.total:           # (no frame at all: nothing to normalise)
         _hip.call('beer_features_cmn', batch.nutt, _hip.ptr(batch.frame_off), buf.shape[1],
                   buf.shape[1], _hip.ptr(buf))
     parts = torch.split(buf, batch.nframes)

@@ -428,10 +428,12 @@ def path_counts(batch, path, xi):
         _hip.call('beer_hmm_path_counts_cat', batch.ref(), _hip.ptr(path.contiguous()),
                   ctypes.byref(batch.cat_map), _hip.ptr(cat_counts))
         return ('cat', cat_counts, None)
-    last_states = path[batch.bufs['frame_off'][1:] - 1]
     last = torch.zeros(xi.shape[0], dtype=torch.float64, device=xi.device)
-    last.index_add_(0, last_states, torch.ones(len(last_states), dtype=torch.float64,
-                                               device=xi.device))
+    if path.numel():
+        # an utterance of no frames ends in no state: it counts 0 (at whatever index)
+        off = batch.bufs['frame_off']
+        ends = (off[1:] - 1).clamp_(min=0)
+        last.index_add_(0, path[ends], (off[1:] > off[:-1]).to(torch.float64))
     return ('dense', xi, last)
 
 
@@ -1011,11 +1013,15 @@ def segments_within(entry_frame, entry_cat, seg, beam):
 
 
 def path_posteriors(batch, path, want_xi=False):
+    '''(gamma one-hot packed, xi_sum [S, S] fp64 or None, gamma0_sum [S] fp64 or None) of a state
+    path; xi / gamma0 need a batch sharing one graph.'''
     dt, dev = batch.dtype, batch.device
     path = _hip.on_device(torch.as_tensor(path)).to(torch.int64).contiguous()
     gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
     xi = g0 = None
     if want_xi:
+        if not batch.shared_graph:
+            raise ValueError('transition counts of a path need one graph for the whole batch')
         S = batch.n_states[0]
         xi = torch.zeros(S, S, dtype=torch.float64, device=dev)
         g0 = torch.zeros(S, dtype=torch.float64, device=dev)

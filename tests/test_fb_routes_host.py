@@ -345,8 +345,8 @@ def validation_rows():
         b=desc(32768, **DENSE))
     add('not a one-wave descriptor', WAVE_ONLY, -100000, b=desc(300))
     add('no low-degree image', WAVE_ONLY, -100000, b=desc(64, all_lowdeg=0))
-    add('two graphs', ['posteriors_fused_counts', 'forward_backward_counts', 'last_frame_sum'],
-        -100000, b=_two_graphs())
+    add('two graphs', ['posteriors_fused_counts', 'forward_backward_counts', 'last_frame_sum',
+                       'path_posteriors'], -100000, b=_two_graphs())
     add('a hub', CAT, -100000, b=desc(64, max_hubs=1, members=3))
     add('null map', CAT + ['path_counts_cat'], -100000, m=None)
     for member in ('arc_cat', 'last_cat', 'arc_off', 'state_off'):
