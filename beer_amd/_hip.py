@@ -395,6 +395,10 @@ SIGNATURES = {
     'beer_weights_from_acc': [c_i, c_i, c_i, c_p, c_p, c_p],
     'beer_tied_lognorm': [c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_tied_accumulate': [c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_nw_predictive_table': _four, 'beer_ng_predictive_table': _four,
+    'beer_ing_predictive_table': _four,
+    'beer_predictive_llh': [c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p],
+    'beer_mixtureset_predictive': [c_i, c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_gather': [c_i, c_p, c_i, c_p, c_d, c_p, c_p],
     'beer_hmm_forward_backward': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_posteriors_fused': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p, c_p,

@@ -580,6 +580,10 @@ class decode:
                             help='with --nbest: among the N state paths keep the best-scoring '
                                  'one of each unit sequence and renumber (may print fewer than N)')
         parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('--predictive', action='store_true',
+                            help='decode with the posterior-predictive (Student-t) emission '
+                                 'densities instead of the expected log-likelihoods (the most '
+                                 'likely path only: not with --nbest or --nsamples)')
         parser.add_argument('-u', '--utts', help='utterances to decode ("-" for stdin)')
         parser.add_argument('model', help='hmm based model')
         parser.add_argument('dataset', help='data set')
@@ -594,6 +598,10 @@ class decode:
                 raise SystemExit(f'--nbest: 1 .. {_hip.NBEST_MAX}')
         elif args.scores is not None or args.distinct:
             raise SystemExit('--scores and --distinct go with --nbest')
+        if getattr(args, 'predictive', False) and \
+                (args.nbest is not None or args.nsamples is not None):
+            raise SystemExit('--predictive decodes the most likely path: not with --nbest or '
+                             '--nsamples')
 
     @staticmethod
     def nbest_lines(uttid, paths, scores, start_pdf, per_frame=False, distinct=False):
@@ -652,8 +660,8 @@ class decode:
                     print(f'{uttid}-{k}', ' '.join(phones))
             logger.info(f'successfully drew {args.nsamples} paths for {len(kept)} utterances.')
             return
-        paths = beer.decode_batch(model, feats, inference_graphs=use, scale=args.acoustic_scale) \
-            if kept else []
+        paths = beer.decode_batch(model, feats, inference_graphs=use, scale=args.acoustic_scale,
+                                  predictive=args.predictive) if kept else []
         for uttid, path in zip(kept, paths):
             phones = phones_of_path(path.cpu().numpy(), model.start_pdf, args.per_frame)
             print(uttid, ' '.join(phones))
@@ -668,6 +676,10 @@ class score:
     def setup(parser):
         parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
         parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('--predictive', action='store_true',
+                            help='score with the posterior-predictive (Student-t) emission '
+                                 'densities: the held-out likelihood of the Bayesian model '
+                                 '(the default scores with exp(E[ln p]), which is not a density)')
         parser.add_argument('-u', '--utts', help='utterances to score ("-" for stdin)')
         parser.add_argument('model', help='hmm based model')
         parser.add_argument('dataset', help='data set')
@@ -679,8 +691,9 @@ class score:
         alis = _load_alis(args.alis)
         feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
         use = None if alis is None else [g if g is not None else model.graph for g in graphs]
-        values = beer.log_evidence_batch(model, feats, inference_graphs=use,
-                                         scale=args.acoustic_scale).cpu().tolist() if kept else []
+        values = beer.log_evidence_batch(
+            model, feats, inference_graphs=use, scale=args.acoustic_scale,
+            predictive=args.predictive).cpu().tolist() if kept else []
         total, n_frames = 0., 0
         for uttid, value, utt in zip(kept, values, feats):
             print(uttid, '%.6f' % value, len(utt))

@@ -368,6 +368,111 @@ __global__ void ng_from_natural_kernel(int K, int D, const T* eta, T* mean, T* s
 }
 
 // ---------------------------------------------------------------------------
+// Posterior-predictive (Student-t) tables: per pdf the mean, the scaled precision
+// factor and the two constants of l = c - h * L(x) (include/beer_hip.h,
+// "Posterior-predictive densities"; the frame kernels are in predictive.hip).
+// ---------------------------------------------------------------------------
+
+// ln Gamma(x + delta) - ln Gamma(x), x > 0, delta >= 0, without the cancellation of two
+// lgamma calls (each is ~x ln x: at x = 1e6 their difference would keep 2e-9 of the ~7 it
+// is).  Both arguments are moved up to x >= 16 by Gamma's recurrence -- the product of the
+// ratios as a sum of log1p -- where Stirling's series is exact to 1e-18 after six terms and
+// the leading terms combine in closed form:
+//   (x - 1/2) log1p(delta / x) + delta (ln(x + delta) - 1) + S(x + delta) - S(x).
+__device__ inline double stirling_tail(double x) {
+    const double f = 1.0 / (x * x);
+    return (1.0 / x) * (1.0 / 12.0 + f * (-1.0 / 360.0 + f * (1.0 / 1260.0 + f * (-1.0 / 1680.0 +
+           f * (1.0 / 1188.0 + f * (-691.0 / 360360.0))))));
+}
+__device__ inline double lgamma_diff(double x, double delta) {
+    double r = 0.0;
+    while (x < 16.0) {
+        r -= log1p(delta / x);
+        x += 1.0;
+    }
+    return r + (x - 0.5) * log1p(delta / x) + delta * (log(x + delta) - 1.0) +
+           stirling_tail(x + delta) - stirling_tail(x);
+}
+
+// One thread per pdf.  Row: [m (D), kappa' / (2 b_d) (D) | kappa' / (2 b) (1), c, h].
+template <typename T, bool ISO>
+__global__ void ng_predictive_table_kernel(int K, int D, const T* mean, const T* scale,
+                                           const T* shape, const T* rates, T* out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const int Q = ISO ? D + 3 : 2 * D + 2;
+    const double a = (double)shape[k], kappa = (double)scale[k], kp = kappa / (kappa + 1.0);
+    T* o = out + (size_t)k * Q;
+    for (int d = 0; d < D; ++d) o[d] = mean[(size_t)k * D + d];
+    double c, h;
+    if (ISO) {
+        const double b = (double)rates[k], hd = 0.5 * (double)D;
+        o[D] = (T)(kp / (2.0 * b));
+        c = lgamma_diff(a, hd) + hd * (log(kp / b) - kLog2Pi);
+        h = a + hd;
+    } else {
+        double sl = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double b = (double)rates[(size_t)k * D + d];
+            o[D + d] = (T)(kp / (2.0 * b));
+            sl += log(kp / b);
+        }
+        c = (double)D * lgamma_diff(a, 0.5) + 0.5 * (sl - (double)D * kLog2Pi);
+        h = a + 0.5;
+    }
+    o[Q - 2] = (T)c;
+    o[Q - 1] = (T)h;
+}
+
+// One workgroup per pdf: kappa' W = R^T R by a Cholesky factorisation in LDS (fp64).  Row:
+// [m (D), R (D x D row-major, upper triangular, zeros below the diagonal), c, h], so that
+// kappa' (x - m)^T W (x - m) = |R (x - m)|^2 is a sum of squares whatever the rounding.
+template <typename T>
+__global__ __launch_bounds__(kNwThreads) void nw_predictive_table_kernel(
+    int D, const T* __restrict__ mean, const T* __restrict__ scale, const T* __restrict__ W,
+    const T* __restrict__ dof, T* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* A = reinterpret_cast<double*>(smem);       // D*D: lower factor in the lower triangle
+    double* red = A + D * D;                            // 16
+    const int k = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int Q = D * D + D + 2;
+    const double nu = (double)dof[k], kappa = (double)scale[k], kp = kappa / (kappa + 1.0);
+    const T* Wk = W + (size_t)k * D * D;
+    T* o = out + (size_t)k * Q;
+    for (int idx = tid; idx < D * D; idx += nt) {
+        const int i = idx / D, j = idx - i * D;
+        A[idx] = kp * 0.5 * ((double)Wk[i * D + j] + (double)Wk[j * D + i]);
+    }
+    for (int i = tid; i < D; i += nt) o[i] = mean[(size_t)k * D + i];
+    for (int j = 0; j < D; ++j) {
+        __syncthreads();
+        const double ljj = sqrt(A[j * D + j]);
+        __syncthreads();
+        for (int i = j + tid; i < D; i += nt) A[i * D + j] = i == j ? ljj : A[i * D + j] / ljj;
+        __syncthreads();
+        const int n = D - j - 1;                        // trailing block: rows and columns > j
+        for (int idx = tid; idx < n * n; idx += nt) {
+            const int i = j + 1 + idx / n, c = j + 1 + idx % n;
+            if (c <= i) A[i * D + c] -= A[i * D + j] * A[c * D + j];
+        }
+    }
+    __syncthreads();
+    double part = 0.0;
+    for (int i = tid; i < D; i += nt) part += log(A[i * D + i]);
+    const double half_logdet = block_sum(part, red);    // 1/2 ln|kappa' W|
+    for (int idx = tid; idx < D * D; idx += nt) {
+        const int i = idx / D, j = idx - i * D;
+        o[D + idx] = j >= i ? (T)A[j * D + i] : (T)0;
+    }
+    if (tid == 0) {
+        const double hd = 0.5 * (double)D;
+        // 1/2 ln|W| + D/2 ln(kappa' / pi) = 1/2 ln|kappa' W| - D/2 ln pi
+        o[Q - 2] = (T)(lgamma_diff(0.5 * (nu + 1.0) - hd, hd) + half_logdet - hd * kLogPi);
+        o[Q - 1] = (T)(0.5 * (nu + 1.0));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Dirichlet / Gamma: one thread per pdf.
 // ---------------------------------------------------------------------------
 
@@ -582,6 +687,35 @@ int ng_launch(int which, int K, int D, const void* mean, const void* scale,
     else
         hipLaunchKernelGGL((ng_natural_kernel<T, ISO>), g, b, 0, s, K, D, (const T*)mean,
                            (const T*)scale, (const T*)shape, (const T*)rates, (T*)out);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T>
+int nw_predictive_table_launch(int K, int D, const void* mean, const void* scale, const void* W,
+                               const void* dof, void* out, void* stream) {
+    BEER_REQUIRE(K >= 0 && D >= 1 && D <= kMaxFullDim);
+    if (K == 0) return BEER_OK;
+    BEER_REQUIRE(mean && scale && W && dof && out);
+    const size_t lds = ((size_t)D * D + 16) * sizeof(double);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nw_predictive_table_kernel<T>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, beer::kMaxDynLds);
+    hipLaunchKernelGGL(nw_predictive_table_kernel<T>, dim3(K), dim3(nw_threads(K, D)), lds,
+                       as_stream(stream), D, (const T*)mean, (const T*)scale, (const T*)W,
+                       (const T*)dof, (T*)out);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
+template <typename T, bool ISO>
+int ng_predictive_table_launch(int K, int D, const void* mean, const void* scale,
+                               const void* shape, const void* rates, void* out, void* stream) {
+    BEER_REQUIRE(K >= 0 && D >= 1);
+    if (K == 0) return BEER_OK;
+    BEER_REQUIRE(mean && scale && shape && rates && out);
+    hipLaunchKernelGGL((ng_predictive_table_kernel<T, ISO>), dim3(blocks_for(K, 64)), dim3(64), 0,
+                       as_stream(stream), K, D, (const T*)mean, (const T*)scale, (const T*)shape,
+                       (const T*)rates, (T*)out);
     BEER_LAUNCH_CHECK();
     return BEER_OK;
 }
@@ -944,6 +1078,23 @@ int beer_ing_from_natural(int dtype, int K, int D, const void* eta, void* mean, 
                           void* shape, void* rate, void* stream) {
     if (dtype == BEER_F32) return ng_from_natural_launch<float, true>(K, D, eta, mean, scale, shape, rate, stream);
     if (dtype == BEER_F64) return ng_from_natural_launch<double, true>(K, D, eta, mean, scale, shape, rate, stream);
+    return BEER_EINVAL;
+}
+
+int beer_nw_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                             const void* W, const void* dof, void* table, void* stream) {
+    BEER_DISPATCH(dtype, nw_predictive_table_launch, K, D, mean, scale, W, dof, table, stream);
+}
+int beer_ng_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                             const void* shape, const void* rates, void* table, void* stream) {
+    if (dtype == BEER_F32) return ng_predictive_table_launch<float, false>(K, D, mean, scale, shape, rates, table, stream);
+    if (dtype == BEER_F64) return ng_predictive_table_launch<double, false>(K, D, mean, scale, shape, rates, table, stream);
+    return BEER_EINVAL;
+}
+int beer_ing_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                              const void* shape, const void* rate, void* table, void* stream) {
+    if (dtype == BEER_F32) return ng_predictive_table_launch<float, true>(K, D, mean, scale, shape, rate, table, stream);
+    if (dtype == BEER_F64) return ng_predictive_table_launch<double, true>(K, D, mean, scale, shape, rate, table, stream);
     return BEER_EINVAL;
 }
 

@@ -84,6 +84,14 @@ class _NormalFamily(ExponentialFamily):
     def log_norm(self):
         return self._memoised('lnorm', lambda: self._launch('log_norm', 0))
 
+    def predictive_table(self):
+        '''What the posterior-predictive (Student-t) frame kernels read per pdf, [K, Q] ([Q]
+        for a single pdf; Q as `natural_shape`): the mean, the scaled precision factor and
+        the constants c, h of ln p(x | this pdf) = c - h L(x) (include/beer_hip.h:
+        `beer_*_predictive_table`).  Memoised per parameter version, like E[T].'''
+        return self._memoised('pred', lambda: self._launch(
+            'predictive_table', self._qdim(self.params.mean.shape[-1])))
+
 
 def _normal_from_natural(prefix, out_shapes, single_shapes):
     def from_natural(cls, natural_params):

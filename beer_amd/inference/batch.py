@@ -345,6 +345,22 @@ def _emission_estep(groups, stats, dtype, for_accumulate=False):
     return pc_all, comps
 
 
+def _emission_predictive(groups, stats):
+    '''pc_all [T, S_total] of posterior-predictive log-densities: the predictive twin of
+    `_emission_estep` for the searches (Student-t densities of the Gaussians under the
+    logarithm of the MEAN weights; nothing is kept for an accumulation).'''
+    cols = []
+    for grp, S, G in groups:
+        if isinstance(grp, TiedMixtureSet):
+            grp.predictive_log_likelihood(stats)            # raises: not supported
+        ns = _normalset(grp)
+        lmw = grp.leaf_log_mean_weights() if isinstance(grp, MixtureSet) else None
+        cols.append(kernels.mixtureset_predictive(
+            stats.as_cov(ns.cov_type), ns.means_precisions.posterior.predictive_table(), lmw,
+            S, G, ns.cov_type))
+    return cols[0] if len(cols) == 1 else torch.cat(cols, dim=-1)
+
+
 def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths, max_frames,
                frame_images=None, statics=None, sample=None):
     emissions = model._emissions()
@@ -654,11 +670,15 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
     return _finish(model, value_terms, kl, len(lengths), acc, datasize, total)
 
 
-def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20):
+def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20,
+                 predictive=False):
     '''Viterbi pdf-id paths for a shard: list of int64 tensors, one per
-    utterance (`HMM.decode`, beer/models/hmm.py:105-114, batched).'''
+    utterance (`HMM.decode`, beer/models/hmm.py:105-114, batched).  `predictive`: the
+    emissions are the posterior-predictive densities; the arcs of the graphs are used as
+    they stand (fixed, or E[ln a] / E[ln pi] where learned), as in `HMM.decode`.'''
     return _paths_batch(model, utterances, inference_graphs, scale, max_frames, 0,
-                        lambda batch, pc_llhs: hk.viterbi(batch, pc_llhs, map_pdf=True))
+                        lambda batch, pc_llhs: hk.viterbi(batch, pc_llhs, map_pdf=True),
+                        predictive=predictive)
 
 
 def sample_paths_batch(model, utterances, inference_graphs=None, scale=1., nsamples=1,
@@ -697,10 +717,13 @@ def decode_nbest_batch(model, utterances, k, inference_graphs=None, scale=1.,
 
 
 def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_frame=False,
-                       max_frames=1 << 20):
+                       max_frames=1 << 20, predictive=False):
     '''ln p(x) of every utterance of a shard under the model, summed over all state paths:
     float64 [nutt] on the device (`HMM.log_evidence`, batched); with `per_frame` also a list of
-    float64 [T_u] tensors, the terms ln p(x_t | x_0 .. x_{t-1}) of every utterance.'''
+    float64 [T_u] tensors, the terms ln p(x_t | x_0 .. x_{t-1}) of every utterance.
+    `predictive`: the emissions are the posterior-predictive densities (held-out likelihood);
+    the arcs of the graphs are used as they stand (fixed, or E[ln a] / E[ln pi] where
+    learned), as in `HMM.log_evidence`.'''
     packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
         isinstance(utterances[0], torch.Tensor)
     if not packed:
@@ -713,7 +736,8 @@ def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_f
     totals, frames = [], []
     # decode_batch's scratch without the trellis; a float64 per frame besides
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
-                                                       max_frames, 8 if per_frame else 0, 0):
+                                                       max_frames, 8 if per_frame else 0, 0,
+                                                       predictive=predictive):
         utt, frame = hk.log_evidence(batch, pc_llhs, per_frame=per_frame)
         totals.append(utt)
         if per_frame:
@@ -851,22 +875,24 @@ def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frame
 
 
 def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_bytes, search,
-                 trellis_bytes=4):
+                 trellis_bytes=4, predictive=False):
     '''`search(batch, pc_llhs)` -> paths [..., n_frames] over sub-batches of the shard, split by
     utterance along the last dimension.  Scratch per frame: decode_batch's, with `trellis_bytes`
     per state for the search's own workspace and `extra_bytes` besides.'''
     paths = []
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
-                                                       max_frames, extra_bytes, trellis_bytes):
+                                                       max_frames, extra_bytes, trellis_bytes,
+                                                       predictive=predictive):
         paths += list(torch.split(search(batch, pc_llhs), run_lengths, dim=-1))
     return paths
 
 
 def _search_batches(model, utterances, inference_graphs, scale, max_frames, extra_bytes,
-                    trellis_bytes):
+                    trellis_bytes, predictive=False):
     '''The sub-batches of a shard for a search over its utterances: yields (HmmBatch, gathered
     pc_llhs, lengths) per sub-batch.  Scratch per frame: the emissions' E-step, the gathered
-    log-likelihoods, `trellis_bytes` per state and `extra_bytes` besides.'''
+    log-likelihoods, `trellis_bytes` per state and `extra_bytes` besides.  `predictive`: the
+    emissions' posterior-predictive densities (`_emission_predictive`) in place of the E-step.'''
     X, lengths = pack_utterances(utterances)
     groups = _groups(model._emissions())
     S_total = sum(S for _, S, _ in groups)
@@ -885,7 +911,10 @@ def _search_batches(model, utterances, inference_graphs, scale, max_frames, extr
     for run in _sub_batches(lengths, bpf, max_frames):
         f0, f1 = off[run[0]], off[run[-1] + 1]
         stats = FrameStats(X[f0:f1], _normalset(groups[0][0]).cov_type)
-        pc_all, _ = _emission_estep(groups, stats, X.dtype)
+        if predictive:
+            pc_all = _emission_predictive(groups, stats)
+        else:
+            pc_all, _ = _emission_estep(groups, stats, X.dtype)
         run_lengths = [lengths[u] for u in run]
         if inference_graphs is None:
             uniq = [model.graph]

@@ -13,7 +13,7 @@ from . import _hip
 from .stats import FrameStats
 
 __all__ = ['normal_llh', 'mixtureset_estep', 'normal_accumulate', 'weights_from_acc',
-           'tied_lognorm', 'tied_accumulate',
+           'tied_lognorm', 'tied_accumulate', 'predictive_llh', 'mixtureset_predictive',
            'is_dense', 'dense_llh', 'dense_softmax', 'dense_accumulate', 'rowdot',
            'attach_stats_grad', 'differentiable_stats', 'sample_stats', 'attach_frame_grad',
            'frames_llh_backward', 'normal_llh_autograd']
@@ -487,6 +487,91 @@ def tied_accumulate(pool_llh, m, pc, log_weights, state_resps, counts=None):
               _hip.ptr(mm), _hip.ptr(norm), _hip.ptr(lw), _hip.ptr(g), _hip.ptr(r),
               _hip.ptr(counts))
     return r, counts
+
+
+# ---- posterior-predictive (Student-t) densities ------------------------------------------------
+# ln of the integral of p(x | theta) q(theta) from the frames and the family's
+# `predictive_table()` (include/beer_hip.h, "Posterior-predictive densities").
+
+def _table_dim(table, cov_type):
+    'D of a predictive table [K, Q] (Q = the family\'s statistics dimension).'
+    Q = table.shape[-1]
+    if cov_type == 'diagonal':
+        return (Q - 2) // 2
+    if cov_type == 'isotropic':
+        return Q - 3
+    D = int(round((-1 + (1 + 4 * (Q - 2)) ** .5) / 2))
+    if D * D + D + 2 != Q:
+        raise ValueError(f'a full-covariance predictive table has D^2 + D + 2 columns, not {Q}')
+    return D
+
+
+def predictive_frames(data_or_stats, dim, cov_type):
+    '''The `FrameStats` a predictive density is evaluated on: raw frames [T, dim] or the lazy
+    statistics of such frames.  Dense [T, Q] statistics (sample averages handed to the prior
+    of a VAE), scaled statistics and frames that carry an autograd graph raise
+    `NotImplementedError`: the predictive density of averaged or scaled statistics is not
+    defined, and it has no gradient kernel.  Checked before any device work.'''
+    if isinstance(data_or_stats, FrameStats):
+        st = data_or_stats
+        if has_source(st):
+            raise NotImplementedError('predictive densities are not differentiable w.r.t. the '
+                                      'frames: detach them')
+        if st.scale != 1.0:
+            raise NotImplementedError('predictive densities of scaled statistics are not defined')
+        if st.data.shape[1] != dim:
+            raise ValueError(f'frames of dimension {st.data.shape[1]} for a model of dimension {dim}')
+        return st.as_cov(cov_type)
+    X = data_or_stats
+    if not isinstance(X, torch.Tensor) or X.dim() != 2:
+        raise TypeError('expected frames [T, D] or the statistics returned by '
+                        'model.sufficient_statistics(X)')
+    if torch.is_grad_enabled() and X.requires_grad:
+        raise NotImplementedError('predictive densities are not differentiable w.r.t. the '
+                                  'frames: detach them')
+    if X.shape[1] != dim:
+        raise NotImplementedError(
+            f'a [T, {X.shape[1]}] tensor is not frames of dimension {dim}: the predictive density '
+            'of dense (sample-averaged) statistics is not defined')
+    return FrameStats(X, cov_type)
+
+
+def predictive_llh(X_or_stats, table, cov_type):
+    '''l[t,k] = ln p(x_t | posterior of component k) -> [T, K] (`beer_predictive_llh`);
+    `table` [K, Q] from the family's `predictive_table()`.'''
+    table = table.view(1, -1) if table.dim() == 1 else table
+    st = predictive_frames(X_or_stats, _table_dim(table, cov_type), cov_type)
+    X = st.data
+    T, D = X.shape
+    tab = _hip.on_device(table, X.dtype)
+    out = torch.empty(T, tab.shape[0], dtype=X.dtype, device=X.device)
+    _hip.call('beer_predictive_llh', _hip.dtype_code(X.dtype), _hip.COV_CODE[cov_type], T, D,
+              tab.shape[0], _hip.ptr(X), _hip.ptr(tab), _hip.ptr(out))
+    return out
+
+
+def mixtureset_predictive(stats, table, log_mean_weights, S, G, cov_type):
+    '''log_norm [T, S]: ln sum_g exp(log_mean_weights[s,g] + l[t, s G + g]), the predictive
+    density of S mixtures of G components (`beer_mixtureset_predictive`; the [T, S G] matrix is
+    not formed).  `log_mean_weights` [S, G] = ln E[pi] or None (= 0).'''
+    if not isinstance(stats, FrameStats):
+        raise NotImplementedError('predictive densities take the lazy statistics of frames '
+                                  '(model.sufficient_statistics(X)): the predictive density of '
+                                  'dense (sample-averaged) statistics is not defined')
+    table = table.view(1, -1) if table.dim() == 1 else table
+    if table.shape[0] != S * G:
+        raise ValueError(f'{table.shape[0]} table rows for {S} x {G} mixture components')
+    st = predictive_frames(stats, _table_dim(table, cov_type), cov_type)
+    X = st.data
+    T, D = X.shape
+    tab = _hip.on_device(table, X.dtype)
+    lw = None if log_mean_weights is None else _hip.on_device(log_mean_weights, X.dtype)
+    if lw is not None and lw.numel() != S * G:
+        raise ValueError(f'{lw.numel()} weights for {S} x {G} mixture components')
+    log_norm = torch.empty(T, S, dtype=X.dtype, device=X.device)
+    _hip.call('beer_mixtureset_predictive', _hip.dtype_code(X.dtype), _hip.COV_CODE[cov_type], T,
+              D, S, G, _hip.ptr(X), _hip.ptr(tab), _hip.ptr(lw), _hip.ptr(log_norm))
+    return log_norm
 
 
 # ---- dense ("stats-in") statistics: the prior of a VAE ------------------------

@@ -112,6 +112,15 @@ class Normal(Model):
         nparams = self.mean_precision.natural_form()
         return self.mean_precision.likelihood_fn(nparams, stats)
 
+    def predictive_log_likelihood(self, data_or_stats):
+        '''ln p(x_t | posterior) [T]: the posterior-predictive (Student-t) density of every
+        frame, the integral of the Normal over the posterior of its mean and precision -- a
+        density, unlike exp(`expected_log_likelihood`).  Takes frames [T, D] or their lazy
+        statistics; dense or differentiable statistics raise `NotImplementedError`.'''
+        fn = self.mean_precision.likelihood_fn
+        table = self.mean_precision.posterior.predictive_table()
+        return kernels.predictive_llh(data_or_stats, table, fn.cov_type).view(-1)
+
     def accumulate(self, stats, parent_msg=None):
         fn = self.mean_precision.likelihood_fn
         if kernels.is_dense(stats):
@@ -156,6 +165,12 @@ class NormalSet(ModelSet):
         'Per-Gaussian expected log-likelihood [T, K] (fused kernel, no [T,Q]).'
         nparams = self.means_precisions.natural_form()
         return self.means_precisions.likelihood_fn(nparams, stats)
+
+    def predictive_log_likelihood(self, data_or_stats):
+        '''Per-Gaussian posterior-predictive (Student-t) log-density [T, K]
+        (`Normal.predictive_log_likelihood` for every member, one kernel).'''
+        table = self.means_precisions.posterior.predictive_table()
+        return kernels.predictive_llh(data_or_stats, table, self.cov_type)
 
     def accumulate(self, stats, resps):
         'resps^T @ phi(X) -> [K, Q], accumulated in fp64 on the GPU.'

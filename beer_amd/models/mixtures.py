@@ -149,6 +149,28 @@ class Mixture(DiscreteLatentModel):
                 ns.means_precisions.natural_form())
         return value
 
+    def _log_mean_weights(self):
+        '''ln E[pi] of every component (float64); of every LEAF when nested: the sum of the
+        ln E[pi] down to it -- the predictive twin of `_log_weights`.'''
+        lw = self.categorical.mean.double().log()
+        if not self.nested:
+            return lw
+        inner = self.modelset.leaf_log_mean_weights()
+        return (lw.to(inner.device)[:, None] + inner).reshape(-1)
+
+    def predictive_log_likelihood(self, data_or_stats):
+        '''ln p(x_t | posterior) [T]: the posterior-predictive density of the mixture,
+        ln sum_k E[pi_k] St_k(x_t) -- the mean weights and the Student-t predictive densities of
+        the Gaussians, not E[ln pi] and the expected log-likelihoods.  Frames [T, D] or their
+        lazy statistics; dense or differentiable statistics raise `NotImplementedError`.'''
+        ns = self.normalset
+        K = len(ns)
+        stats = kernels.predictive_frames(data_or_stats, ns.means_precisions.likelihood_fn.dim,
+                                          ns.cov_type)
+        return kernels.mixtureset_predictive(
+            stats, ns.means_precisions.posterior.predictive_table(),
+            self._log_mean_weights().view(1, K), 1, K, ns.cov_type).view(-1)
+
     def _dense_expected_log_likelihood(self, stats, labels):
         '''Statistics-in variant (prior of a VAE): same value, and the gradient
         w.r.t. the statistics flows through sum_k r_k l_k only (mixture.py:92).'''
@@ -335,6 +357,29 @@ class MixtureSet(ModelSet):
         self.cache['resps'] = resps.view(-1, S, G)
         return log_norm
 
+    def leaf_log_mean_weights(self):
+        '''ln E[pi] of every leaf Gaussian of every mixture [S, L] (float64): the sum of the
+        ln E[pi] of the leaf and of its ancestors inside this set (`leaf_log_weights` with
+        the logarithm of the mean in place of the mean of the logarithm).'''
+        lw = self.categoricalset.mean.double().log()
+        if not self.nested:
+            return lw
+        inner = self.modelset.leaf_log_mean_weights()
+        S, M = lw.shape
+        return (lw.to(inner.device)[:, :, None] + inner.view(S, M, -1)).reshape(S, -1)
+
+    def predictive_log_likelihood(self, data_or_stats):
+        '''Per-state posterior-predictive log-density [T, S]: ln sum_g E[pi_sg] St_sg(x_t), one
+        kernel (`kernels.mixtureset_predictive`), nothing cached.  Frames [T, D] or their lazy
+        statistics; dense or differentiable statistics raise `NotImplementedError`.'''
+        ns = self.normalset
+        S, G = len(self), self.n_leaves_per_mixture
+        stats = kernels.predictive_frames(data_or_stats, ns.means_precisions.likelihood_fn.dim,
+                                          ns.cov_type)
+        return kernels.mixtureset_predictive(
+            stats, ns.means_precisions.posterior.predictive_table(),
+            self.leaf_log_mean_weights(), S, G, ns.cov_type)
+
     def accumulate(self, stats, resps):
         'Joint (state x component) responsibilities -> weights + Gaussian stats.'
         ns = self.normalset
@@ -421,6 +466,10 @@ class TiedMixtureSet(ModelSet):
         tied = self.estep(stats)
         self.cache['tied'] = tied
         return tied[2]
+
+    def predictive_log_likelihood(self, data_or_stats):
+        raise NotImplementedError('TiedMixtureSet has no posterior-predictive density yet: the '
+                                  'predictive kernels take mixtures that own their Gaussians')
 
     def weights_accumulate(self, counts):
         '{weights parameter: statistics} from the counts C [S, K] (last column <- row sum).'

@@ -79,6 +79,11 @@ class JointModelSet(ModelSet):
         columns = [member.expected_log_likelihood(stats) for member in self.modelsets]
         return columns[0] if len(columns) == 1 else torch.cat(columns, dim=-1)
 
+    def predictive_log_likelihood(self, data_or_stats):
+        'The members\' posterior-predictive log-densities side by side, [T, len(self)].'
+        columns = [member.predictive_log_likelihood(data_or_stats) for member in self.modelsets]
+        return columns[0] if len(columns) == 1 else torch.cat(columns, dim=-1)
+
     def accumulate(self, stats, resps):
         collected = {}
         for member, first, last in self._spans():
@@ -112,6 +117,12 @@ class DynamicallyOrderedModelSet(_Wrapper):
         self.cache['order'] = list(range(len(self._inner))) if order is None else order
         return gather_columns(self._inner.expected_log_likelihood(stats), self.cache['order'])
 
+    def predictive_log_likelihood(self, data_or_stats, order=None):
+        'The inner set\'s posterior-predictive log-densities, column s that of pdf order[s].'
+        from ..hmm_kernels import gather_columns
+        order = list(range(len(self._inner))) if order is None else order
+        return gather_columns(self._inner.predictive_log_likelihood(data_or_stats), order)
+
     def accumulate(self, stats, resps):
         from ..hmm_kernels import scatter_columns
         by_pdf = scatter_columns(resps, self.cache['order'], len(self._inner))
@@ -137,6 +148,9 @@ class RepeatedModelSet(_Wrapper):
     def expected_log_likelihood(self, stats):
         once = self._inner.expected_log_likelihood(stats)
         return once.repeat(1, self.repeat)
+
+    def predictive_log_likelihood(self, data_or_stats):
+        return self._inner.predictive_log_likelihood(data_or_stats).repeat(1, self.repeat)
 
     def accumulate(self, stats, resps):
         per_copy = resps.reshape(resps.shape[0], self.repeat, len(self._inner))

@@ -565,11 +565,22 @@ class HMM(DiscreteLatentModel):
         return retval
 
     # -- DiscreteLatentModel interface ------------------------------------------------
-    def decode(self, data, inference_graph=None, scale=1.):
-        'Viterbi path mapped to pdf ids, LongTensor on the host (hmm.py:105-114).'
+    def _emission_llhs(self, stats, predictive):
+        '''The per-pdf matrix [T, S_total] a search runs on: the expected log-likelihoods, or
+        with `predictive` the posterior-predictive (Student-t, mean-weight) log-densities.'''
+        if predictive:
+            return self._emissions().predictive_log_likelihood(stats)
+        return self._emissions().expected_log_likelihood(stats)
+
+    def decode(self, data, inference_graph=None, scale=1., predictive=False):
+        '''Viterbi path mapped to pdf ids, LongTensor on the host (hmm.py:105-114).
+        `predictive` (not in the reference): the emissions are the posterior-predictive
+        densities (`predictive_log_likelihood` of the emission model) in place of the expected
+        log-likelihoods.  The arcs of the graph are used as they stand -- fixed log-probabilities,
+        or E[ln a] and E[ln pi] where they are learned: predictive arc weights are not formed.'''
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
+        pc_all = self._emission_llhs(stats, predictive)
         if getattr(getattr(graph, '_set', None), 'is_bound', False):
             self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
@@ -608,14 +619,18 @@ class HMM(DiscreteLatentModel):
         return hk.sample_paths(batch, pc_llhs, nsamples=nsamples, generator=generator,
                                map_pdf=True).cpu()
 
-    def log_evidence(self, data, inference_graph=None, scale=1., per_frame=False):
+    def log_evidence(self, data, inference_graph=None, scale=1., per_frame=False,
+                     predictive=False):
         '''ln p(x_0 .. x_{T-1}) under the model's expected log-likelihoods and the graph's
         (expected) log-transitions, summed over all state paths: a 0-d float64 tensor on the
         device, or with `per_frame` (value, [T] float64 of ln p(x_t | x_0 .. x_{t-1})).  Not in
-        the reference, whose `lognorm` (graph.py:289-326) is this number.  Otherwise as `decode`.'''
+        the reference, whose `lognorm` (graph.py:289-326) is this number.  With `predictive`
+        the emissions are the posterior-predictive densities -- the held-out likelihood of a
+        Bayesian model, never below the default's value; the arcs stay as they are (fixed, or
+        E[ln a] / E[ln pi] where learned).  Otherwise as `decode`.'''
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
+        pc_all = self._emission_llhs(stats, predictive)
         if getattr(getattr(graph, '_set', None), 'is_bound', False):
             self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)

@@ -95,6 +95,11 @@ class VAE(Model):
         # there; the prior's kernels get the latent samples on the GPU either way.
         return data.to(self.enc_mean_layer.weight.device)
 
+    def predictive_log_likelihood(self, data_or_stats):
+        raise NotImplementedError('a VAE has no closed-form posterior-predictive density: its '
+                                  'prior sees sample-averaged statistics of the latent variable, '
+                                  'for which the predictive density is not defined')
+
     def expected_log_likelihood(self, data, nsamples=1, llh_weight=1., kl_weight=1.,
                                 **kwargs):
         posts = self.posteriors(data)

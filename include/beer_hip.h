@@ -557,6 +557,56 @@ int beer_tied_accumulate(int dtype, int64_t T, int K, int S, const void* l, cons
                          void* stream);
 
 /* ------------------------------------------------------------------------
+ * Posterior-predictive densities (no reference counterpart: the reference and every
+ * entry point above compute exp(E_q[ln p(x | theta)]), which is not a density)
+ * ----------------------------------------------------------------------
+ * ln p(x | posterior) = ln of the integral of p(x | theta) q(theta): for the three Gaussian
+ * families a Student-t in closed form.  With kappa' = kappa / (kappa + 1):
+ *   diagonal   l = D [lnG(a + 1/2) - lnG(a)] + 1/2 sum_d ln(kappa' / (2 pi b_d))
+ *                  - (a + 1/2) sum_d log1p(kappa' (x_d - m_d)^2 / (2 b_d))
+ *   isotropic  l = lnG(a + D/2) - lnG(a) + D/2 ln(kappa' / (2 pi b))
+ *                  - (a + D/2) log1p(kappa' |x - m|^2 / (2 b))
+ *   full       l = lnG((nu + 1)/2) - lnG((nu + 1 - D)/2) + 1/2 ln|W| + D/2 ln(kappa' / pi)
+ *                  - ((nu + 1)/2) log1p(kappa' (x - m)^T W (x - m))
+ * each of the form l = c - h L(x), L >= 0, and l = c exactly at x = m.
+ *
+ * beer_*_predictive_table: what the frame kernels need per pdf, computed in fp64 and stored
+ * in `dtype`; standard parameters as for beer_*_expected_stats; `table` [K, Q], Q the
+ * family's statistics dimension (2 D + 2, D + 3, D^2 + D + 2), row k:
+ *   diagonal   [ m (D) | kappa' / (2 b_d) (D)                          | c | h ]
+ *   isotropic  [ m (D) | kappa' / (2 b)                                | c | h ]
+ *   full       [ m (D) | R (D x D row-major, upper triangular, zeros   | c | h ]
+ *                        below the diagonal), R^T R = kappa' W
+ * (R: the quadratic form is |R (x - m)|^2, a sum of squares of the centred frame.)  The
+ * differences of ln Gamma are formed without cancellation (shape and dof up to 1e6 and
+ * beyond keep c to fp64 rounding of its terms).  Full covariance: D <= 128. */
+int beer_ng_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                             const void* shape, const void* rates, void* table, void* stream);
+int beer_ing_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                              const void* shape, const void* rate, void* table, void* stream);
+int beer_nw_predictive_table(int dtype, int K, int D, const void* mean, const void* scale,
+                             const void* scale_matrix, const void* dof, void* table,
+                             void* stream);
+
+/* out[t,k] = l_k(x_t) from the raw frames X [T,D] and a table of K rows (no [T,Q]
+ * statistics).  BEER_F32 / BEER_F64; log1p is evaluated accurately relative to its argument
+ * (a trained Gaussian has arguments ~1e-5 multiplied by h ~ 1e4..1e6).  One kernel form.
+ * BEER_EINVAL where a tile of 64 frames and a chunk of table rows exceed a CU's LDS:
+ * 4 (65 D + 32 D + 48) bytes > 160 KiB diagonal float32, i.e. D > ~420 (half that in
+ * float64); full covariance D > 128 in float32, D > ~100 in float64. */
+int beer_predictive_llh(int dtype, int cov, int64_t T, int D, int K, const void* X,
+                        const void* table, void* out, void* stream);
+
+/* log_norm[t,s] = ln sum_g exp(log_mean_weights[s,g] + l_{s,g}(x_t)): the predictive
+ * density of S mixtures of G components (table row s G + g) by an online log-sum-exp
+ * inside the kernel -- the [T, S G] matrix is never written.  `log_mean_weights` [S,G]
+ * are ln E[pi] (NOT E[ln pi]); nullable (= 0).  Any G >= 1.  Same kernel and limits as
+ * beer_predictive_llh, which is this call with G = 1 and no weights. */
+int beer_mixtureset_predictive(int dtype, int cov, int64_t T, int D, int S, int G,
+                               const void* X, const void* table,
+                               const void* log_mean_weights, void* log_norm, void* stream);
+
+/* ------------------------------------------------------------------------
  * HMM inference over a ragged batch of utterances
  * ---------------------------------------------------------------------- */
 
