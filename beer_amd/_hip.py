@@ -239,6 +239,20 @@ def segments_team(route):
     return 1 << (route & 0xF)
 
 
+# BEER_SEGPOSTS_* of include/beer_hip.h: what `beer_hmm_segposts_route` returns
+SEGPOSTS_BLOCK, SEGPOSTS_ARCS_LDS, SEGPOSTS_BINS_LDS = 0x1000, 0x100, 0x200
+
+
+def segposts_family(route):
+    'BEER_SEGPOSTS_FAMILY: the kernel form of a `beer_hmm_segposts_route` value.'
+    return route & 0xF000
+
+
+def segposts_team(route):
+    'BEER_SEGPOSTS_TEAM: the lanes of a team of the expand kernel.'
+    return 1 << (route & 0xF)
+
+
 # BEER_ESTEP_* / BEER_ARG_* of include/beer_hip.h: what `beer_estep_route` takes and returns
 ESTEP_PLAIN, ESTEP_PACKED, ESTEP_IMAGE = 0, 1, 2
 ARG_PC_LLH, ARG_LOG_NORM, ARG_RESPS, ARG_LLH_SUM, ARG_LABELS, ARG_SCALED, ARG_LOG_WEIGHTS = \
@@ -433,6 +447,10 @@ SIGNATURES = {
     'beer_hmm_segment_margins': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i,
                                  c_p, c_p],
     'beer_hmm_segments_route': [c_i, c_p, c_i, c_i],               # (host only: no stream)
+    'beer_hmm_segpost_trellis': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_hmm_segment_posteriors': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                    c_l, c_i, c_p, c_p],
+    'beer_hmm_segposts_route': [c_i, c_p, c_i, c_i],               # (host only: no stream)
     'beer_hmm_trans_posteriors': [c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_path_posteriors': [c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_scatter': [c_i, c_p, c_i, c_p, c_p, c_d, c_p, c_p, c_p, c_p],

@@ -815,6 +815,67 @@ class lattice:
                     '.')
 
 
+class segments:
+    '''write the unit segments of all the utterances of a dataset with their posteriors,
+    "<outdir>/<uttid>.npz": every "unit" that begins at frame "start" and lasts until frame "end"
+    with a probability "post" of at least --min-post, sorted by (start, unit, end), the
+    "log_evidence" and the "units"; prints "<uttid> <log-evidence> <n_segments> <n_frames>".
+    --durations also saves the expected duration histogram of the shard, [n_units, max_dur]: how
+    many instances of a unit last exactly k + 1 frames'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
+        parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('-u', '--utts', help='utterances to process ("-" for stdin)')
+        parser.add_argument('--min-post', default=1e-3, type=float,
+                            help='keep the segments of at least this posterior (default 0.001)')
+        parser.add_argument('--max-dur', default=None, type=int,
+                            help='the longest segment, in frames (default: the utterance)')
+        parser.add_argument('--durations', metavar='FILE',
+                            help='save the expected duration histogram of the shard as "npy" '
+                                 '(needs --max-dur)')
+        parser.add_argument('model', help='phone-loop model')
+        parser.add_argument('dataset', help='data set')
+        parser.add_argument('outdir', help='output directory')
+
+    @staticmethod
+    def main(args, logger):
+        if not 0. <= args.min_post <= 1.:
+            raise SystemExit(f'--min-post: a probability in [0, 1], not {args.min_post}')
+        if args.max_dur is not None and args.max_dur < 1:
+            raise SystemExit(f'--max-dur: at least 1 frame, not {args.max_dur}')
+        if args.durations is not None and args.max_dur is None:
+            raise SystemExit('--durations needs --max-dur: the width of the histogram')
+        model = _load(args.model).to(_device())
+        dataset = _load(args.dataset)
+        alis = _load_alis(args.alis)
+        feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
+        use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        os.makedirs(args.outdir, exist_ok=True)
+        evidence, segs = beer.unit_segment_posteriors_batch(
+            model, feats, min_post=args.min_post, max_dur=args.max_dur, inference_graphs=use,
+            scale=args.acoustic_scale) if kept else ([], [])
+        units = np.asarray([str(u) for u in model.start_pdf])
+        total = 0
+        for uttid, value, utt, seg in zip(kept, evidence.cpu().tolist() if kept else [], feats,
+                                          segs):
+            start, end, unit, post = (v.cpu().numpy() for v in seg)
+            np.savez(os.path.join(args.outdir, f'{uttid}.npz'), start=start, end=end, unit=unit,
+                     post=post, log_evidence=np.float64(value), units=units)
+            print(uttid, '%.6f' % value, len(start), len(utt))
+            total += len(start)
+        if args.durations is not None:
+            hist = beer.unit_durations_batch(
+                model, feats, args.max_dur, inference_graphs=use,
+                scale=args.acoustic_scale).cpu().numpy() if kept else \
+                np.zeros((len(units), args.max_dur))
+            with open(args.durations, 'wb') as f:           # (np.save would append ".npy")
+                np.save(f, hist)
+        logger.info(f'wrote the unit segments of {len(kept)} utterances with a posterior of at '
+                    f'least {args.min_post:g}: {total / max(len(kept), 1):.1f} per utterance.')
+
+
 class posteriors:
     'state / phone posteriors of all the utterances of a dataset'
     EPS = 1e-5
@@ -855,4 +916,4 @@ class posteriors:
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
             mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, lattice,
-            boundaries]
+            segments, boundaries]

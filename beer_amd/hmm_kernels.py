@@ -17,7 +17,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'log_evidence', 'evidence_route', 'arc_posteriors', 'arcs_route',
            'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest',
            'max_marginals', 'maxmarg_route', 'SegmentMap', 'segment_map', 'segments_route',
-           'segment_margins', 'segments_within', 'check_segments']
+           'segment_margins', 'segments_within', 'check_segments', 'segposts_route',
+           'segment_posteriors', 'segments_above', 'check_segment_posteriors']
 
 
 class HmmBatch:
@@ -1008,6 +1009,139 @@ def segments_within(entry_frame, entry_cat, seg, beam):
     '''(start int64, end int64, unit int32, margin float64) of the cells of `segment_margins`'
     `seg` that are >= -beam, sorted by (start, unit, end); the frames indexed as `entry_frame`.'''
     at = torch.nonzero(_within(seg, float(beam)))
+    start = entry_frame[at[:, 0]]
+    return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
+
+
+def segposts_route(batch, n_cat, max_closure=0):
+    '''beer_hmm_segposts_route: the form `segment_posteriors` runs on (the trellis kernel's arcs
+    and bins in LDS or not, and in the low bits the team size of the expand kernel,
+    `_hip.segposts_team`); HipInvalid where it refuses.'''
+    route = _hip.lib().beer_hmm_segposts_route(_hip.dtype_code(batch.dtype), batch.ref(),
+                                               int(n_cat), int(max_closure))
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'segment_posteriors: {n_cat} categories with closures of up to {max_closure} states '
+            f'on graphs of up to {batch.struct.max_states} states: at least one category, two '
+            "fp64 rows of the graph in the CU's 160 KB of LDS (about 10000 states), and four fp64 "
+            'rows of the largest closure in 64 KB (2046 states)')
+    return route
+
+
+def check_segment_posteriors(min_post, max_dur, what='segment_posteriors'):
+    '''(min_post as a float, max_dur as an int or None); ValueError for a min_post that is
+    negative, NaN or above 1, and for max_dur < 1.'''
+    min_post = float(min_post)
+    if not 0. <= min_post <= 1.:
+        raise ValueError(f'{what}: min_post is a probability in [0, 1], not {min_post}')
+    if max_dur is not None:
+        if int(max_dur) != max_dur or max_dur < 1:
+            raise ValueError(f'{what}: max_dur is an integer >= 1, not {max_dur}')
+        max_dur = int(max_dur)
+    return min_post, max_dur
+
+
+def _above(values, min_post):
+    'values >= min_post, and > 0 (min_post = 0 keeps every possible cell).'
+    return (values >= min_post) & (values > 0)
+
+
+def _check_entries(entries, n_frames, n_cat, what):
+    '(entry_frame int64, entry_cat int32) of the caller; ValueError when unsorted or out of range.'
+    if not isinstance(entries, (tuple, list)) or len(entries) != 2:
+        raise ValueError(f'{what}: entries is a pair (entry_frame, entry_cat)')
+    frame, cat = (e if torch.is_tensor(e) else torch.as_tensor(np.asarray(e)) for e in entries)
+    if frame.dim() != 1 or cat.dim() != 1 or len(frame) != len(cat):
+        raise ValueError(f'{what}: entry_frame and entry_cat are two vectors of one length')
+    if frame.dtype.is_floating_point or cat.dtype.is_floating_point:
+        raise ValueError(f'{what}: entries are integers')
+    if len(frame):
+        f, c = frame.cpu().numpy().astype(np.int64), cat.cpu().numpy().astype(np.int64)
+        if f.min() < 0 or f.max() >= n_frames or c.min() < 0 or c.max() >= n_cat:
+            raise ValueError(f'{what}: an entry outside the batch\'s {n_frames} frames or its '
+                             f'{n_cat} categories')
+        if (np.diff(f) < 0).any():
+            raise ValueError(f'{what}: the entries are not sorted by frame')
+    return frame.to(torch.int64), cat.to(torch.int32)
+
+
+def segment_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, min_post, max_dur, seg_map=None,
+                       entries=None):
+    '''(evidence [nutt] fp64, starts [n_frames, n_cat], entry_frame [n_entries] int64, entry_cat
+    [n_entries] int32, seg [n_entries, max_dur]) on the device, `starts` and `seg` of the batch's
+    dtype: the segment posteriors (`beer_hmm_segpost_trellis`, `beer_hmm_segment_posteriors`), the
+    sum-product twin of `segment_margins`.  `evidence` is ln p(x) of every utterance, `starts`
+    the start posteriors (`arc_posteriors`' per-frame rows).  The entries are the cells (frame,
+    category) of `starts` that are >= `min_post` and > 0, in row-major order, or with
+    `entries=(entry_frame, entry_cat)` the caller's, sorted by frame (those `segment_margins`
+    returned, for instance: a lattice's arcs then get their posteriors).  seg[n, k] is the
+    probability that category entry_cat[n] begins at frame entry_frame[n] (indexed as in the
+    batch's frame offsets) and lasts exactly k more frames -- the next boundary, or the utterance's
+    end, follows frame entry_frame[n] + k; 0 where that is impossible or the segment would pass the
+    utterance's end.  With max_dur >= T a row sums to its entry's start posterior.  `seg_map`:
+    `segment_map` of the batch's distinct graphs and these categories, built here when not given.
+    The entry selection is one `torch.nonzero`, which waits for the device.  ValueError, before
+    any device work: a min_post that is negative, NaN or above 1, max_dur < 1 or None, bad
+    categories, a segment map of another shape, unsorted or out-of-range entries.'''
+    what = 'segment_posteriors'
+    min_post, max_dur = check_segment_posteriors(min_post, max_dur)
+    if max_dur is None:
+        raise ValueError(f'{what}: max_dur is an integer >= 1, not None')
+    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat)
+    n_cat = int(n_cat)
+    if seg_map is None:
+        seg_map = segment_map(batch.source_graphs, arcs.cpu(), inits.cpu(), n_cat)
+    if seg_map.n_cat != n_cat or seg_map.n_graphs != len(batch.n_states):
+        raise ValueError(f'{what}: a segment map of {seg_map.n_graphs} graphs and '
+                         f'{seg_map.n_cat} categories for {len(batch.n_states)} and {n_cat}')
+    if entries is not None:
+        entries = _check_entries(entries, batch.n_frames, n_cat, what)
+    dev, dt = batch.device, batch.dtype
+    segposts_route(batch, n_cat, seg_map.max_closure)
+    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    starts = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev)
+    if batch.nutt == 0:
+        return evidence, starts, torch.empty(0, dtype=torch.int64, device=dev), \
+            torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, max_dur, dtype=dt, device=dev)
+    dcode = _hip.dtype_code(dt)
+    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+    if arcs.device.type != 'cuda':
+        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+    if inits.device.type != 'cuda':
+        host['inits'] = inits
+    up = _hip.upload(host, dev)
+    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
+                       up['state_off'].data_ptr())
+    # the two trellises and the normalisers (an element more: no pointer is NULL)
+    trellis = torch.empty(2 * batch.n_elems + batch.n_frames + 1, dtype=torch.float64, device=dev)
+    alpha, y, norm = trellis[:batch.n_elems], trellis[batch.n_elems:2 * batch.n_elems], \
+        trellis[2 * batch.n_elems:]
+    _hip.call('beer_hmm_segpost_trellis', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              ctypes.byref(amap), n_cat, _hip.ptr(alpha), _hip.ptr(y), _hip.ptr(norm),
+              _hip.ptr(starts), _hip.ptr(evidence))
+    if entries is None:
+        at = torch.nonzero(_above(starts, min_post))        # (row-major; waits for the device)
+        entry_frame = at[:, 0].contiguous()
+        entry_cat = at[:, 1].to(torch.int32)
+    else:
+        entry_frame, entry_cat = (e.to(dev).contiguous() for e in entries)
+    entry_off = torch.searchsorted(entry_frame, batch.bufs['frame_off'])
+    seg = torch.empty(len(entry_frame), max_dur, dtype=dt, device=dev)
+    _hip.call('beer_hmm_segment_posteriors', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              ctypes.byref(seg_map.struct(dev)), n_cat, _hip.ptr(alpha), _hip.ptr(y),
+              _hip.ptr(norm), _hip.ptr(evidence), _hip.ptr(entry_frame), _hip.ptr(entry_cat),
+              _hip.ptr(entry_off), len(entry_frame), max_dur, _hip.ptr(seg))
+    return evidence, starts, entry_frame, entry_cat, seg
+
+
+def segments_above(entry_frame, entry_cat, seg, min_post):
+    '''(start int64, end int64, unit int32, post float64) of the cells of `segment_posteriors`'
+    `seg` that are >= min_post and > 0, sorted by (start, unit, end); the frames indexed as
+    `entry_frame`.'''
+    at = torch.nonzero(_above(seg, float(min_post)))
     start = entry_frame[at[:, 0]]
     return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
 

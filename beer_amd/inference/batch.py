@@ -34,7 +34,7 @@ from .objectives import EvidenceLowerBoundInstance
 __all__ = ['accumulate_elbo', 'pack_utterances', 'decode_batch', 'sample_paths_batch',
            'log_evidence_batch', 'unit_starts_batch', 'unit_counts_batch',
            'unit_start_margins_batch', 'unit_segments_batch', 'ShardStatics',
-           'decode_nbest_batch']
+           'decode_nbest_batch', 'unit_segment_posteriors_batch', 'unit_durations_batch']
 
 # Scratch of one sub-batch (responsibilities, per-state likelihoods, trellis): up to
 # three sub-batches are in flight, so a sub-batch may take an eighth of what is free on
@@ -821,6 +821,88 @@ def unit_segments_batch(model, utterances, beam=10., max_dur=None, inference_gra
                           (start.to(torch.int32), end.to(torch.int32), unit, margin))))
     return (torch.cat(bests) if bests else
             torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
+
+
+def _segment_posteriors_batches(what, model, utterances, min_post, max_dur, inference_graphs,
+                                scale, max_frames):
+    '''(batch, lengths, `hk.segment_posteriors`' outputs) per sub-batch of a shard, under the
+    unit-start categories; the arguments are checked before the first sub-batch is built.'''
+    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+        isinstance(utterances[0], torch.Tensor)
+    if not packed:
+        utterances = list(utterances)
+    if inference_graphs is not None:
+        nutt = len(utterances[1]) if packed else len(utterances)
+        if len(inference_graphs) != nutt:
+            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
+                             'utterances')
+    if not hasattr(model, 'start_pdf'):
+        raise ValueError(f'{what}: a phone loop (a model with units), not '
+                         f'{type(model).__name__}')
+    n_units = len(model.start_pdf)
+    cats = {}                       # the categories of every distinct graph, built once per call
+
+    def categories(graph):
+        if id(graph) not in cats:
+            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+        return cats[id(graph)]
+
+    # decode_batch's scratch with two fp64 trellises (â and Y) in place of the back-pointers; a
+    # normaliser and a row of start posteriors per frame besides (sized for float64).  The
+    # segment rows of the entries come on top: n_entries * max_dur values.
+    for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
+                                                       max_frames, 8 + 8 * n_units, 16):
+        pairs = [categories(g) for g in batch.distinct_graphs]
+        dur = max(max(run_lengths), 1) if max_dur is None else max_dur
+        yield batch, run_lengths, hk.segment_posteriors(
+            batch, pc_llhs, [p[0] for p in pairs], [p[1] for p in pairs], n_units, min_post, dur)
+
+
+def unit_segment_posteriors_batch(model, utterances, min_post=1e-3, max_dur=None,
+                                  inference_graphs=None, scale=1., max_frames=1 << 20):
+    '''The log-evidence and the unit segments with their posteriors of every utterance of a
+    shard: (float64 [nutt], list of (start, end, unit, post) per utterance) on the device
+    (`PhoneLoop.unit_segment_posteriors`, batched): the segments whose posterior is >= `min_post`
+    (and > 0), frames counted from the utterance's first, sorted by (start, unit, end).  `max_dur`
+    None: the length of the longest utterance of a sub-batch, which cuts nothing.'''
+    what = 'unit_segment_posteriors_batch'
+    min_post, max_dur = hk.check_segment_posteriors(min_post, max_dur, what)
+    out, totals = [], []
+    for batch, run_lengths, (evidence, _, frame, unit, seg) in _segment_posteriors_batches(
+            what, model, utterances, min_post, max_dur, inference_graphs, scale, max_frames):
+        totals.append(evidence)
+        start, end, unit, post = hk.segments_above(frame, unit, seg, min_post)
+        first = batch.bufs['frame_off']
+        utt = torch.searchsorted(first[1:].contiguous(), start, right=True)
+        counts = torch.bincount(utt, minlength=len(run_lengths)).tolist()
+        start, end = start - first[utt], end - first[utt]
+        out += list(zip(*(torch.split(v, counts) for v in
+                          (start.to(torch.int32), end.to(torch.int32), unit, post))))
+    return (torch.cat(totals) if totals else
+            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
+
+
+def unit_durations_batch(model, utterances, max_dur, inference_graphs=None, scale=1.,
+                         max_frames=1 << 20):
+    '''The expected duration histogram of a shard: float64 [n_units, max_dur] on the device, the
+    sum over the utterances of `PhoneLoop.unit_durations` -- entry (u, k) is the expected number of
+    instances of unit u that last exactly k + 1 frames.  `max_dur` is required: the shard's
+    utterances share the histogram's width; instances longer than it are left out.'''
+    what = 'unit_durations_batch'
+    _, max_dur = hk.check_segment_posteriors(0., max_dur, what)
+    if max_dur is None:
+        raise ValueError(f'{what}: max_dur is an integer >= 1, not None')
+    hist = None
+    for _, _, (_, _, _, unit, seg) in _segment_posteriors_batches(
+            what, model, utterances, 0., max_dur, inference_graphs, scale, max_frames):
+        if hist is None:
+            hist = torch.zeros(len(model.start_pdf), max_dur, dtype=torch.float64,
+                               device=seg.device)
+        hist.index_add_(0, unit.long(), seg.double())
+    if hist is None:                                        # (no utterance)
+        hist = torch.zeros(len(model.start_pdf), max_dur, dtype=torch.float64,
+                           device=_hip.require_device())
+    return hist
 
 
 def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame,

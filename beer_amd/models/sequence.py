@@ -785,11 +785,59 @@ def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, sc
     return best[0], start.to(torch.int32), end.to(torch.int32), unit, margin
 
 
+def _segment_posteriors_of(model, data, min_post, max_dur, inference_graph, scale, what):
+    '`hk.segment_posteriors` of one utterance under the unit-start categories: its five outputs.'
+    min_post, max_dur = hk.check_segment_posteriors(min_post, max_dur, what)
+    graph = model.graph if inference_graph is None else inference_graph
+    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+    n_units = len(model.start_pdf)
+    src, _ = graph.out_arcs()
+    cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_units)
+    stats = model.sufficient_statistics(data)
+    pc_all = model._emissions().expected_log_likelihood(stats)
+    if getattr(getattr(graph, '_set', None), 'is_bound', False):
+        model._bound_set(graph).refresh(pc_all.dtype)
+    batch = model._batch_of_one(graph, len(stats), pc_all.dtype)
+    return hk.segment_posteriors(batch, hk.gather(batch, pc_all, scale), *cats, n_units, min_post,
+                                 max(len(stats), 1) if max_dur is None else max_dur)
+
+
+def _unit_segment_posteriors(model, data, min_post=1e-3, max_dur=None, inference_graph=None,
+                             scale=1.):
+    '''(log_evidence, start, end, unit, post) on the device: ln p(x) (0-d float64) and the unit
+    segments with their posteriors -- every (unit, start, end) such that, with probability
+    `post` >= `min_post` (float64, and > 0), the unit BEGINS at frame `start` (as `unit_starts`
+    has it) and the next unit begins at frame `end` + 1 (or the utterance ends with frame `end`).
+    The sum-product twin of `unit_segments`: `start`, `end`, `unit` are int32, the units numbered
+    in `start_pdf` order; sorted by (start, unit, end).  `max_dur`: the longest segment looked for,
+    in frames (None: the utterance's length).  With `min_post` = 0 the posteriors of the segments
+    that cover a frame sum to 1.  Otherwise as `decode`.'''
+    evidence, _, frame, unit, seg = _segment_posteriors_of(
+        model, data, min_post, max_dur, inference_graph, scale, 'unit_segment_posteriors')
+    start, end, unit, post = hk.segments_above(frame, unit, seg, min_post)
+    return evidence[0], start.to(torch.int32), end.to(torch.int32), unit, post
+
+
+def _unit_durations(model, data, max_dur=None, inference_graph=None, scale=1.):
+    '''The expected duration histogram [n_units, max_dur], float64 on the device, the units in
+    `start_pdf` order: entry (u, k) is the expected number of instances of unit u that last
+    exactly k + 1 frames, the sum over the start frames s of the posterior of the segment
+    (u, s, s + k) -- the soft version of counting the durations on `decode`'s path.  `max_dur`
+    None: the utterance's length, and row u sums to the expected count of unit u
+    (`unit_starts(...).sum(0)`).  Otherwise as `decode`.'''
+    _, _, _, unit, seg = _segment_posteriors_of(
+        model, data, 0., max_dur, inference_graph, scale, 'unit_durations')
+    hist = torch.zeros(len(model.start_pdf), seg.shape[1], dtype=torch.float64, device=seg.device)
+    return hist.index_add_(0, unit.long(), seg.double())
+
+
 class PhoneLoop(HMM):
     'Phone-loop HMM with a prior over the phone (unigram) weights.'
     unit_starts = _unit_starts
     unit_start_margins = _unit_start_margins
     unit_segments = _unit_segments
+    unit_segment_posteriors = _unit_segment_posteriors
+    unit_durations = _unit_durations
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
@@ -968,6 +1016,8 @@ class BigramPhoneLoop(HMM):
     unit_starts = _unit_starts
     unit_start_margins = _unit_start_margins
     unit_segments = _unit_segments
+    unit_segment_posteriors = _unit_segment_posteriors
+    unit_durations = _unit_durations
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,

@@ -1410,6 +1410,103 @@ size_t beer_hmm_segments_scratch_doubles(int dtype, const beer_batch* batch_h);
 #define BEER_SEGMENTS_TEAM(route) (1 << ((route) & 0xF))
 int beer_hmm_segments_route(int dtype, const beer_batch* batch_h, int n_cat, int max_closure);
 
+/* Segment posteriors: the sum-product twin of the unit segment lattice.  Categories, boundaries
+ * and "the path HAS THE SEGMENT (c, s, e)" are exactly those of beer_hmm_segment_trellis above:
+ * frame 0 is a boundary labelled init_cat[z_0], frame t >= 1 one labelled arc_cat(z_{t-1} -> z_t)
+ * when that is >= 0; the segment runs from boundary s with label c through frames without a
+ * boundary to e, where e + 1 is a boundary or e = T - 1.
+ *   post(c, s, e) = P(the path has the segment (c, s, e) | x_0 .. x_{T-1})
+ * under pc_llhs and the graph's init / arc / final weights.  With â_t, c_t as
+ * beer_hmm_log_evidence documents them, f = ln sum_j exp(â_{T-1}(j) + final_j) and the normalised
+ * backward values of beer_hmm_arc_posteriors:
+ *   b_{T-1}(j) = final_j - f
+ *   b_{t-1}(i) = ln sum over arcs i->j of exp(w_ij + l_t(j) + b_t(j)) - c_t
+ *   Y_{T-1}(i) = final_i - f
+ *   Y_t(i)     = ln sum over arcs i->j with arc_cat >= 0 of exp(w_ij + l_{t+1}(j) + b_{t+1}(j))
+ *                - c_{t+1}                                                              t < T-1
+ *   r_s(j)     = â_0(j) if init_cat[j] == c else -inf                                   s = 0
+ *   r_s(j)     = ln sum over arcs i->j with arc_cat == c of exp(â_{s-1}(i) + w_ij)
+ *                + l_s(j) - c_s                                                         s >= 1
+ *   r_t(j)     = ln sum over arcs i->j with arc_cat == -1 of exp(r_{t-1}(i) + w_ij)
+ *                + l_t(j) - c_t                                                         t = s+1 ..
+ *   post(c,s,e) = sum_i exp(r_e(i) + Y_e(i))
+ * sum_e post(c, s, e) is the start posterior frame_out[s, c] of beer_hmm_arc_posteriors, and
+ * ln p(x) = sum_t c_t + f.  Only members of the closure of c (beer_seg_map) can carry r, and
+ * r_t(j) <= â_t(j): the expand kernel carries the ratio rho_t(j) = exp(r_t(j) - â_t(j)) in [0, 1],
+ *   rho_t(j) = sum over arcs i->j of category -1 of
+ *              rho_{t-1}(i) exp((â_{t-1}(i) + w_ij) + ((l_t(j) - c_t) - â_t(j)))
+ *   post(c,s,e) = sum_j rho_e(j) exp(â_e(j) + Y_e(j))
+ * one exponential of a log-probability per arc and step, no logarithm; an underflow is 0.
+ * Arithmetic.  Differences, sums, the trellises, the rows and the folds are fp64; exp / log are in
+ * the model's precision, as in beer_hmm_arc_posteriors.
+ *
+ * beer_hmm_segpost_trellis: one launch, one workgroup of 256 threads per utterance, the shape of
+ * beer_hmm_arc_posteriors.
+ *   map, n_cat the categories, n_cat >= 1
+ *   alpha, y   [n_elems] fp64 each, packed like pc_llhs, written (=): â_t(j) and Y_t(i) (-inf:
+ *              unreachable, or nothing goes on); of an utterance whose evidence is -inf their
+ *              content is unspecified
+ *   norm       [n_frames] fp64, written (=): c_t, up to the frame at which an utterance died
+ *   frame_out  [n_frames, n_cat] of dtype, written (=): the start posteriors, with the meaning of
+ *              beer_hmm_arc_posteriors' frame_out
+ *   evidence   [nutt] fp64, written (=): ln p(x); 0 for an utterance of no frames, as
+ *              beer_hmm_log_evidence has it
+ * Every value of alpha and y is written by the thread that owns its state, every sum of a row in
+ * the row's order: the two trellises, norm and evidence are the same bits on every run.  The bins
+ * of frame_out take atomic adds, whose order is not fixed.
+ * Edges.  -inf log-likelihoods and unreachable states are legal.  An utterance whose evidence is
+ * -inf gets zeros in frame_out; T = 1 and an utterance of no frames are legal; inputs without NaN
+ * give no NaN; pc_llhs is not modified.
+ * EINVAL, checked before anything is launched: where beer_hmm_arc_posteriors refuses the batch
+ * with frame_out given; a NULL map or map member; n_cat < 1; with utterances in the batch a NULL
+ * pc_llhs, alpha, y, norm, frame_out or evidence. */
+int beer_hmm_segpost_trellis(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                             const beer_arc_map* map, int n_cat, double* alpha, double* y,
+                             double* norm, void* frame_out, double* evidence, void* stream);
+
+/* beer_hmm_segment_posteriors: expands a list of entries (frame, category) into their segment
+ * posteriors, from the trellises, norm and evidence that beer_hmm_segpost_trellis wrote for the
+ * same batch, pc_llhs and categories.  entry_frame, entry_cat, entry_off as
+ * beer_hmm_segment_margins takes them.
+ *   out         [n_entries, max_dur] of dtype, written (=): column k holds post(c, s, s + k); 0
+ *               where the segment is impossible or runs past the utterance
+ * A team of L lanes handles an entry (L: the smallest power of two in 4 .. 256 that is
+ * >= max_closure; lanes stride over larger closures), a workgroup of 256 threads holds 256 / L
+ * teams, each with four fp64 rows of max_closure (at least 1) doubles (rho and â of the closure,
+ * ping-pong) and eight 8-byte slots in LDS.  The fold over a team is a sum in a fixed order
+ * (cross-lane moves within a wave, then the waves' partial sums in order), no atomic add: given
+ * the same trellises and entries, `out` is the same bits on every run.  An entry whose category is
+ * outside [0, n_cat), whose frame is outside its utterance or whose utterance has evidence -inf
+ * gets zeros in its row.
+ * EINVAL where beer_hmm_segpost_trellis refuses the batch; a NULL seg map or member;
+ * max_closure < 0 or above max_states; (256 / L) (32 max(max_closure, 1) + 64) bytes above 64 KiB
+ * (max_closure > 2046); n_entries < 0; max_dur < 1; with entries and utterances a NULL argument. */
+int beer_hmm_segment_posteriors(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                                const beer_seg_map* seg_map, int n_cat, const double* alpha,
+                                const double* y, const double* norm, const double* evidence,
+                                const int64_t* entry_frame, const int32_t* entry_cat,
+                                const int64_t* entry_off, int64_t n_entries, int max_dur,
+                                void* out, void* stream);
+
+/* The form the two launches pick (host only), built from the launchers' own plan.  With S =
+ * max_states, A = max_arcs, w = 4 / 8 bytes of the dtype, rows = 16 S + 128 bytes and arcs =
+ * 4 (S + 2 + 2 A) + w (A + 1) bytes as beer_hmm_arcs_route has them:
+ *   BEER_SEGPOSTS_BLOCK     the trellis kernel: one workgroup of 256 threads per utterance
+ *   BEER_SEGPOSTS_ARCS_LDS  its arc lists and categories are kept in LDS: rows + arcs <= 64 KiB
+ *   BEER_SEGPOSTS_BINS_LDS  a frame's bins are fp64 in LDS and written as a row once per frame:
+ *                           n_cat <= 1024 and rows <= 96 KiB; else the rows of frame_out are
+ *                           zeroed and take global atomic adds in the dtype
+ *   BEER_SEGPOSTS_TEAM(route)  the lanes L of a team of the expand kernel, 4 .. 256
+ * BEER_EINVAL exactly where beer_hmm_segpost_trellis or, with this max_closure,
+ * beer_hmm_segment_posteriors refuses the batch and n_cat.  The trellis kernel keeps nothing
+ * besides the two trellises and norm: there is no scratch to size. */
+#define BEER_SEGPOSTS_BLOCK 0x1000
+#define BEER_SEGPOSTS_ARCS_LDS 0x100
+#define BEER_SEGPOSTS_BINS_LDS 0x200
+#define BEER_SEGPOSTS_FAMILY(route) ((route) & 0xF000)
+#define BEER_SEGPOSTS_TEAM(route) (1 << ((route) & 0xF))
+int beer_hmm_segposts_route(int dtype, const beer_batch* batch_h, int n_cat, int max_closure);
+
 /* One-hot posteriors of a given state path (hmm.py:42-58: viterbi=True /
  * state_path= branches): gamma one-hot, xi_sum[p_t, p_t+1] += 1,
  * gamma0_sum[p_0] += 1. */
