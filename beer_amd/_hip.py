@@ -336,6 +336,7 @@ def frames_llh_backward_route(dtype_code_, cov, T, D, K, workspace_bytes):
     return lib().beer_frames_llh_backward_route(dtype_code_, cov, T, D, K, workspace_bytes)
 
 
+CMLLR_MAX_DIM = 63          # BEER_CMLLR_MAX_DIM of include/beer_hip.h
 BIGRAM_MAX_PHONES = 128     # BEER_BIGRAM_MAX_PHONES of include/beer_hip.h
 BIGRAM_MAX_STATES = 512     # BEER_BIGRAM_MAX_STATES
 
@@ -413,6 +414,11 @@ SIGNATURES = {
     'beer_ing_predictive_table': _four,
     'beer_predictive_llh': [c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p],
     'beer_mixtureset_predictive': [c_i, c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    'beer_cmllr_frame_params': [c_i, c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    'beer_cmllr_accumulate': [c_i, c_l, c_i, c_i, ctypes.c_int32, ctypes.c_int32, c_p, c_p, c_p,
+                              c_p, c_p, c_z, ctypes.c_int32, c_p, c_p, c_p, c_p, c_z, c_p],
+    'beer_cmllr_apply': [c_i, c_l, c_i, ctypes.c_int32, ctypes.c_int32, c_p, c_p, c_p, c_p, c_p,
+                         c_p, c_p],
     'beer_hmm_gather': [c_i, c_p, c_i, c_p, c_d, c_p, c_p],
     'beer_hmm_forward_backward': [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_posteriors_fused': [c_i, c_p, c_i, c_p, c_d, c_p, c_p, c_p, c_i, c_p, c_p, c_p,
@@ -487,6 +493,7 @@ HOST_SIGNATURES = {
     'beer_graphset_export': [c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'beer_graphset_image_bytes': [c_p, c_i, c_p],
     'beer_graphset_image': [c_p, c_i, c_p, ctypes.c_uint64, c_p],
+    'beer_cmllr_table': [ctypes.c_int32, ctypes.c_int32, c_p, c_p, ctypes.c_int32, c_p, c_p],
 }
 
 # size queries: return a byte count, take no stream
@@ -504,6 +511,7 @@ SIZE_QUERIES = {
     'beer_hmm_maxmarg_scratch_doubles': [c_i, c_p],
     'beer_hmm_segments_scratch_doubles': [c_i, c_p],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
+    'beer_cmllr_workspace_bytes': [c_i, c_i, c_l],
 }
 
 

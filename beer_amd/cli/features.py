@@ -117,4 +117,52 @@ class archive:
         logger.info(f'created archive from {counts} features files')
 
 
-COMMANDS = [extract, archive]
+class transform:
+    '''apply per-speaker affine transforms (`beer hmm adapt`) to a features archive: writes the
+    transformed "npz" archive and "<out_archive>.logdet", one "<uttid> <T ln|det A|>" per
+    line -- the term to add to a score of the transformed utterance when scores under
+    different transforms are compared.  Utterances of a speaker without a transform are
+    copied (0 in the file)'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('archive', help='features archive ("npz")')
+        parser.add_argument('utt2spk', help='text file, "<uttid> <speaker>" per line')
+        parser.add_argument('transforms', help='transforms of "beer hmm adapt" ("npz")')
+        parser.add_argument('out_archive', help='output features archive ("npz")')
+
+    @staticmethod
+    def main(args, logger):
+        import torch
+        from ..adaptation import AffineTransforms
+        from .hmm import read_utt2spk
+        utt2spk = read_utt2spk(args.utt2spk)
+        transforms = AffineTransforms.load(args.transforms)
+        with np.load(args.archive) as feats:
+            uttids = list(feats.keys())
+            for uttid in uttids:
+                if uttid not in utt2spk:
+                    raise SystemExit(f'utt2spk: no speaker for utterance "{uttid}"')
+            mats = [np.ascontiguousarray(feats[u]) for u in uttids]
+        speakers = [utt2spk[u] for u in uttids]
+        out, dtypes = {}, {m.dtype for m in mats}
+        # (one launch per dtype of the archive: the kernel writes the frames' own type)
+        for dtype in dtypes:
+            pick = [n for n, m in enumerate(mats) if m.dtype == dtype]
+            work = np.float32 if dtype == np.float32 else np.float64
+            done = transforms.apply([torch.from_numpy(mats[n].astype(work)) for n in pick],
+                                    [speakers[n] for n in pick])
+            for n, y in zip(pick, done):
+                out[uttids[n]] = y.cpu().numpy().astype(dtype)
+        terms = transforms.log_det_terms([len(m) for m in mats], speakers)
+        with open(args.out_archive, 'wb') as f:           # (np.savez would append ".npz")
+            np.savez(f, **{u: out[u] for u in uttids})
+        with open(args.out_archive + '.logdet', 'w') as f:
+            for uttid, term in zip(uttids, terms.tolist()):
+                f.write(f'{uttid} {term:.6f}\n')
+        known = sum(s in transforms.names for s in speakers)
+        logger.info(f'transformed {known} of {len(uttids)} utterances '
+                    f'({len(uttids) - known} copied).')
+
+
+COMMANDS = [extract, archive, transform]

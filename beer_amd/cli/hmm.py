@@ -876,6 +876,96 @@ class segments:
                     f'least {args.min_post:g}: {total / max(len(kept), 1):.1f} per utterance.')
 
 
+def read_utt2spk(path):
+    '{utterance id: speaker} of a text file, one "<uttid> <speaker>" per line.'
+    out = {}
+    with open(path) as f:
+        for n, line in enumerate(f, start=1):
+            tokens = line.split()
+            if not tokens:
+                continue
+            if len(tokens) != 2:
+                raise SystemExit(f'{path}:{n}: expected "<uttid> <speaker>", got {line.strip()!r}')
+            out[tokens[0]] = tokens[1]
+    return out
+
+
+def speakers_of(uttids, utt2spk):
+    '''(names, index per utterance): the speakers of `uttids` in order of first appearance.  An
+    utterance without a speaker is an error that names it.'''
+    names, where, idx = [], {}, []
+    for uttid in uttids:
+        if uttid not in utt2spk:
+            raise SystemExit(f'utt2spk: no speaker for utterance "{uttid}"')
+        spk = utt2spk[uttid]
+        if spk not in where:
+            where[spk] = len(names)
+            names.append(spk)
+        idx.append(where[spk])
+    return names, idx
+
+
+class adapt:
+    '''estimate one affine feature transform per speaker (constrained MLLR) under the model and
+    write them as an "npz" archive ("speakers", "W" [n, D, D + 1]); prints
+    "<speaker> <n_frames> <gain per frame>" per speaker, the gain of the auxiliary function
+    summed over the rounds (a lower bound of the gain in log-likelihood per frame)'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('-a', '--alis', help='alignment graphs in a "npz" archive')
+        parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
+        parser.add_argument('--iters', type=int, default=3,
+                            help='rounds of statistics and estimation (default 3)')
+        parser.add_argument('--sweeps', type=int, default=20,
+                            help='sweeps over the rows of a transform per round (default 20)')
+        parser.add_argument('--min-count', type=float, default=500.,
+                            help='frames a speaker needs to get a transform (default 500)')
+        parser.add_argument('--init', metavar='TRANSFORMS',
+                            help='transforms to start from (default: the identity)')
+        parser.add_argument('-u', '--utts', help='utterances to use ("-" for stdin)')
+        parser.add_argument('model', help='hmm based model')
+        parser.add_argument('dataset', help='data set')
+        parser.add_argument('utt2spk', help='text file, "<uttid> <speaker>" per line')
+        parser.add_argument('out', help='output transforms ("npz")')
+
+    @staticmethod
+    def main(args, logger):
+        if args.iters < 1 or args.sweeps < 1:
+            raise SystemExit('--iters and --sweeps: at least 1')
+        utt2spk = read_utt2spk(args.utt2spk)
+        model = _load(args.model).to(_device())
+        dataset = _load(args.dataset)
+        alis = _load_alis(args.alis)
+        feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
+        names, idx = speakers_of(kept, utt2spk)
+        use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        init = None
+        if args.init:
+            # the speakers of this run, in its order: those of the file keep their transform
+            old = beer.AffineTransforms.load(args.init)
+            init = beer.AffineTransforms(names, old.dim)
+            for n, at in enumerate(old.indices(names)):
+                if at >= 0:
+                    init.W[n] = old.W[at]
+        frames = np.zeros(len(names), dtype=np.int64)
+        for n, utt in zip(idx, feats):
+            frames[n] += len(utt)
+        if kept:
+            transforms, gains = beer.adapt(
+                model, feats, idx, names, iters=args.iters, transforms=init,
+                inference_graphs=use, scale=args.acoustic_scale, sweeps=args.sweeps,
+                min_count=args.min_count)
+            total = np.sum(gains, axis=0)
+        else:
+            transforms, total = beer.AffineTransforms(names, dataset.mean.shape[0]), np.zeros(0)
+        transforms.save(args.out)
+        for name, count, gain in zip(names, frames.tolist(), total.tolist()):
+            print(name, count, '%.6f' % gain)
+        logger.info(f'estimated the transforms of {len(names)} speakers from {len(kept)} '
+                    f'utterances ({int(frames.sum())} frames).')
+
+
 class posteriors:
     'state / phone posteriors of all the utterances of a dataset'
     EPS = 1e-5
@@ -916,4 +1006,4 @@ class posteriors:
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
             mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, lattice,
-            segments, boundaries]
+            segments, adapt, boundaries]

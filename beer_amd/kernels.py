@@ -4,9 +4,11 @@ Shapes and argument checks only: the arithmetic is in beer_amd/csrc.  All
 returned tensors live on the GPU.
 """
 
+import ctypes
 import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -16,7 +18,8 @@ __all__ = ['normal_llh', 'mixtureset_estep', 'normal_accumulate', 'weights_from_
            'tied_lognorm', 'tied_accumulate', 'predictive_llh', 'mixtureset_predictive',
            'is_dense', 'dense_llh', 'dense_softmax', 'dense_accumulate', 'rowdot',
            'attach_stats_grad', 'differentiable_stats', 'sample_stats', 'attach_frame_grad',
-           'frames_llh_backward', 'normal_llh_autograd']
+           'frames_llh_backward', 'normal_llh_autograd', 'cmllr_frame_params', 'cmllr_table',
+           'cmllr_accumulate', 'cmllr_apply', 'CmllrTable']
 
 LOG_2PI = 1.8378770664093453
 
@@ -577,6 +580,135 @@ def mixtureset_predictive(stats, table, log_mean_weights, S, G, cov_type):
 # ---- dense ("stats-in") statistics: the prior of a VAE ------------------------
 # beer/models/vae.py:63-89 hands the prior sample-averaged statistics [T, Q]
 # and differentiates its expected log-likelihood w.r.t. them.
+
+def cmllr_frame_params(comp_resps, state_resps, exp_stats, S, G, dim, cov_type, out=None):
+    '''out [T, P + D + 1] float64 += [omega | nu | c], the posterior-averaged parameters of
+    every frame (`beer_cmllr_frame_params`): r[t, k] = comp_resps[t, k] * state_resps[t, k // G]
+    as in `normal_accumulate`, `exp_stats` [S*G, Q] the Gaussians' `natural_form()`; P = D
+    for diagonal, 1 for isotropic covariances.'''
+    given = comp_resps if comp_resps is not None else state_resps
+    if given is None:
+        raise ValueError('cmllr_frame_params: component or state responsibilities')
+    dtype, T, D = given.dtype, given.shape[0], int(dim)
+    cr = None if comp_resps is None else _hip.on_device(comp_resps, dtype)
+    sr = None if state_resps is None else _hip.on_device(state_resps, dtype)
+    E = _hip.on_device(exp_stats, dtype)
+    cov = _hip.COV_CODE[cov_type]
+    P = D if cov == _hip.DIAG else 1
+    if E.shape[0] != S * G or (cr is not None and tuple(cr.shape) != (T, S * G)) or \
+            (sr is not None and tuple(sr.shape) != (T, S)):
+        raise ValueError(f'cmllr_frame_params: {E.shape[0]} Gaussians, responsibilities '
+                         f'{None if cr is None else tuple(cr.shape)} / '
+                         f'{None if sr is None else tuple(sr.shape)} for {S} x {G} components')
+    if out is None:
+        out = torch.zeros(T, P + D + 1, dtype=torch.float64, device=E.device)
+    _hip.call('beer_cmllr_frame_params', _hip.dtype_code(dtype), cov, T, D, S, G, _hip.ptr(cr),
+              _hip.ptr(sr), _hip.ptr(E), _hip.ptr(out))
+    return out
+
+
+class CmllrTable:
+    '''The host-built table of `beer_cmllr_accumulate` (`beer_cmllr_table`): `host` int32
+    numpy, `n_items` work items of at most `chunk_frames` frames (0: the library's default),
+    `device()` its copy on the GPU.'''
+
+    def __init__(self, host, nutt, n_speakers, chunk_frames):
+        self.host, self.nutt, self.n_speakers, self.chunk_frames = host, nutt, n_speakers, chunk_frames
+        self.n_items = int(host[0])
+        self._dev = None
+
+    def device(self):
+        if self._dev is None:
+            self._dev = _hip.to_device(torch.from_numpy(self.host))
+        return self._dev
+
+
+def cmllr_table(lengths, speakers, n_speakers, chunk_frames=0):
+    '''`CmllrTable` of a ragged batch: `speakers[u]` in -1 .. n_speakers - 1 (-1: the utterance
+    is left out).  Host only; a speaker out of range raises `HipInvalid`.'''
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    spk = np.ascontiguousarray(np.asarray(speakers, dtype=np.int64).reshape(-1))
+    if len(lens) != len(spk):
+        raise ValueError(f'cmllr_table: {len(spk)} speakers for {len(lens)} utterances')
+    if len(spk) and (spk.min() < -(1 << 31) or spk.max() >= 1 << 31):
+        raise _hip.HipInvalid('beer_cmllr_table failed: invalid argument')
+    spk = spk.astype(np.int32)
+    n = ctypes.c_size_t(0)
+    args = (len(lens), int(n_speakers), ctypes.c_void_p(lens.ctypes.data),
+            ctypes.c_void_p(spk.ctypes.data), int(chunk_frames))
+    _hip.call_host('beer_cmllr_table', *args, None, ctypes.byref(n))
+    host = np.zeros(n.value, dtype=np.int32)
+    _hip.call_host('beer_cmllr_table', *args, ctypes.c_void_p(host.ctypes.data), ctypes.byref(n))
+    return CmllrTable(host, len(lens), int(n_speakers), int(chunk_frames))
+
+
+def _frame_offsets(lengths, device):
+    off = torch.zeros(len(lengths) + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(torch.as_tensor(lengths, dtype=torch.int64), 0)
+    return _hip.to_device(off, device)
+
+
+def cmllr_accumulate(X, params, lengths, speakers, n_speakers, G=None, k=None, beta=None,
+                     chunk_frames=0, table=None, frame_off=None):
+    '''(G [n, P, E(E+1)/2], k [n, D, E], beta [n]) float64 += the CMLLR statistics of the
+    frames X [T, D] of a ragged batch (`beer_cmllr_accumulate`; E = D + 1, the lower triangle
+    of G_i packed row by row) with `params` [T, P + D + 1] of `cmllr_frame_params`.
+    `chunk_frames`: the frames of a work item (0: the library's default); `table`: the
+    `cmllr_table` of the same lengths, speakers and chunk, `frame_off`: the offsets on the
+    device, for callers that keep them.'''
+    X = _hip.on_device(X)
+    T, D = X.shape
+    prm = _hip.on_device(params, torch.float64)
+    P = prm.shape[1] - D - 1
+    if prm.shape[0] != T or sum(lengths) != T:
+        raise ValueError(f'cmllr_accumulate: {T} frames, parameters of {prm.shape[0]}, '
+                         f'utterances of {sum(lengths)}')
+    if table is None:
+        table = cmllr_table(lengths, speakers, n_speakers, chunk_frames)
+    n, E = int(n_speakers), D + 1
+    if P in (1, D):
+        shapes = ((n, P, E * (E + 1) // 2), (n, D, E), (n,))
+        G, k, beta = (torch.zeros(s, dtype=torch.float64, device=X.device) if t is None else t
+                      for s, t in zip(shapes, (G, k, beta)))
+        if any(tuple(t.shape) != s or t.dtype != torch.float64 or not t.is_contiguous()
+               for s, t in zip(shapes, (G, k, beta))):
+            raise ValueError(f'cmllr_accumulate: float64 statistics of shapes {shapes}')
+    ws, ws_bytes = _hip.scratch(('cmllr', D, P), _hip.lib().beer_cmllr_workspace_bytes(
+        D, P, table.n_items), X.device)
+    if frame_off is None:
+        frame_off = _frame_offsets(lengths, X.device)
+    _hip.call('beer_cmllr_accumulate', _hip.dtype_code(X.dtype), T, D, P, table.nutt, n,
+              _hip.ptr(X), _hip.ptr(prm), _hip.ptr(frame_off),
+              ctypes.c_void_p(table.host.ctypes.data), _hip.ptr(table.device()), len(table.host),
+              table.chunk_frames, _hip.ptr(G), _hip.ptr(k), _hip.ptr(beta), _hip.ptr(ws), ws_bytes)
+    return G, k, beta
+
+
+def cmllr_apply(X, W, lengths, speakers):
+    '''Y[t] = A_s x_t + b_s over a ragged batch (`beer_cmllr_apply`): W [n, D, D + 1] float64,
+    `speakers[u]` the transform of utterance u, -1 to copy its frames.  Computed in float64,
+    returned in the frames' dtype.'''
+    X = _hip.on_device(X)
+    T, D = X.shape
+    W = _hip.on_device(W, torch.float64)
+    if W.dim() != 3 or tuple(W.shape[1:]) != (D, D + 1):
+        raise ValueError(f'cmllr_apply: transforms {tuple(W.shape)} for frames of dimension {D}')
+    spk = np.ascontiguousarray(np.asarray(speakers, dtype=np.int64).reshape(-1))
+    if len(spk) != len(lengths) or sum(lengths) != T:
+        raise ValueError(f'cmllr_apply: {len(spk)} speakers, {len(lengths)} utterances of '
+                         f'{sum(lengths)} frames for {T} frames')
+    if len(spk) and (spk.min() < -1 or spk.max() >= W.shape[0]):
+        raise _hip.HipInvalid('beer_cmllr_apply failed: invalid argument')
+    spk = spk.astype(np.int32)
+    off = torch.zeros(len(lengths) + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(torch.as_tensor(lengths, dtype=torch.int64), 0)
+    up = _hip.upload({'off': off, 'spk': torch.from_numpy(spk)}, X.device)
+    Y = torch.empty_like(X)
+    _hip.call('beer_cmllr_apply', _hip.dtype_code(X.dtype), T, D, len(lengths), W.shape[0],
+              _hip.ptr(X), _hip.ptr(W), _hip.ptr(up['off']), _hip.ptr(up['spk']),
+              ctypes.c_void_p(spk.ctypes.data), _hip.ptr(Y))
+    return Y
+
 
 def _dense(stats, dtype=None):
     return _hip.on_device(stats.detach(), dtype)

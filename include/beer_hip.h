@@ -607,6 +607,77 @@ int beer_mixtureset_predictive(int dtype, int cov, int64_t T, int D, int S, int 
                                const void* log_mean_weights, void* log_norm, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Speaker-adaptive affine feature transforms (CMLLR / fMLLR), cmllr.hip
+ * ---------------------------------------------------------------------- */
+/* y = A_s x + b_s per speaker, W_s = [A_s | b_s] [D, D+1], estimated by maximum likelihood
+ * under a model of diagonal or isotropic Gaussians.  With r_tk the
+ * component responsibilities of frame t, xi_t = [x_t; 1] and E = D + 1:
+ *   omega_ti = sum_k r_tk E[lambda]_ki       [T, P]   P = D diagonal, 1 isotropic
+ *   nu_ti    = sum_k r_tk E[lambda mu]_ki    [T, D]
+ *   c_t      = sum_k r_tk
+ *   G_{s,i}  = sum_t omega_ti xi_t xi_t^T    symmetric E x E, i < P (packed lower triangle,
+ *                                            entry (a, b), b <= a, at a (a + 1) / 2 + b)
+ *   k_{s,i}  = sum_t nu_ti xi_t              E entries, i < D
+ *   beta_s   = sum_t c_t
+ * the sums over the frames of speaker s.  D <= BEER_CMLLR_MAX_DIM everywhere below. */
+#define BEER_CMLLR_MAX_DIM 63
+
+/* out[t, :] += [omega_t | nu_t | c_t], float64 [T, P + D + 1], with
+ * r_tk = comp_resps[t, k] * state_resps[t, k / G] -- the contract of beer_normal_accumulate,
+ * transposed: `comp_resps` [T, S G] nullable when G == 1 (= 1), `state_resps` [T, S] nullable
+ * (= 1), both in `dtype` like E [S G, Q], the natural_form() of the Gaussians (BEER_DIAG:
+ * Q = 2 D + 2, BEER_ISO: Q = D + 3; its first D columns are E[lambda mu], the next P
+ * E[lambda]).  Products and sums in float64 on the matrix cores; it ADDS, so that the groups
+ * of a joint emission set accumulate into one buffer.  BEER_EINVAL for BEER_FULL. */
+int beer_cmllr_frame_params(int dtype, int cov, int64_t T, int D, int S, int G,
+                            const void* comp_resps, const void* state_resps, const void* E,
+                            double* out, void* stream);
+
+/* HOST: the table beer_cmllr_accumulate walks, from the utterances' lengths and speakers
+ * (host arrays; speaker -1: the utterance is left out).  The frames of a speaker, in
+ * utterance order, are cut into items of `chunk_frames` frames (0: the default, 1024); an
+ * item lists its runs of frames inside utterances.  With `table` NULL *n_ints receives the
+ * number of int32 the table takes; else *n_ints is the room in `table` on entry and what
+ * was written on return:
+ *   [n_items, n_segs, n_spk, nutt | spk_ptr [n_spk + 1] | item_spk [n_items] |
+ *    item_ptr [n_items + 1] | seg [n_segs][3] = (utterance, first frame in it, frames)]
+ * BEER_EINVAL for a speaker outside -1 .. n_spk - 1 or an utterance of 2^31 frames. */
+int beer_cmllr_table(int32_t nutt, int32_t n_spk, const int64_t* lengths,
+                     const int32_t* utt_spk, int32_t chunk_frames, int32_t* table,
+                     size_t* n_ints);
+
+/* Bytes of workspace beer_cmllr_accumulate needs for a table of n_items items (a slab of
+ * P E (E + 1) / 2 + D E + 1 doubles each); 0 for a shape it refuses. */
+size_t beer_cmllr_workspace_bytes(int D, int P, int64_t n_items);
+
+/* G [n_spk, P, E (E + 1) / 2], k [n_spk, D, E], beta [n_spk] (float64) += the statistics
+ * above of the frames X [T, D] (`dtype`) with params [T, P + D + 1] = [omega | nu | c] of
+ * beer_cmllr_frame_params, over the ragged batch `frame_off` [nutt + 1] (device).  `table`:
+ * the device copy of `table_host` (beer_cmllr_table with the same chunk_frames), whose
+ * structure is checked on the host before anything is launched.  Every item is summed on
+ * the matrix cores by one workgroup per eight dimensions i into a slab of the workspace,
+ * four frames per step in frame order; a second kernel adds a speaker's slabs in chunk
+ * order.  No atomics: the result depends on the inputs and chunk_frames only, bit for bit.
+ * BEER_EINVAL: D > BEER_CMLLR_MAX_DIM, P neither 1 nor D, a table that does not fit
+ * (n_spk, nutt, chunk_frames) or names a speaker or utterance out of range, a workspace
+ * smaller than beer_cmllr_workspace_bytes. */
+int beer_cmllr_accumulate(int dtype, int64_t T, int D, int P, int32_t nutt, int32_t n_spk,
+                          const void* X, const double* params, const int64_t* frame_off,
+                          const int32_t* table_host, const int32_t* table, size_t table_ints,
+                          int32_t chunk_frames, double* G, double* k, double* beta,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Y[t] = A_s x_t + b_s, s = utt_spk[utterance of t], W [n_spk, D, D + 1] float64: the sum
+ * in float64 (a fused multiply-add chain over the dimensions, then + b), rounded once to
+ * `dtype`.  A speaker of -1 (and a frame outside every utterance) copies the frame.
+ * `utt_spk` [nutt] on the device; `utt_spk_host` (nullable): its host copy, checked before
+ * the launch -- BEER_EINVAL for an entry outside -1 .. n_spk - 1 (an entry the kernel meets
+ * out of range copies the frame).  Y must not be X. */
+int beer_cmllr_apply(int dtype, int64_t T, int D, int32_t nutt, int32_t n_spk, const void* X,
+                     const double* W, const int64_t* frame_off, const int32_t* utt_spk,
+                     const int32_t* utt_spk_host, void* Y, void* stream);
+
+/* ------------------------------------------------------------------------
  * HMM inference over a ragged batch of utterances
  * ---------------------------------------------------------------------- */
 
