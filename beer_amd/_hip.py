@@ -193,6 +193,16 @@ def evidence_spl(route):
     return route & 0xF
 
 
+# BEER_HSMM_* of include/beer_hip.h: the limits and what `beer_hsmm_route` returns
+HSMM_MAX_DUR, HSMM_MAX_STATES = 128, 2048
+HSMM_BLOCK, HSMM_RING_LDS, HSMM_LOWDEG = 0x1000, 0x100, 0x200
+
+
+def hsmm_team(route):
+    'BEER_HSMM_TEAM: the lanes that share one state\'s ring slots.'
+    return 1 << (route & 0xF)
+
+
 # BEER_NBEST_* of include/beer_hip.h: the largest k and what `beer_hmm_nbest_route` returns
 NBEST_MAX, NBEST_ARCS_LDS = 16, 0x100
 
@@ -445,6 +455,10 @@ SIGNATURES = {
     'beer_hmm_sample_route': [c_i, c_p, ctypes.c_int32],           # (host only: no stream)
     'beer_hmm_log_evidence': [c_i, c_p, c_p, c_p, c_p, c_p],
     'beer_hmm_evidence_route': [c_i, c_p],                         # (host only: no stream)
+    'beer_hsmm_forward_backward': [c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p,
+                                   c_p, c_p],
+    'beer_hsmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p],
+    'beer_hsmm_route': [c_i, c_p, c_i],                            # (host only: no stream)
     'beer_hmm_arc_posteriors': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
     'beer_hmm_arcs_route': [c_i, c_p, c_i, c_i],                   # (host only: no stream)
     'beer_hmm_max_marginals': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
@@ -510,6 +524,7 @@ SIZE_QUERIES = {
     'beer_hmm_arcs_scratch_doubles': [c_i, c_p],
     'beer_hmm_maxmarg_scratch_doubles': [c_i, c_p],
     'beer_hmm_segments_scratch_doubles': [c_i, c_p],
+    'beer_hsmm_scratch_doubles': [c_i, c_p, c_i],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
     'beer_cmllr_workspace_bytes': [c_i, c_i, c_l],
 }

@@ -252,6 +252,8 @@ def cmllr_statistics_batch(model, utterances, speakers, n_speakers, transforms=N
     or a JointModelSet of them).  Per sub-batch of at most `max_frames` frames: transform,
     E-step with dense responsibilities, forward-backward, `cmllr_frame_params` per emission
     group, `cmllr_accumulate` (work items of `chunk_frames` frames; 0: the library's default).'''
+    if getattr(model, 'durations', None) is not None:
+        model._refuse_durations('speaker adaptation (adapt, cmllr_statistics_batch)')
     groups, is_mixture, cov = _emission_groups(model)
     X, lengths = pack_utterances(utterances)
     D, n_speakers = X.shape[1], int(n_speakers)
@@ -345,6 +347,8 @@ def adapt(model, utterances, speakers, names, iters=3, transforms=None, **kw):
     them.  `speakers[u]`: a name of `names` or its index; `transforms`: where to start
     (default: the identity).  `sweeps`, `min_gain`, `min_count` go to `estimate`, every other
     keyword to `cmllr_statistics_batch`.'''
+    if getattr(model, 'durations', None) is not None:
+        model._refuse_durations('speaker adaptation (adapt, cmllr_statistics_batch)')
     names = [str(n) for n in names]
     est = {k: kw.pop(k) for k in _ESTIMATE_ARGS if k in kw}
     X, lengths = pack_utterances(utterances)

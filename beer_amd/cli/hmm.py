@@ -159,13 +159,19 @@ BIGRAM_PRIORS = ('dirichlet2', 'hierarchical_dirichlet_process')
 
 
 def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirichlet_process',
-               concentration=None, train_transitions=False, transitions_prior_strength=1.):
+               concentration=None, train_transitions=False, transitions_prior_strength=1.,
+               max_duration=0, durations_prior_strength=1.):
     '''`beer hmm mkphoneloop` (mkphoneloop.py:30-80): a `BigramPhoneLoop` for the
     bigram priors (`dirichlet2`, `hierarchical_dirichlet_process`), else a `PhoneLoop`.
     `train_transitions` (not in the reference): the units' transition probabilities are
-    learned too (PhoneLoop only).'''
+    learned too (PhoneLoop only).  `max_duration` D > 0 (not in the reference): every state
+    stays 1 .. D frames under a learned duration law (PhoneLoop only).'''
     size = len(start_pdf)
     conc = concentration if concentration else size / 2
+    if max_duration and weights_prior in BIGRAM_PRIORS:
+        raise NotImplementedError('explicit durations (--max-duration) with a BigramPhoneLoop '
+                                  f'(--weights-prior {weights_prior}) are not supported: its '
+                                  'fused kernel has no duration laws')
     if train_transitions and weights_prior in BIGRAM_PRIORS:
         raise ValueError('learned transitions (--train-transitions) are not supported on a '
                          f'bigram phone loop (--weights-prior {weights_prior})')
@@ -187,7 +193,9 @@ def phone_loop(graph, start_pdf, end_pdf, emissions, weights_prior='gamma_dirich
         raise ValueError(f'unknown prior over the weights: {weights_prior!r}')
     return beer.PhoneLoop.create(graph.compile(), start_pdf, end_pdf, emissions, cat,
                                  train_transitions=train_transitions,
-                                 transitions_prior_strength=transitions_prior_strength)
+                                 transitions_prior_strength=transitions_prior_strength,
+                                 max_duration=max_duration,
+                                 durations_prior_strength=durations_prior_strength)
 
 
 def bigram_loop(ploop, weights_prior):
@@ -199,6 +207,10 @@ def bigram_loop(ploop, weights_prior):
     if getattr(ploop, 'transitions', None) is not None:
         raise ValueError('learned transitions are not supported on a bigram phone loop: make '
                          'the bigram loop from a unigram loop without --train-transitions')
+    if getattr(ploop, 'durations', None) is not None:
+        raise NotImplementedError('explicit durations (--max-duration) with a BigramPhoneLoop are '
+                                  'not supported: make the bigram loop from a unigram loop '
+                                  'without --max-duration')
     if weights_prior == 'dirichlet2':
         cset = beer.CategoricalSet.create(torch.ones(size, size) / size, prior_strength=1)
     elif weights_prior == 'hierarchical_dirichlet_process':
@@ -316,6 +328,12 @@ class mkphoneloop:
                                  '(Dirichlet priors; not in the reference)')
         parser.add_argument('--transitions-prior-strength', type=float, default=1.,
                             help='prior strength of the learned transition probabilities')
+        parser.add_argument('--max-duration', type=int, default=0,
+                            help='explicit state durations: every state stays 1 .. D frames '
+                                 'under a learned law (0: the geometric stay of the self-loops; '
+                                 'not in the reference)')
+        parser.add_argument('--durations-prior-strength', type=float, default=1.,
+                            help='prior strength of the duration laws')
         parser.add_argument('decode_graph', help='decoding graph')
         parser.add_argument('hmms', help="phones' hmm")
         parser.add_argument('out', help='phone loop model')
@@ -327,7 +345,8 @@ class mkphoneloop:
         size = len(start_pdf)
         ploop = phone_loop(graph, start_pdf, end_pdf, emissions, args.weights_prior,
                            args.concentration, args.train_transitions,
-                           args.transitions_prior_strength)
+                           args.transitions_prior_strength, args.max_duration,
+                           args.durations_prior_strength)
         _dump(ploop, args.out)
         logger.info(f'successfully created a phone-loop model with {size} phones')
 
@@ -1004,6 +1023,36 @@ class posteriors:
         logger.info(f'successfully computed the posteriors for {count} utterances.')
 
 
+def duration_lines(model):
+    '''The lines of `beer hmm durations`: "<unit> <state> <mean frames> <mode> <p(1)> .. <p(D)>"
+    per state of every unit (the states of a unit counted from 0), from the posterior means of
+    the duration laws.'''
+    if getattr(model, 'durations', None) is None:
+        raise SystemExit('the model has no explicit durations (mkphoneloop --max-duration)')
+    probs, means = model.durations.expected_durations()
+    lines = []
+    for unit in model.start_pdf:
+        for k, pdf in enumerate(range(int(model.start_pdf[unit]), int(model.end_pdf[unit]) + 1)):
+            row = probs[pdf]
+            lines.append(' '.join([str(unit), str(k), '%.4f' % float(means[pdf]),
+                                   str(int(row.argmax()) + 1)] + ['%.6f' % float(p) for p in row]))
+    return lines
+
+
+class durations:
+    '''print the learned duration laws of a model made with --max-duration:
+    "<unit> <state> <mean frames> <mode> <p(1)> .. <p(D)>" per unit state'''
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('model', help='phone-loop model with explicit durations')
+
+    @staticmethod
+    def main(args, logger):
+        for line in duration_lines(_load(args.model)):
+            print(line)
+
+
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
             mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, lattice,
-            segments, adapt, boundaries]
+            segments, adapt, durations, boundaries]

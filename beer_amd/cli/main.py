@@ -70,7 +70,12 @@ def main(argv=None):
         random.seed(args.seed)
     if args.debug:
         logger.setLevel(logging.DEBUG)
-    args.func(args, logger)
+    try:
+        args.func(args, logger)
+    except NotImplementedError as err:
+        # (a combination a model refuses, e.g. explicit durations with an n-best search: its
+        #  message, not a traceback)
+        raise SystemExit(f'beer: {err}')
 
 
 if __name__ == '__main__':

@@ -1,0 +1,626 @@
+// Explicit state durations (hidden semi-Markov model): forward-backward and Viterbi over
+// (state, duration) for every utterance of a ragged batch (include/beer_hip.h:
+// beer_hsmm_forward_backward, beer_hsmm_viterbi -- the definitions are there).
+//
+// One workgroup of 256 threads per utterance, at most 512 workgroups striding over the batch.
+// fp64 log space throughout.  The running scores of the segments in progress sit in a ring
+// [S][D] indexed by the segment's start (backward pass: its end) mod D.  A frame has three
+// phases between barriers:
+//   A  a thread per state: the arcs (beg_t from end_{t-1}; backward bend_t from bbeg_{t+1}),
+//      after one wave per hub has reduced the hub's value;
+//   B  a TEAM of 1 .. 64 lanes per state: every live slot += l_t(j) - c_t - n, the new slot is
+//      written, and one log-sum-exp (Viterbi: max) over the slots with the rotated duration law
+//      gives end_t(j) (backward: bbeg_t(j), and with the same exponentials the duration counts);
+//   R  a block reduction: the next frame's offsets c_{t+1} and n_t.
+// Offsets.  Stored values are true values minus a running offset that is the same for every
+// state: forward O_t = sum_{tau<=t} c_tau + sum_{tau<t} n_tau, backward Q_t = sum_{tau>=t} c_tau +
+// sum_{tau>t} n'_tau.  c_t = rint(max_j l_t(j)) and n = the frame's largest end (begin) value
+// rounded to a multiple of 1/256: their running sums are exact, so a posterior's exponent
+// N_t + N'_t' - Z is formed without cancellation error and a per-frame shift of the inputs moves
+// nothing but the evidence.
+// The posteriors come out of the backward pass: with B_t(j), E_t(j) the posteriors that a segment
+// of j begins / ends at t, gamma_t = gamma_{t+1} - B_{t+1} + E_t from gamma_{T-1} = E_{T-1}.
+
+#include "common.h"
+
+using namespace beer;
+
+namespace {
+
+constexpr int kHsThreads = 256;
+constexpr int kHsMaxGrid = 512;          // workgroups of a launch (each with a ring in `ws`)
+constexpr int kHsRows = 8;               // per-state rows of doubles in LDS
+constexpr int kHsMisc = 32;              // doubles: reduction scratch [16], hub values [4], spare
+constexpr int kHsMaxHubs = 4;            // (kMaxHubs of hmm.hip)
+constexpr double kHsQuant = 256.0;       // n is a multiple of 1 / kHsQuant
+
+struct HsArgs {
+    const double* log_dur;
+    const double* leave_w;
+    int D, S_total;
+    double* ws;
+    size_t ring_total;                   // doubles of `ws` taken by the rings (0: rings in LDS)
+    int ring_lds, lowdeg, team_log2;
+    // forward-backward
+    void* gamma;
+    double* utt_evidence;
+    double* dur_counts;
+    double* entry_sum;
+    double* gamma0_sum;
+    // Viterbi
+    int64_t* path;
+    double* score;
+    int map_pdf;
+};
+
+__device__ __forceinline__ double hmax(double a, double b) { return b > a ? b : a; }
+
+// log-sum-exp as the pair (m, s): sum = s exp(m)
+__device__ __forceinline__ void hs_add(double& m, double& s, double v) {
+    if (v > m) {
+        s = s * exp(m - v) + 1.0;                       // (m = -inf: s = 0 stays 0)
+        m = v;
+    } else if (v > neg_inf()) {
+        s += exp(v - m);
+    }
+}
+__device__ __forceinline__ double hs_value(double m, double s) {
+    return s > 0.0 ? m + log(s) : neg_inf();
+}
+// Viterbi: the larger value, the smaller index among equals
+__device__ __forceinline__ void hs_best(double& m, int& arg, double v, int i) {
+    if (v > m || (v == m && v > neg_inf() && i < arg)) { m = v; arg = i; }
+}
+
+// the maxima of two values over the workgroup, in every thread; a barrier separates two calls
+__device__ __forceinline__ void hs_block_max2(double& a, double& b, double* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    a = wave_max(a);
+    b = wave_max(b);
+    if (lane == 0) { red[w] = a; red[8 + w] = b; }
+    __syncthreads();
+    a = red[0]; b = red[8];
+    for (int i = 1; i < kHsThreads / 64; ++i) { a = hmax(a, red[i]); b = hmax(b, red[8 + i]); }
+}
+__device__ __forceinline__ double hs_block_sum(double a, double* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    a = wave_sum(a);
+    if (lane == 0) red[w] = a;
+    __syncthreads();
+    double r = 0.0;
+    for (int i = 0; i < kHsThreads / 64; ++i) r += red[i];
+    return r;
+}
+__device__ __forceinline__ double hs_quant(double v) {
+    return v > neg_inf() ? __builtin_rint(v * kHsQuant) / kHsQuant : 0.0;
+}
+
+template <typename T, bool VIT>
+__global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
+                                                          const T* __restrict__ pc_llhs,
+                                                          HsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int SM = b.max_states, D = a.D;
+    double* rows = reinterpret_cast<double*>(smem);
+    double* r0 = rows;                    // forward: end_{t-1}        backward: bbeg_{t+1}
+    double* r1 = rows + SM;               // forward: end_{t-1} + leave  backward: bend_t
+    double* r2 = rows + 2 * SM;           // forward: beg_t
+    double* lv = rows + 3 * SM;           // leave_w[id(j)]
+    double* g_row = rows + 4 * SM;        // gamma_{t+1}
+    double* bprev = rows + 5 * SM;        // B_{t+1}
+    double* ent = rows + 6 * SM;          // sum_{t>=1} B_t
+    int* sid = reinterpret_cast<int*>(rows + 7 * SM);      // id(j), -1: outside the table
+    double* red = rows + (size_t)kHsRows * SM;
+    double* hubv = red + 16;
+    double* ring = a.ring_lds ? red + kHsMisc
+                              : a.ws + (size_t)blockIdx.x * 2 * (size_t)SM * (size_t)D;
+    double* acc = ring + (size_t)SM * D;
+    const int team = 1 << a.team_log2, nteams = kHsThreads / team;
+    const int tj = tid >> a.team_log2, tl = tid & (team - 1);
+
+    for (int slot = blockIdx.x; slot < b.nutt; slot += gridDim.x) {
+        __syncthreads();                                     // the rows of the last utterance
+        const int u = b.order ? b.order[slot] : slot;
+        const int gi = b.graph_id[u];
+        const beer_graph g = b.graphs[gi];
+        const int S = g.n_states;
+        const int64_t f0 = b.frame_off[u];
+        const int64_t T_ = b.frame_off[u + 1] - f0;
+        if (T_ <= 0) {
+            if (tid == 0) {
+                if (VIT) a.score[u] = 0.0;
+                else if (a.utt_evidence) a.utt_evidence[u] = 0.0;
+            }
+            continue;
+        }
+        const int64_t e0 = b.llh_off[u];
+        const T* llh = pc_llhs + e0;
+        const int32_t* ids = b.pdf_ids + b.pdf_off[gi];
+        const T* init = (const T*)g.init;
+        const T* fin = (const T*)g.final;
+        double* region = a.ws + a.ring_total + 2 * (size_t)e0 + 2 * (size_t)f0;
+        double* begT = region;                               // [T, S] beg_t(j) - O_{t-1}
+        double* endT = region + (size_t)T_ * S;              // [T, S] end_t(j) - O_t
+        double* ncum = endT + (size_t)T_ * S;                // [T] N_t = sum_{tau<=t} n_tau
+        double* cfr = ncum + T_;                             // [T] c_t
+        int32_t* bp = reinterpret_cast<int32_t*>(region);    // Viterbi: (source, duration)
+
+        // arcs: the low-degree image and its hubs, or the full CSR
+        const bool ld = !VIT && a.lowdeg && g.lowdeg != nullptr;
+        beer_graph_lowdeg L = {};
+        if (ld) L = *g.lowdeg;
+        const int n_hubs = ld ? (L.n_hubs < kHsMaxHubs ? L.n_hubs : kHsMaxHubs) : 0;
+        const int32_t* in_ptr = ld ? L.in_ptr : g.in_ptr;
+        const int32_t* in_src = ld ? L.in_src : g.in_src;
+        const T* in_w = (const T*)(ld ? L.in_w : g.in_w);
+        const int32_t* out_ptr = ld ? L.out_ptr : g.out_ptr;
+        const int32_t* out_dst = ld ? L.out_dst : g.out_dst;
+        const T* out_w = (const T*)(ld ? L.out_w : g.out_w);
+        const T* hsw = (const T*)L.hub_src_w;
+        const T* hdw = (const T*)L.hub_dst_w;
+
+        for (int j = tid; j < S; j += kHsThreads) {
+            const int id = ids[j];
+            const bool ok = id >= 0 && id < a.S_total;
+            sid[j] = ok ? id : -1;
+            lv[j] = (ok && a.leave_w) ? a.leave_w[id] : 0.0;
+            ent[j] = 0.0;
+        }
+        for (int i = tid; i < S * D; i += kHsThreads) ring[i] = neg_inf();
+        double cN, dummy = neg_inf();
+        {
+            double m = neg_inf();
+            for (int j = tid; j < S; j += kHsThreads) m = hmax(m, (double)llh[j]);
+            hs_block_max2(m, dummy, red);
+            cN = m > neg_inf() ? __builtin_rint(m) : 0.0;
+        }
+        __syncthreads();
+
+        // ------------------------------ forward ------------------------------
+        double nprev = 0.0, Nprev = 0.0, Ctot = 0.0;         // n_{t-1}, N_{t-1}, C_{t-1}
+        for (int64_t t = 0; t < T_; ++t) {
+            if (t > 0 && n_hubs > 0) {
+                for (int h = wave; h < n_hubs; h += kHsThreads / 64) {
+                    const int p0 = L.src_ptr[h], p1 = L.src_ptr[h + 1];
+                    double m = neg_inf();
+                    for (int p = p0 + lane; p < p1; p += 64) {
+                        const int i = L.src_list[p];
+                        m = hmax(m, r1[i] + (double)hsw[i]);
+                    }
+                    m = wave_max(m);
+                    const double base = m > neg_inf() ? m : 0.0;
+                    double s = 0.0;
+                    for (int p = p0 + lane; p < p1; p += 64) {
+                        const int i = L.src_list[p];
+                        s += exp(r1[i] + (double)hsw[i] - base);
+                    }
+                    s = wave_sum(s);
+                    if (lane == 0) hubv[h] = s > 0.0 ? base + log(s) : neg_inf();
+                }
+                __syncthreads();
+            }
+            // A: beg_t
+            for (int j = tid; j < S; j += kHsThreads) {
+                double bg;
+                int src = -1;
+                if (t == 0) {
+                    bg = (double)init[j];
+                } else if (VIT) {
+                    bg = neg_inf();
+                    for (int e = in_ptr[j]; e < in_ptr[j + 1]; ++e) {
+                        const int i = in_src[e];
+                        if (i != j) hs_best(bg, src, r1[i] + (double)in_w[e], i);
+                    }
+                } else {
+                    double m = neg_inf(), s = 0.0;
+                    for (int e = in_ptr[j]; e < in_ptr[j + 1]; ++e) {
+                        const int i = in_src[e];
+                        if (i != j) hs_add(m, s, r1[i] + (double)in_w[e]);
+                    }
+                    const int hd = n_hubs > 0 ? L.hub_dst_id[j] : -1;
+                    if (hd >= 0 && hd < n_hubs) {
+                        if (L.hub_src_id[j] == hd) {
+                            // j feeds the hub that feeds it: the hub's value without j's own term
+                            for (int p = L.src_ptr[hd]; p < L.src_ptr[hd + 1]; ++p) {
+                                const int i = L.src_list[p];
+                                if (i != j) hs_add(m, s, r1[i] + (double)hsw[i] + (double)hdw[j]);
+                            }
+                        } else {
+                            hs_add(m, s, hubv[hd] + (double)hdw[j]);
+                        }
+                    }
+                    bg = hs_value(m, s);
+                }
+                r2[j] = bg;
+                if (VIT) bp[2 * (t * S + j)] = src;
+                else begT[t * S + j] = bg;
+            }
+            __syncthreads();
+            // B: the ring and end_t
+            const int kn = (int)(t % D);
+            for (int jb = 0; jb < S; jb += nteams) {
+                const int j = jb + tj;
+                const bool valid = j < S;
+                const int id = valid ? sid[j] : -1;
+                const double aj = valid ? ((double)llh[t * S + j] - cN) - nprev : neg_inf();
+                const double bgv = valid ? r2[j] : neg_inf();
+                const double* lam = a.log_dur + (size_t)(id < 0 ? 0 : id) * D;
+                double* R = ring + (size_t)(valid ? j : 0) * D;
+                double m = neg_inf();
+                int darg = D + 1;
+                if (valid) {
+                    for (int k = tl; k < D; k += team) {
+                        const double r = (k == kn ? bgv : R[k]) + aj;
+                        R[k] = r;
+                        int dd = kn - k;
+                        if (dd < 0) dd += D;
+                        const double v = id < 0 ? neg_inf() : r + lam[dd];
+                        if (VIT) hs_best(m, darg, v, dd + 1);
+                        else m = hmax(m, v);
+                    }
+                }
+                for (int o = team >> 1; o > 0; o >>= 1) {
+                    const double om = __shfl_xor(m, o);
+                    if (VIT) {
+                        const int od = __shfl_xor(darg, o);
+                        hs_best(m, darg, om, od);
+                    } else {
+                        m = hmax(m, om);
+                    }
+                }
+                double endv = m;
+                if (!VIT) {
+                    const double base = m > neg_inf() ? m : 0.0;
+                    double s = 0.0;
+                    if (valid && id >= 0 && m > neg_inf()) {
+                        for (int k = tl; k < D; k += team) {
+                            int dd = kn - k;
+                            if (dd < 0) dd += D;
+                            s += exp(R[k] + lam[dd] - base);
+                        }
+                    }
+                    for (int o = team >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                    endv = s > 0.0 ? base + log(s) : neg_inf();
+                }
+                if (valid && tl == 0) {
+                    r0[j] = endv;
+                    r1[j] = endv + lv[j];
+                    if (VIT) bp[2 * (t * S + j) + 1] = darg;
+                    else endT[t * S + j] = endv;
+                }
+            }
+            __syncthreads();
+            // R: n_t and c_{t+1}
+            double nm = neg_inf(), cm = neg_inf();
+            for (int j = tid; j < S; j += kHsThreads) {
+                nm = hmax(nm, r0[j]);
+                if (t + 1 < T_) cm = hmax(cm, (double)llh[(t + 1) * S + j]);
+            }
+            hs_block_max2(nm, cm, red);
+            const double nt = hs_quant(nm);
+            if (!VIT && tid == 0) { ncum[t] = Nprev + nt; cfr[t] = cN; }
+            Ctot += cN;
+            if (t + 1 < T_) {
+                Nprev += nt;
+                nprev = nt;
+                cN = cm > neg_inf() ? __builtin_rint(cm) : 0.0;
+            }
+        }
+        // (here Nprev = N_{T-2}: the offset of end_{T-1} is C_{T-1} + N_{T-2})
+        __syncthreads();
+
+        if (VIT) {
+            double m = neg_inf();
+            int arg = S;
+            for (int j = tid; j < S; j += kHsThreads) hs_best(m, arg, r0[j] + (double)fin[j], j);
+            // the workgroup's best: through LDS, the smaller state among equals
+            double* bm = red;
+            int* ba = reinterpret_cast<int*>(hubv);
+            for (int o = 32; o > 0; o >>= 1) {
+                const double om = __shfl_xor(m, o);
+                const int oa = __shfl_xor(arg, o);
+                hs_best(m, arg, om, oa);
+            }
+            if (lane == 0) { bm[wave] = m; ba[wave] = arg; }
+            __syncthreads();
+            m = bm[0]; arg = ba[0];
+            for (int i = 1; i < kHsThreads / 64; ++i) hs_best(m, arg, bm[i], ba[i]);
+            if (!(m > neg_inf())) {
+                for (int64_t t = tid; t < T_; t += kHsThreads) a.path[f0 + t] = -1;
+                if (tid == 0) a.score[u] = neg_inf();
+                continue;
+            }
+            if (tid == 0) {
+                a.score[u] = (m + Nprev) + Ctot;
+                int j = arg;
+                int64_t t = T_ - 1;
+                while (t >= 0) {
+                    int d = bp[2 * (t * S + j) + 1];
+                    if (d < 1 || d > t + 1) d = (int)(t + 1);          // (never on a finite path)
+                    const int64_t s = t - d + 1;
+                    const int64_t lab = a.map_pdf ? (int64_t)ids[j] : (int64_t)j;
+                    for (int64_t tau = s; tau <= t; ++tau) a.path[f0 + tau] = lab;
+                    if (s == 0) break;
+                    const int i = bp[2 * (s * S + j)];
+                    if (i < 0 || i >= S) break;                        // (never on a finite path)
+                    j = i;
+                    t = s - 1;
+                }
+            }
+            continue;
+        }
+
+        // ------------------------------ evidence ------------------------------
+        T* gamma = (T*)a.gamma + e0;
+        double zs;
+        {
+            double m = neg_inf(), dm = neg_inf();
+            for (int j = tid; j < S; j += kHsThreads) m = hmax(m, r0[j] + (double)fin[j]);
+            hs_block_max2(m, dm, red);
+            __syncthreads();
+            const double base = m > neg_inf() ? m : 0.0;
+            double s = 0.0;
+            for (int j = tid; j < S; j += kHsThreads) s += exp(r0[j] + (double)fin[j] - base);
+            s = hs_block_sum(s, red);
+            zs = s > 0.0 ? base + log(s) : neg_inf();
+        }
+        if (!(zs > neg_inf())) {
+            for (int64_t i = tid; i < T_ * S; i += kHsThreads) gamma[i] = (T)0;
+            if (tid == 0 && a.utt_evidence) a.utt_evidence[u] = neg_inf();
+            continue;
+        }
+        const double Zs = zs + Nprev;
+        if (tid == 0 && a.utt_evidence) a.utt_evidence[u] = Zs + Ctot;
+        const bool counts = a.dur_counts != nullptr;
+        for (int i = tid; i < S * D; i += kHsThreads) {
+            ring[i] = neg_inf();
+            if (counts) acc[i] = 0.0;
+        }
+        __syncthreads();
+
+        // ------------------------------ backward ------------------------------
+        double npn = 0.0, Np1 = 0.0, Np2 = 0.0;              // n'_{t+1}, N'_{t+1}, N'_{t+2}
+        for (int64_t t = T_ - 1; t >= 0; --t) {
+            const double ct = cfr[t];
+            const double Nt1 = t >= 1 ? ncum[t - 1] : 0.0, Nt2 = t >= 2 ? ncum[t - 2] : 0.0;
+            const double kapE = (Nt1 + Np2) - Zs, kapB = (Nt2 + Np1) - Zs;
+            if (t < T_ - 1 && n_hubs > 0) {
+                for (int h = wave; h < n_hubs; h += kHsThreads / 64) {
+                    const int p0 = L.dst_ptr[h], p1 = L.dst_ptr[h + 1];
+                    double m = neg_inf();
+                    for (int p = p0 + lane; p < p1; p += 64) {
+                        const int k = L.dst_list[p];
+                        m = hmax(m, r0[k] + (double)hdw[k]);
+                    }
+                    m = wave_max(m);
+                    const double base = m > neg_inf() ? m : 0.0;
+                    double s = 0.0;
+                    for (int p = p0 + lane; p < p1; p += 64) {
+                        const int k = L.dst_list[p];
+                        s += exp(r0[k] + (double)hdw[k] - base);
+                    }
+                    s = wave_sum(s);
+                    if (lane == 0) hubv[h] = s > 0.0 ? base + log(s) : neg_inf();
+                }
+                __syncthreads();
+            }
+            // A: bend_t, the end posterior E_t and gamma_t
+            for (int j = tid; j < S; j += kHsThreads) {
+                double bend;
+                if (t == T_ - 1) {
+                    bend = (double)fin[j];
+                } else {
+                    double m = neg_inf(), s = 0.0;
+                    for (int e = out_ptr[j]; e < out_ptr[j + 1]; ++e) {
+                        const int k = out_dst[e];
+                        if (k != j) hs_add(m, s, r0[k] + (double)out_w[e]);
+                    }
+                    const int hs = n_hubs > 0 ? L.hub_src_id[j] : -1;
+                    if (hs >= 0 && hs < n_hubs) {
+                        if (L.hub_dst_id[j] == hs) {
+                            for (int p = L.dst_ptr[hs]; p < L.dst_ptr[hs + 1]; ++p) {
+                                const int k = L.dst_list[p];
+                                if (k != j) hs_add(m, s, r0[k] + (double)hdw[k] + (double)hsw[j]);
+                            }
+                        } else {
+                            hs_add(m, s, hubv[hs] + (double)hsw[j]);
+                        }
+                    }
+                    bend = hs_value(m, s) + lv[j];
+                }
+                const double ex = endT[t * S + j] + bend + kapE;
+                const double E = ex > neg_inf() ? exp(ex) : 0.0;
+                const double gm = t == T_ - 1 ? E : (g_row[j] - bprev[j]) + E;
+                g_row[j] = gm;
+                gamma[t * S + j] = (T)(gm > 0.0 ? gm : 0.0);
+                r1[j] = bend;
+            }
+            __syncthreads();
+            // B: the ring, bbeg_t, the begin posterior B_t and the duration counts
+            const int kn = (int)(t % D);
+            for (int jb = 0; jb < S; jb += nteams) {
+                const int j = jb + tj;
+                const bool valid = j < S;
+                const int id = valid ? sid[j] : -1;
+                const double aj = valid ? ((double)llh[t * S + j] - ct) - npn : neg_inf();
+                const double bev = valid ? r1[j] : neg_inf();
+                const double* lam = a.log_dur + (size_t)(id < 0 ? 0 : id) * D;
+                double* V = ring + (size_t)(valid ? j : 0) * D;
+                double m = neg_inf();
+                if (valid) {
+                    for (int k = tl; k < D; k += team) {
+                        const double r = (k == kn ? bev : V[k]) + aj;
+                        V[k] = r;
+                        int dd = k - kn;
+                        if (dd < 0) dd += D;
+                        m = hmax(m, id < 0 ? neg_inf() : r + lam[dd]);
+                    }
+                }
+                for (int o = team >> 1; o > 0; o >>= 1) m = hmax(m, __shfl_xor(m, o));
+                const double base = m > neg_inf() ? m : 0.0;
+                double s = 0.0;
+                if (valid && id >= 0 && m > neg_inf()) {
+                    const double fx = base + begT[t * S + j] + kapB;
+                    const double F = fx > neg_inf() ? exp(fx) : 0.0;
+                    double* A = acc + (size_t)j * D;
+                    for (int k = tl; k < D; k += team) {
+                        int dd = k - kn;
+                        if (dd < 0) dd += D;
+                        const double p = exp(V[k] + lam[dd] - base);
+                        s += p;
+                        if (counts) A[dd] += p * F;
+                    }
+                    for (int o = team >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                    if (tl == 0) {
+                        const double Bv = s * F;
+                        r0[j] = s > 0.0 ? base + log(s) : neg_inf();
+                        bprev[j] = Bv;
+                        if (t == 0) {
+                            if (a.gamma0_sum) atomicAdd(a.gamma0_sum + j, Bv);
+                        } else {
+                            ent[j] += Bv;
+                        }
+                    }
+                } else {
+                    for (int o = team >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                    if (valid && tl == 0) { r0[j] = neg_inf(); bprev[j] = 0.0; }
+                }
+            }
+            __syncthreads();
+            // R: n'_t
+            double nm = neg_inf(), dm = neg_inf();
+            for (int j = tid; j < S; j += kHsThreads) nm = hmax(nm, r0[j]);
+            hs_block_max2(nm, dm, red);
+            const double nt = hs_quant(nm);
+            Np2 = Np1;
+            Np1 += nt;
+            npn = nt;
+        }
+        __syncthreads();
+        if (a.entry_sum)
+            for (int j = tid; j < S; j += kHsThreads) atomicAdd(a.entry_sum + j, ent[j]);
+        if (counts) {
+            for (int i = tid; i < S * D; i += kHsThreads) {
+                const int j = i / D, id = sid[j];
+                const double v = acc[i];
+                if (id >= 0 && v != 0.0) atomicAdd(a.dur_counts + (size_t)id * D + (i - j * D), v);
+            }
+        }
+    }
+}
+
+// The form of a launch (beer_hsmm_route packs it): false where the launch refuses
+struct HsmmPlan {
+    int team_log2, ring_lds, lowdeg, grid;
+    size_t lds, ring_total;
+};
+inline bool hsmm_plan(int dtype, const beer_batch* b, int D, HsmmPlan* p) {
+    if (!b || b->nutt < 0 || (dtype != BEER_F32 && dtype != BEER_F64) || D < 1 ||
+        D > BEER_HSMM_MAX_DUR || b->max_states < 1 || b->max_states > BEER_HSMM_MAX_STATES)
+        return false;
+    const size_t S = (size_t)b->max_states;
+    const size_t rows = (kHsRows * S + kHsMisc) * 8, ring = 2 * S * (size_t)D * 8;
+    p->ring_lds = rows + ring <= (size_t)kMaxDynLds;
+    p->lds = rows + (p->ring_lds ? ring : 0);
+    p->lowdeg = b->all_lowdeg != 0 && b->max_degree > 0 && b->max_hubs <= kHsMaxHubs;
+    int team = 1, lg = 0;
+    while (team * 2 <= 64 && team < D && (size_t)team * 2 * S <= (size_t)kHsThreads) {
+        team *= 2;
+        ++lg;
+    }
+    p->team_log2 = lg;
+    p->grid = b->nutt < kHsMaxGrid ? b->nutt : kHsMaxGrid;
+    p->ring_total = p->ring_lds ? 0 : (size_t)p->grid * 2 * S * (size_t)D;
+    return true;
+}
+
+template <typename T, bool VIT>
+int hsmm_launch(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
+                void* stream) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, VIT>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    hipLaunchKernelGGL((hsmm_kernel<T, VIT>), dim3(p.grid), dim3(kHsThreads), p.lds,
+                       as_stream(stream), *b, (const T*)pc_llhs, a);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+template <typename T>
+int hsmm_launch_fb(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
+                   void* stream) {
+    return hsmm_launch<T, false>(b, p, pc_llhs, a, stream);
+}
+template <typename T>
+int hsmm_launch_vit(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
+                    void* stream) {
+    return hsmm_launch<T, true>(b, p, pc_llhs, a, stream);
+}
+
+HsArgs hsmm_args(const HsmmPlan& p, const double* log_dur, const double* leave_w, int D,
+                 int S_total, double* ws) {
+    HsArgs a = {};
+    a.log_dur = log_dur;
+    a.leave_w = leave_w;
+    a.D = D;
+    a.S_total = S_total;
+    a.ws = ws;
+    a.ring_total = p.ring_total;
+    a.ring_lds = p.ring_lds;
+    a.lowdeg = p.lowdeg;
+    a.team_log2 = p.team_log2;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int beer_hsmm_forward_backward(int dtype, const beer_batch* b, const void* pc_llhs,
+                               const double* log_dur, const double* leave_w, int D, int S_total,
+                               double* ws, void* gamma, double* utt_evidence,
+                               double* dur_counts, double* entry_sum, double* gamma0_sum,
+                               void* stream) {
+    HsmmPlan p;
+    BEER_REQUIRE(hsmm_plan(dtype, b, D, &p));
+    BEER_REQUIRE(S_total >= 1);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_llhs && log_dur && ws && gamma);
+    HsArgs a = hsmm_args(p, log_dur, leave_w, D, S_total, ws);
+    a.gamma = gamma;
+    a.utt_evidence = utt_evidence;
+    a.dur_counts = dur_counts;
+    a.entry_sum = entry_sum;
+    a.gamma0_sum = gamma0_sum;
+    BEER_DISPATCH(dtype, hsmm_launch_fb, b, p, pc_llhs, a, stream);
+}
+
+int beer_hsmm_viterbi(int dtype, const beer_batch* b, const void* pc_llhs, const double* log_dur,
+                      const double* leave_w, int D, int S_total, double* ws, int64_t* path,
+                      double* score, int map_pdf, void* stream) {
+    HsmmPlan p;
+    BEER_REQUIRE(hsmm_plan(dtype, b, D, &p));
+    BEER_REQUIRE(S_total >= 1);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_llhs && log_dur && ws && path && score);
+    HsArgs a = hsmm_args(p, log_dur, leave_w, D, S_total, ws);
+    a.path = path;
+    a.score = score;
+    a.map_pdf = map_pdf;
+    BEER_DISPATCH(dtype, hsmm_launch_vit, b, p, pc_llhs, a, stream);
+}
+
+size_t beer_hsmm_scratch_doubles(int dtype, const beer_batch* b, int D) {
+    HsmmPlan p;
+    if (!hsmm_plan(dtype, b, D, &p)) return 0;
+    return p.ring_total;
+}
+
+int beer_hsmm_route(int dtype, const beer_batch* b, int D) {
+    HsmmPlan p;
+    BEER_REQUIRE(hsmm_plan(dtype, b, D, &p));
+    return BEER_HSMM_BLOCK | (p.ring_lds ? BEER_HSMM_RING_LDS : 0) |
+           (p.lowdeg ? BEER_HSMM_LOWDEG : 0) | p.team_log2;
+}
+
+}  // extern "C"

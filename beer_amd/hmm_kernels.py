@@ -18,7 +18,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'check_arc_categories', 'viterbi_nbest', 'nbest_route', 'check_nbest',
            'max_marginals', 'maxmarg_route', 'SegmentMap', 'segment_map', 'segments_route',
            'segment_margins', 'segments_within', 'check_segments', 'segposts_route',
-           'segment_posteriors', 'segments_above', 'check_segment_posteriors']
+           'segment_posteriors', 'segments_above', 'check_segment_posteriors',
+           'check_durations', 'duration_route', 'duration_forward_backward', 'duration_viterbi']
 
 
 class HmmBatch:
@@ -1144,6 +1145,95 @@ def segments_above(entry_frame, entry_cat, seg, min_post):
     at = torch.nonzero(_above(seg, float(min_post)))
     start = entry_frame[at[:, 0]]
     return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
+
+
+def check_durations(log_dur, S_total, leave_w=None):
+    '''The duration table of the explicit-duration entry points, checked on the host before any
+    launch: `log_dur` a float64 tensor [S_total, D] with 1 <= D <= BEER_HSMM_MAX_DUR, no NaN and
+    no +inf (-inf is legal); `leave_w` None or float64 [S_total], finite.  Returns D.'''
+    if not torch.is_tensor(log_dur) or log_dur.dtype != torch.float64 or log_dur.dim() != 2:
+        raise ValueError('durations: log_dur is a float64 tensor [S_total, D]')
+    if log_dur.shape[0] != int(S_total):
+        raise ValueError(f'durations: log_dur has {log_dur.shape[0]} rows for {S_total} pdf ids')
+    D = int(log_dur.shape[1])
+    if not 1 <= D <= _hip.HSMM_MAX_DUR:
+        raise ValueError(f'durations: D = {D} is outside 1 .. {_hip.HSMM_MAX_DUR} '
+                         '(BEER_HSMM_MAX_DUR)')
+    if bool(torch.isnan(log_dur).any()) or bool((log_dur == float('inf')).any()):
+        raise ValueError('durations: log_dur holds NaN or +inf')
+    if leave_w is not None:
+        if not torch.is_tensor(leave_w) or leave_w.dtype != torch.float64 or \
+                tuple(leave_w.shape) != (int(S_total),):
+            raise ValueError(f'durations: leave_w is a float64 tensor [{S_total}]')
+        if not bool(torch.isfinite(leave_w).all()):
+            raise ValueError('durations: leave_w must be finite')
+    return D
+
+
+def duration_route(batch, D):
+    '''beer_hsmm_route: the form the explicit-duration kernels take for this batch and D (the
+    team of lanes per state, ring in LDS or not, low-degree images or the full CSR); HipInvalid
+    -- naming the limit -- where they refuse.'''
+    route = _hip.lib().beer_hsmm_route(_hip.dtype_code(batch.dtype), batch.ref(), int(D))
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'explicit durations: D = {D} on graphs of up to {batch.struct.max_states} states: at '
+            f'most {_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
+            f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)')
+    return route
+
+
+def _duration_args(batch, pc_llhs, log_dur, leave_w):
+    S_total = log_dur.shape[0] if torch.is_tensor(log_dur) and log_dur.dim() == 2 else 0
+    D = check_durations(log_dur, S_total, leave_w)
+    if len(batch._pdf_ids_h) and int(batch._pdf_ids_h.max()) >= S_total:
+        raise ValueError(f'durations: a pdf id of the batch is not below {S_total}')
+    if pc_llhs.dtype != batch.dtype or pc_llhs.numel() != batch.n_elems:
+        raise ValueError('durations: pc_llhs is the packed buffer of the batch, in its dtype')
+    duration_route(batch, D)
+    log_dur = _hip.on_device(log_dur)
+    leave_w = None if leave_w is None else _hip.on_device(leave_w)
+    extra = _hip.lib().beer_hsmm_scratch_doubles(_hip.dtype_code(batch.dtype), batch.ref(), D)
+    ws = torch.empty(max(2 * batch.n_elems + 2 * batch.n_frames + extra, 1), dtype=torch.float64,
+                     device=batch.device)
+    return D, S_total, log_dur, leave_w, ws
+
+
+def duration_forward_backward(batch, pc_llhs, log_dur, leave_w=None, want_counts=True):
+    '''Forward-backward over (state, duration) (`beer_hsmm_forward_backward`): (gamma packed,
+    evidence [nutt] fp64, dur_counts [S_total, D] fp64 or None, entry_sum [S] fp64 or None,
+    gamma0_sum [S] fp64 or None).  `log_dur` [S_total, D] float64 are the log duration laws by
+    pdf id, `leave_w` [S_total] float64 (None: 0) is added to every arc that leaves a state.
+    `want_counts`: the duration counts and -- when the batch shares one graph -- the segment
+    entries per state from the second frame on and in the first frame.'''
+    D, S_total, log_dur, leave_w, ws = _duration_args(batch, pc_llhs, log_dur, leave_w)
+    dt, dev = batch.dtype, batch.device
+    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
+    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    counts = entry = g0 = None
+    if want_counts:
+        counts = torch.zeros(S_total, D, dtype=torch.float64, device=dev)
+        if batch.shared_graph:
+            entry = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+            g0 = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+    _hip.call('beer_hsmm_forward_backward', _hip.dtype_code(dt), batch.ref(), _hip.ptr(pc_llhs),
+              _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, _hip.ptr(ws), _hip.ptr(gamma),
+              _hip.ptr(evidence), _hip.ptr(counts), _hip.ptr(entry), _hip.ptr(g0))
+    return gamma, evidence, counts, entry, g0
+
+
+def duration_viterbi(batch, pc_llhs, log_dur, leave_w=None, map_pdf=False):
+    '''(path int64 [n_frames] -- state indices, or pdf ids with `map_pdf` --, score [nutt] fp64):
+    the best segmentation under explicit durations (`beer_hsmm_viterbi`).  An utterance without
+    a finite path has the score -inf and a path of -1.'''
+    D, S_total, log_dur, leave_w, ws = _duration_args(batch, pc_llhs, log_dur, leave_w)
+    dev = batch.device
+    path = torch.empty(batch.n_frames, dtype=torch.int64, device=dev)
+    score = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    _hip.call('beer_hsmm_viterbi', _hip.dtype_code(batch.dtype), batch.ref(), _hip.ptr(pc_llhs),
+              _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, _hip.ptr(ws), _hip.ptr(path),
+              _hip.ptr(score), 1 if map_pdf else 0)
+    return path, score
 
 
 def path_posteriors(batch, path, want_xi=False):

@@ -397,6 +397,11 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         # their image before the first recursion, counts by category out of the launches
         model._bound_set(graphs).refresh(dtype)
     tcounts_tot = None
+    # explicit durations (HMM.durations): their own forward-backward over (state, duration)
+    durations = model.durations is not None
+    if durations and (viterbi or state_paths is not None or sample is not None):
+        model._refuse_durations('viterbi=, state_paths= or sample= training')
+    dur_tot = ent_tot = None
     bigram = free_loop and isinstance(model, BigramPhoneLoop)
     counts_tot = None
     max_S = model.graph.n_states if free_loop else max(g.n_states for g in graphs)
@@ -410,6 +415,8 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
     bpf = (K_scratch + 2 * S_total) * X.element_size() + max_S * (3 * X.element_size() + 8)
     if sample is not None:
         bpf += 16                                 # the uniform and the drawn state of a frame
+    if durations:
+        bpf += 16 * max_S + 16                    # the beg / end trellises and two offsets a frame
     if bigram:
         model.declare_block()
         bpf += 16 * len(model.start_pdf)          # the u / v rows the bigram counts come from
@@ -465,6 +472,21 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
                 statics.items.pop(bkey)
                 batch, _, uniq, images = statics.entry(skey, bkey, make_batch)
         hard = viterbi or state_paths is not None or sample is not None
+        if durations:
+            # gather, forward-backward over (state, duration), scatter; the counts are summed
+            # over the sub-batches
+            pc_llhs = hk.gather(batch, pc_all, scale)
+            gamma, _, dc, entry, g0 = hk.duration_forward_backward(
+                batch, pc_llhs, *model._duration_tables())
+            sr, _ = hk.scatter(batch, pc_llhs, gamma, S_total, scale, want_exp_llh=False,
+                               utt_llh=utt_llh[run[0]:run[-1] + 1])
+            dur_tot = dc if dur_tot is None else dur_tot + dc
+            if free_loop:
+                ent_tot = entry if ent_tot is None else ent_tot + entry
+                g0_tot = g0 if g0_tot is None else g0_tot + g0
+            _accumulate_emissions(groups, comps, accs, sr, stats, tied_counts)
+            done.record()
+            continue
         if bigram and not hard:
             # the fused bigram kernel (the general path when the block does not qualify)
             sr, counts = hk.posteriors_bigram(batch, pc_all, scale,
@@ -537,6 +559,8 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
             out.update(grp.weights_accumulate(cnt))
     if learned:
         out.update(model.transitions.accumulate_counts(tcounts_tot))
+    if durations:
+        out.update(model.durations.accumulate_counts(dur_tot))
     if isinstance(model, BigramPhoneLoop):
         if bigram and counts_tot is None and xi_tot is not None:       # (Viterbi training)
             counts_tot = model.bigram_counts(xi_tot)
@@ -546,8 +570,13 @@ def _hmm_batch(model, X, lengths, datasize, graphs, scale, viterbi, state_paths,
         wparam = model.categorical.mean_field_factorization()[0][0]
         ref = wparam.stats
         if free_loop:
-            counts = model.phone_counts(xi_tot, g0_tot, flow_tot).to(dtype=ref.dtype,
-                                                                     device=ref.device)
+            if durations:
+                # a phone is counted where a segment of its start state begins
+                _, starts = model._index_tensors(g0_tot.device)
+                counts = g0_tot[starts] + ent_tot[starts]
+            else:
+                counts = model.phone_counts(xi_tot, g0_tot, flow_tot)
+            counts = counts.to(dtype=ref.dtype, device=ref.device)
             # per-utterance `sufficient_statistics` (last <- sum) then sum over
             # utterances == the same map applied to the summed counts.
             cstats = model.categorical.sufficient_statistics(counts.view(1, -1))
@@ -670,12 +699,25 @@ def accumulate_elbo(model, utterances, datasize=-1, inference_graphs=None, scale
     return _finish(model, value_terms, kl, len(lengths), acc, datasize, total)
 
 
+def _no_durations(model, what):
+    'NotImplementedError for the searches explicit durations (HMM.durations) do not cover.'
+    if getattr(model, 'durations', None) is not None:
+        model._refuse_durations(what)
+
+
 def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20,
                  predictive=False):
     '''Viterbi pdf-id paths for a shard: list of int64 tensors, one per
     utterance (`HMM.decode`, beer/models/hmm.py:105-114, batched).  `predictive`: the
     emissions are the posterior-predictive densities; the arcs of the graphs are used as
     they stand (fixed, or E[ln a] / E[ln pi] where learned), as in `HMM.decode`.'''
+    if getattr(model, 'durations', None) is not None:
+        # explicit durations: back-pointers (source, duration) in two doubles per state
+        tables = model._duration_tables()
+        return _paths_batch(model, utterances, inference_graphs, scale, max_frames, 16,
+                            lambda batch, pc_llhs: hk.duration_viterbi(
+                                batch, pc_llhs, *tables, map_pdf=True)[0],
+                            trellis_bytes=16, predictive=predictive)
     return _paths_batch(model, utterances, inference_graphs, scale, max_frames, 0,
                         lambda batch, pc_llhs: hk.viterbi(batch, pc_llhs, map_pdf=True),
                         predictive=predictive)
@@ -686,6 +728,7 @@ def sample_paths_batch(model, utterances, inference_graphs=None, scale=1., nsamp
     '''`nsamples` pdf-id paths per utterance drawn from the posterior: list of int64
     [nsamples, T_u] tensors, one per utterance (`HMM.sample_path`, batched).  `generator`: a
     device torch.Generator for the uniforms.'''
+    _no_durations(model, 'sample_paths_batch')
     nsamples = int(nsamples)
     if nsamples < 1:
         raise ValueError('sample_paths_batch: at least one sample')
@@ -703,6 +746,7 @@ def decode_nbest_batch(model, utterances, k, inference_graphs=None, scale=1.,
     (`HMM.decode_nbest`, batched): (list of int64 [k, T_u] tensors, float64 [nutt, k]) on the
     device, best first; ranks without a path of finite score hold -1 and -inf.'''
     k = hk.check_nbest(k, 'decode_nbest_batch')
+    _no_durations(model, 'decode_nbest_batch')
     scores = []
 
     def search(batch, pc_llhs):
@@ -734,6 +778,17 @@ def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_f
             raise ValueError(f'log_evidence_batch: {len(inference_graphs)} inference graphs for '
                              f'{nutt} utterances')
     totals, frames = [], []
+    if getattr(model, 'durations', None) is not None:
+        if per_frame:
+            model._refuse_durations('log_evidence_batch(per_frame=True)')
+        tables = model._duration_tables()
+        for batch, pc_llhs, _ in _search_batches(model, utterances, inference_graphs, scale,
+                                                 max_frames, 16, 16 + utterances[0].element_size()
+                                                 if packed else 24, predictive=predictive):
+            totals.append(hk.duration_forward_backward(batch, pc_llhs, *tables,
+                                                       want_counts=False)[1])
+        return torch.cat(totals) if totals else \
+            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())
     # decode_batch's scratch without the trellis; a float64 per frame besides
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 if per_frame else 0, 0,
@@ -781,6 +836,7 @@ def unit_segments_batch(model, utterances, beam=10., max_dur=None, inference_gra
     length of the longest utterance of a sub-batch, which cuts nothing.'''
     what = 'unit_segments_batch'
     beam, max_dur = hk.check_segments(beam, max_dur, what)
+    _no_durations(model, what)
     packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
         isinstance(utterances[0], torch.Tensor)
     if not packed:
@@ -827,6 +883,7 @@ def _segment_posteriors_batches(what, model, utterances, min_post, max_dur, infe
                                 scale, max_frames):
     '''(batch, lengths, `hk.segment_posteriors`' outputs) per sub-batch of a shard, under the
     unit-start categories; the arguments are checked before the first sub-batch is built.'''
+    _no_durations(model, what)
     packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
         isinstance(utterances[0], torch.Tensor)
     if not packed:
@@ -907,6 +964,7 @@ def unit_durations_batch(model, utterances, max_dur, inference_graphs=None, scal
 
 def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame,
                      margins=False):
+    _no_durations(model, what)
     packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
         isinstance(utterances[0], torch.Tensor)
     if not packed:

@@ -53,6 +53,8 @@ class CapturedIteration:
     def __init__(self, model, optim, data, datasize=-1, **kwargs):
         if not isinstance(optim, VBConjugateOptimizer):
             raise TypeError('CapturedIteration drives a VBConjugateOptimizer')
+        if getattr(model, 'durations', None) is not None:
+            model._refuse_durations('CapturedIteration')
         self.model, self.optim = model, optim
         # `data`: one resident minibatch [T, D] (-> evidence_lower_bound), or a shard of
         # utterances as `(X_packed, lengths)` (-> accumulate_elbo: the batched E-step of

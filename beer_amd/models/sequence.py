@@ -13,9 +13,10 @@ from ..stats import reference_layout_enabled
 from .basemodel import DiscreteLatentModel, Model
 from .gaussians import NormalSet
 from .modelset import DynamicallyOrderedModelSet
+from .durations import StateDurations
 from .weights import Categorical, CategoricalSet, SBCategorical, SBCategoricalSet
 
-__all__ = ['HMM', 'PhoneLoop', 'BigramPhoneLoop', 'HMMTransitions']
+__all__ = ['HMM', 'PhoneLoop', 'BigramPhoneLoop', 'HMMTransitions', 'StateDurations']
 
 
 class HMMTransitions(Model):
@@ -213,16 +214,24 @@ class HMM(DiscreteLatentModel):
     with `train_transitions=True` (`transitions`: `HMMTransitions`, None = fixed).'''
 
     @classmethod
-    def create(cls, graph, modelset, train_transitions=False, transitions_prior_strength=1.):
+    def create(cls, graph, modelset, train_transitions=False, transitions_prior_strength=1.,
+               max_duration=0, durations_prior_strength=1.):
+        '''`max_duration` D > 0 (not in the reference): explicit state durations of 1 .. D frames
+        (`StateDurations`, learned under Dirichlet priors of strength
+        `durations_prior_strength`); 0: the geometric stay of the self-loops.'''
+        cls._check_durations_with(max_duration, train_transitions)
         transitions = HMMTransitions.create(graph.trans_log_probs,
                                             prior_strength=transitions_prior_strength) \
             if train_transitions else None
-        return cls(graph, modelset, transitions)
+        durations = StateDurations.create(graph, max_duration, durations_prior_strength) \
+            if max_duration else None
+        return cls(graph, modelset, transitions, durations)
 
-    def __init__(self, graph, modelset, transitions=None):
+    def __init__(self, graph, modelset, transitions=None, durations=None):
         super().__init__(DynamicallyOrderedModelSet(modelset))
         self.graph = graph
         self.transitions = transitions
+        self.durations = durations
         if transitions is not None:
             self._attach_transitions()
 
@@ -230,10 +239,30 @@ class HMM(DiscreteLatentModel):
         try:
             return super().__getattr__(name)
         except AttributeError:
-            # (models pickled before transitions could be learned, the reference's included)
-            if name == 'transitions':
+            # (models pickled before transitions / durations could be learned, the reference's
+            #  included)
+            if name in ('transitions', 'durations'):
                 return None
             raise
+
+    # -- explicit durations ---------------------------------------------------------
+    @staticmethod
+    def _check_durations_with(max_duration, train_transitions):
+        if max_duration and train_transitions:
+            raise NotImplementedError(
+                'explicit durations (max_duration > 0) with learned transitions '
+                '(train_transitions=True) are not supported: a stay is the duration law\'s, and '
+                'the transition counts of the kernels include the self-loops')
+
+    def _refuse_durations(self, what):
+        'NotImplementedError naming the combination, for what explicit durations do not cover.'
+        if self.durations is not None:
+            raise NotImplementedError(
+                f'explicit durations (max_duration > 0) with {what} are not supported: the '
+                'explicit-duration kernels cover forward-backward, Viterbi and the evidence only')
+
+    def _duration_tables(self):
+        return self.durations.log_dur(), self.durations.leave_w()
 
     # -- learned transitions --------------------------------------------------------
     def _attach_transitions(self):
@@ -435,6 +464,8 @@ class HMM(DiscreteLatentModel):
         mff = self.modelset.mean_field_factorization()
         if self.transitions is not None:
             mff = list(mff) + self.transitions.mean_field_factorization()
+        if self.durations is not None:
+            mff = list(mff) + self.durations.mean_field_factorization()
         return mff
 
     def sufficient_statistics(self, data):
@@ -450,6 +481,11 @@ class HMM(DiscreteLatentModel):
         reference): True, or a float64 tensor of one uniform per frame -- a state path is
         drawn from the posterior (`hk.sample_paths`) and trained on as `state_path=` is.'''
         sample = hk.check_sample(sample, len(stats), viterbi, state_path)
+        if self.durations is not None:
+            if viterbi or state_path is not None or sample is not None:
+                self._refuse_durations('viterbi=, state_path= or sample= training')
+            return self._duration_expected_log_likelihood(stats, inference_graph, scale,
+                                                          utt_lengths)
         trans_posts = inference_graph is None
         learned = self.transitions is not None
         # (alignment graphs of a learned model: bound ones only -- checked before any device work)
@@ -542,6 +578,35 @@ class HMM(DiscreteLatentModel):
         self.cache['scale'] = scale
         return self._with_gradient(stats, exp_llh, state_resps, emissions, dense)
 
+    def _duration_expected_log_likelihood(self, stats, inference_graph, scale, utt_lengths):
+        '''The E-step under explicit durations: gather, `hk.duration_forward_backward`, scatter.
+        The cache gets the duration counts and -- on the model's own graph -- the segment
+        entries per state a phone loop counts its phones from.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        if kernels.is_dense(stats) or kernels.has_source(stats):
+            self._refuse_durations('a VAE prior (differentiable statistics)')
+        emissions = self._emissions()
+        pc_all = emissions.expected_log_likelihood(stats.detach())
+        self.modelset.cache['order'] = graph.pdf_id_mapping
+        T, S_total = pc_all.shape
+        if utt_lengths is None:
+            batch = self._batch_of_one(graph, T, pc_all.dtype)
+        else:
+            lengths = [int(n) for n in utt_lengths]
+            if sum(lengths) != T:
+                raise ValueError('utt_lengths do not add up to the number of frames')
+            batch = hk.HmmBatch([graph], [0] * len(lengths), lengths, pc_all.dtype)
+        pc_llhs = hk.gather(batch, pc_all, scale)
+        log_dur, leave_w = self._duration_tables()
+        gamma, _, counts, entry, g0 = hk.duration_forward_backward(batch, pc_llhs, log_dur, leave_w)
+        state_resps, exp_llh = hk.scatter(batch, pc_llhs, gamma, S_total, scale)
+        self.cache['resps'] = gamma.view(T, -1)
+        self.cache['dur_counts'] = counts
+        self.cache['dur_entries'] = (g0, entry) if inference_graph is None else None
+        self.cache['scaled_pdf_resps'] = state_resps
+        self.cache['scale'] = scale
+        return exp_llh
+
     @staticmethod
     def _with_gradient(stats, exp_llh, state_resps, emissions, dense):
         'The value with its gradient w.r.t. differentiable statistics / frames (a VAE\'s prior).'
@@ -562,6 +627,8 @@ class HMM(DiscreteLatentModel):
         retval = {**self._emissions().accumulate(stats, self.cache['scaled_pdf_resps'])}
         if self.transitions is not None:
             retval.update(self.transitions.accumulate_counts(self.cache['trans_counts']))
+        if self.durations is not None:
+            retval.update(self.durations.accumulate_counts(self.cache['dur_counts']))
         return retval
 
     # -- DiscreteLatentModel interface ------------------------------------------------
@@ -585,6 +652,9 @@ class HMM(DiscreteLatentModel):
             self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
         pc_llhs = hk.gather(batch, pc_all, scale)
+        if self.durations is not None:
+            return hk.duration_viterbi(batch, pc_llhs, *self._duration_tables(),
+                                       map_pdf=True)[0].cpu()
         return hk.viterbi(batch, pc_llhs, map_pdf=True).cpu()
 
     def decode_nbest(self, data, k, inference_graph=None, scale=1.):
@@ -594,6 +664,7 @@ class HMM(DiscreteLatentModel):
         precision; row 0 is `decode`'s path whenever its score is finite.  Ranks beyond the
         number of paths of finite score have the score -inf and a row of -1.  Not in the
         reference.  Otherwise as `decode`.'''
+        self._refuse_durations('decode_nbest')
         k = hk.check_nbest(k, 'decode_nbest')
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
@@ -609,6 +680,7 @@ class HMM(DiscreteLatentModel):
         '''`nsamples` state paths drawn from the posterior, mapped to pdf ids: LongTensor
         [nsamples, T] on the host.  `generator`: a device torch.Generator for the uniforms
         (default: the device's global one).  Otherwise as `decode`.'''
+        self._refuse_durations('sample_path')
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
         pc_all = self._emissions().expected_log_likelihood(stats)
@@ -634,6 +706,11 @@ class HMM(DiscreteLatentModel):
         if getattr(getattr(graph, '_set', None), 'is_bound', False):
             self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        if self.durations is not None:
+            if per_frame:
+                self._refuse_durations('log_evidence(per_frame=True)')
+            return hk.duration_forward_backward(batch, hk.gather(batch, pc_all, scale),
+                                                *self._duration_tables(), want_counts=False)[1][0]
         utt, frame = hk.log_evidence(batch, hk.gather(batch, pc_all, scale), per_frame=per_frame)
         return (utt[0], frame) if per_frame else utt[0]
 
@@ -646,6 +723,7 @@ class HMM(DiscreteLatentModel):
         sum over the frames, [n_cat] float64.  `arc_cat` follows `graph.out_arcs()`, `init_cat`
         the graph's states; entries are in [0, n_cat) or -1 (count nothing).  Not in the
         reference.  Otherwise as `decode`.'''
+        self._refuse_durations('arc_posteriors')
         graph = self.graph if inference_graph is None else inference_graph
         src, _ = graph.out_arcs()
         cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
@@ -664,6 +742,7 @@ class HMM(DiscreteLatentModel):
         every frame and state, the score of the best path through it minus `best`
         (`hmm_kernels.max_marginals`): 0 along `decode`'s path, negative off it, -inf where no
         path passes.  Not in the reference.  Otherwise as `decode`.'''
+        self._refuse_durations('max_marginals')
         graph = self.graph if inference_graph is None else inference_graph
         stats = self.sufficient_statistics(data)
         pc_all = self._emissions().expected_log_likelihood(stats)
@@ -682,6 +761,7 @@ class HMM(DiscreteLatentModel):
         `init_cat`; without it their maximum over the frames, [n_cat] float64.  -inf: no such
         path.  The categories are those of `arc_posteriors`.  Not in the reference.  Otherwise
         as `decode`.'''
+        self._refuse_durations('max_marginals')
         graph = self.graph if inference_graph is None else inference_graph
         src, _ = graph.out_arcs()
         cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
@@ -704,6 +784,10 @@ class HMM(DiscreteLatentModel):
         if getattr(getattr(graph, '_set', None), 'is_bound', False):
             self._bound_set(graph).refresh(pc_all.dtype)
         batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        if self.durations is not None:
+            gamma = hk.duration_forward_backward(batch, hk.gather(batch, pc_all, 1.),
+                                                 *self._duration_tables(), want_counts=False)[0]
+            return gamma.view(len(stats), -1)
         gamma = hk.forward_backward(batch, hk.gather(batch, pc_all, 1.))[0]
         return gamma.view(len(stats), -1)
 
@@ -768,6 +852,7 @@ def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, sc
     utterance's length); `beam` = inf keeps every possible segment.  The Viterbi segmentation
     has margin 0.  Otherwise as `decode`.'''
     beam, max_dur = hk.check_segments(beam, max_dur, 'unit_segments')
+    model._refuse_durations('the segment functions (unit_segments)')
     graph = model.graph if inference_graph is None else inference_graph
     arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
     n_units = len(model.start_pdf)
@@ -788,6 +873,7 @@ def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, sc
 def _segment_posteriors_of(model, data, min_post, max_dur, inference_graph, scale, what):
     '`hk.segment_posteriors` of one utterance under the unit-start categories: its five outputs.'
     min_post, max_dur = hk.check_segment_posteriors(min_post, max_dur, what)
+    model._refuse_durations(f'the segment functions ({what})')
     graph = model.graph if inference_graph is None else inference_graph
     arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
     n_units = len(model.start_pdf)
@@ -841,10 +927,14 @@ class PhoneLoop(HMM):
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categorical=None,
-               prior_strength=1.0, train_transitions=False, transitions_prior_strength=1.):
+               prior_strength=1.0, train_transitions=False, transitions_prior_strength=1.,
+               max_duration=0, durations_prior_strength=1.):
         '''`train_transitions` (not in the reference): learn the units' transition
         probabilities too (`HMMTransitions`: Dirichlet rows whose prior concentrations are
-        `transitions_prior_strength` x the graph's transition probabilities).'''
+        `transitions_prior_strength` x the graph's transition probabilities).  `max_duration`
+        D > 0 (not in the reference): explicit state durations of 1 .. D frames, as
+        `HMM.create` has them.'''
+        cls._check_durations_with(max_duration, train_transitions)
         tensor = modelset.mean_field_factorization()[0][0].prior._tensors()[0]
         if categorical is None:
             weights = torch.ones(len(start_pdf), dtype=tensor.dtype, device=tensor.device)
@@ -853,14 +943,21 @@ class PhoneLoop(HMM):
         transitions = HMMTransitions.create(
             graph.trans_log_probs, list(end_pdf.values()), list(start_pdf.values()),
             transitions_prior_strength) if train_transitions else None
-        return cls(graph, modelset, start_pdf, end_pdf, categorical, transitions)
+        durations = StateDurations.create(graph, max_duration, durations_prior_strength) \
+            if max_duration else None
+        return cls(graph, modelset, start_pdf, end_pdf, categorical, transitions, durations)
 
-    def __init__(self, graph, modelset, start_pdf, end_pdf, categorical, transitions=None):
+    def __init__(self, graph, modelset, start_pdf, end_pdf, categorical, transitions=None,
+                 durations=None):
         super().__init__(graph, modelset)
         self.start_pdf = start_pdf
         self.end_pdf = end_pdf
         self.categorical = categorical
         self.transitions = transitions
+        self.durations = durations
+        if durations is not None:
+            self._check_durations_with(True, transitions is not None)
+            self._check_units_for_durations()
         param = self.categorical.mean_field_factorization()[0][0]
         param.register_callback(self._on_weights_update)
         if transitions is not None:
@@ -870,6 +967,24 @@ class PhoneLoop(HMM):
 
     def _exit_states(self):
         return list(self.end_pdf.values())
+
+    def _check_units_for_durations(self):
+        '''Explicit durations count a phone where a segment of its start state begins: the start
+        states must be entered from end states only, and no unit's start state is its end state
+        (its one state would be entered from itself, which a duration law cannot express).'''
+        starts, ends = list(self.start_pdf.values()), list(self.end_pdf.values())
+        if set(starts) & set(ends):
+            raise NotImplementedError(
+                'explicit durations (max_duration > 0) with units whose start state is their end '
+                'state are not supported: a one-state unit that follows itself is a longer stay')
+        trans = self.graph.trans_log_probs.detach().to('cpu')
+        arcs = torch.isfinite(trans) & (trans.exp() > 0)
+        arcs.fill_diagonal_(False)
+        inner = torch.ones(trans.shape[0], dtype=torch.bool)
+        inner[torch.as_tensor(ends)] = False
+        if bool(arcs[inner][:, torch.as_tensor(starts)].any()):
+            raise ValueError('explicit durations: a unit\'s start state is entered from a state '
+                             'that ends no unit; the phone counts would miss it')
 
     def _on_transitions_update(self):
         '''Intra-unit entries <- E[ln a], then the phone exits <- E[ln a_exit] + E[ln w]: the
@@ -968,6 +1083,8 @@ class PhoneLoop(HMM):
                             self.categorical.mean_field_factorization())
         if self.transitions is not None:
             mff = mff + self.transitions.mean_field_factorization()
+        if self.durations is not None:
+            mff = mff + self.durations.mean_field_factorization()
         return mff
 
     def phone_counts(self, xi_sum, gamma0, hub_flow=None):
@@ -988,7 +1105,14 @@ class PhoneLoop(HMM):
         retval = super().accumulate(stats, parent_msg)
         wparam = self.categorical.mean_field_factorization()[0][0]
         ref = wparam.stats
-        if 'trans_resps' in self.cache:
+        if self.cache.get('dur_entries') is not None:
+            # explicit durations: a phone is counted where a segment of its start state begins
+            g0, entry = self.cache['dur_entries']
+            _, starts = self._index_tensors(g0.device)
+            counts = (g0[starts] + entry[starts]).to(dtype=ref.dtype, device=ref.device)
+            resps_stats = self.categorical.sufficient_statistics(counts.view(1, -1))
+            retval.update(self.categorical.accumulate(resps_stats))
+        elif 'trans_resps' in self.cache:
             first = self.cache.get('first_resps')
             counts = self.phone_counts(self.cache['trans_resps'],
                                        self.cache['resps'][0] if first is None else first,
@@ -1021,7 +1145,11 @@ class BigramPhoneLoop(HMM):
 
     @classmethod
     def create(cls, graph, start_pdf, end_pdf, modelset, categoricalset=None,
-               prior_strength=1.0, train_transitions=False):
+               prior_strength=1.0, train_transitions=False, max_duration=0):
+        if max_duration:
+            raise NotImplementedError('explicit durations (max_duration > 0) with a '
+                                      'BigramPhoneLoop are not supported: its fused kernel has '
+                                      'no duration laws')
         if train_transitions:
             raise ValueError('learned transitions (train_transitions=True) are not supported '
                              'on a bigram phone loop: its kernel does not count them')

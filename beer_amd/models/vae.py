@@ -52,6 +52,8 @@ class VAE(Model):
         # reference_broadcast=True (default): T x the per-frame value, the reference's own
         # result (its [T, 1] - [T] broadcast, vae.py:84-86); False: the per-frame value
         super().__init__()
+        if getattr(prior, 'durations', None) is not None:
+            prior._refuse_durations('a VAE prior')
         self.prior = prior
         self.encoder = encoder
         self.decoder = decoder

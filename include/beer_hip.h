@@ -1585,6 +1585,98 @@ int beer_hmm_path_posteriors(int dtype, const beer_batch* batch_h,
                              const int64_t* path, void* gamma, double* xi_sum,
                              double* gamma0_sum, void* stream);
 
+/* ---- explicit state durations (hidden semi-Markov model, Ferguson 1980) ------------------
+ * Every emitting state owns a law over how long ONE stay lasts, 1 .. D frames; the self-loop
+ * of the graph is not used.  No reference counterpart: the definitions below are the contract.
+ * For utterance u of T frames on graph g with S states:
+ *   id(j)    the pdf id of state j (the batch's pdf_ids)
+ *   l_t(j)   the packed pc_llhs
+ *   lam_j(d) = log_dur[id(j)][d-1], d = 1 .. D; `log_dur` is a device table [S_total, D] fp64;
+ *            -inf entries are legal (a minimum duration is a row that starts with -inf); a state
+ *            whose id is outside 0 .. S_total-1 has lam = -inf throughout
+ *   w_ij     = trans_ij + leave_w[id(i)] for every arc with i != j; `leave_w` [S_total] fp64,
+ *            nullable (NULL: 0), the renormalisation of a state's other arcs once its self-loop
+ *            is gone
+ * Arcs with src == dst are skipped wherever they are stored, in either CSR or in a hub block (a
+ * stay is the duration law's business); `final` gets no leave_w.  With lse the log-sum-exp over
+ * the finite terms (-inf when there are none):
+ *   beg_0(j)  = init_j                      beg_t(j) = lse_{i != j} end_{t-1}(i) + w_ij
+ *   end_t(j)  = lse_{d=1..min(D,t+1)}  beg_{t-d+1}(j) + lam_j(d) + sum_{tau=t-d+1..t} l_tau(j)
+ *   Z         = lse_j end_{T-1}(j) + final_j     (the last segment ends ON the last frame)
+ *   bend_{T-1}(j) = final_j                 bend_t(j) = lse_{k != j} w_jk + bbeg_{t+1}(k)
+ *   bbeg_t(j) = lse_{d=1..min(D,T-t)}  lam_j(d) + sum_{tau=t..t+d-1} l_tau(j) + bend_{t+d-1}(j)
+ *   q(j,s,d)  = exp(beg_s(j) + lam_j(d) + sum_{tau=s..s+d-1} l_tau(j) + bend_{s+d-1}(j) - Z)
+ * Outputs of beer_hsmm_forward_backward (all nullable but `gamma`; every += array is fp64):
+ *   gamma        packed like pc_llhs, in the batch's dtype, written (=):
+ *                gamma_t(j) = sum over (s, d) with s <= t < s + d of q(j,s,d); rows sum to 1
+ *   utt_evidence [nutt] fp64, written (=): Z
+ *   dur_counts   [S_total, D], += sum_s q(j,s,d) at [id(j)][d-1] (ids may repeat within a graph
+ *                and across utterances: fp64 atomic adds)
+ *   entry_sum    [S], += sum_{s>=1,d} q(j,s,d); the batch must share one graph
+ *   gamma0_sum   [S], += sum_d q(j,0,d); the batch must share one graph
+ * An utterance with no finite segmentation (Z = -inf) gets the evidence -inf, gamma rows all 0
+ * and nothing added to the three count arrays; an utterance of no frames the evidence 0.
+ * Numerics: the recursions run in fp64 log space whatever the dtype (exp and log in fp64 too);
+ * float32 differs only in the type of pc_llhs, gamma and the graph's weights.  Running segment
+ * scores sit in a ring indexed by start (backward: end) mod D: a frame adds l_t(j) - c_t - n to
+ * every live slot and takes one lse over the slots with the rotated lam_j -- no differences of
+ * prefix sums.  c_t is max_j l_t(j) rounded to an integer and n the previous frame's largest
+ * end (backward: begin) value rounded to a multiple of 1/256, so that their running sums are
+ * exact; gamma follows from gamma_t = gamma_{t+1} - B_{t+1} + E_t (B, E the begin and end
+ * posteriors), clamped at 0.  gamma, the evidence and the Viterbi path are the same bits on
+ * every run.  NaN and +inf inputs are outside the contract.
+ * `ws`: fp64 workspace of 2 doubles per element of pc_llhs (the beg and end trellises) plus
+ * 2 per frame of the batch plus beer_hsmm_scratch_doubles(dtype, batch, D).
+ * BEER_EINVAL (everything is checked before anything is launched): a dtype other than
+ * BEER_F32 / BEER_F64, D outside 1 .. BEER_HSMM_MAX_DUR, a graph of more than
+ * BEER_HSMM_MAX_STATES states, S_total < 1, a NULL pc_llhs, log_dur, ws or gamma. */
+#define BEER_HSMM_MAX_DUR 128
+#define BEER_HSMM_MAX_STATES 2048
+int beer_hsmm_forward_backward(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                               const double* log_dur, const double* leave_w, int D, int S_total,
+                               double* ws, void* gamma, double* utt_evidence,
+                               double* dur_counts, double* entry_sum, double* gamma0_sum,
+                               void* stream);
+
+/* The same recursion with max for lse: `path` [n_frames] int64 receives the state of every
+ * frame (graph state indices as beer_hmm_viterbi gives them, pdf ids with `map_pdf`), `score`
+ * [nutt] fp64 the score of the best segmentation.  Back-pointers are (source state, duration).
+ * Ties: the shorter duration first, then the smaller source state, then at the end the smaller
+ * final state.  An utterance without a finite path gets the score -inf and the path -1, one
+ * of no frames the score 0.  Reads the graph's full in-CSR, as beer_hmm_viterbi does (a hub's
+ * arcs are in it).  `ws` and BEER_EINVAL as above (path and score must not be NULL). */
+int beer_hsmm_viterbi(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                      const double* log_dur, const double* leave_w, int D, int S_total,
+                      double* ws, int64_t* path, double* score, int map_pdf, void* stream);
+
+/* Doubles `ws` must hold BESIDES the two trellises and the two values per frame: 0 while the
+ * rings fit LDS (BEER_HSMM_RING_LDS below), else 2 max_states D for each of the
+ * min(nutt, 512) workgroups of the launch.  0 where the entry points refuse the batch. */
+size_t beer_hsmm_scratch_doubles(int dtype, const beer_batch* batch_h, int D);
+
+/* The form the two entry points take for this batch and D (host only: it reads the scalar
+ * fields of the batch and launches nothing; the launcher decides with the same predicates).
+ * One workgroup of 256 threads per utterance, at most 512 workgroups striding over the batch
+ * (batch->order: longest first); with S = max_states:
+ *   BEER_HSMM_BLOCK | BEER_HSMM_RING_LDS | BEER_HSMM_LOWDEG | LOG2TEAM
+ *     LOG2TEAM            log2 of the lanes that share one state's D ring slots: the largest
+ *                         power of two `team` <= 64 with team / 2 < D and team S <= 256
+ *                         (1 when S > 128); 256 / team states are worked on at a time
+ *     BEER_HSMM_RING_LDS  the ring and the duration counts of the utterance, 2 S D doubles,
+ *                         sit in LDS beside the 8 S + 32 doubles of per-state rows:
+ *                         8 (8 S + 32 + 2 S D) <= 160 KiB; else in `ws`
+ *     BEER_HSMM_LOWDEG    forward-backward walks the low-degree images and their hubs:
+ *                         all_lowdeg != 0, max_degree > 0 (the host knows the images) and
+ *                         max_hubs <= 4; else the full CSR
+ * BEER_HSMM_TEAM(route) is the team.  BEER_EINVAL exactly where the entry points refuse the
+ * batch for its shape (dtype, D, max_states). */
+#define BEER_HSMM_BLOCK 0x1000
+#define BEER_HSMM_RING_LDS 0x100
+#define BEER_HSMM_LOWDEG 0x200
+#define BEER_HSMM_FAMILY(route) ((route) & 0xF000)
+#define BEER_HSMM_TEAM(route) (1 << ((route) & 0xF))
+int beer_hsmm_route(int dtype, const beer_batch* batch_h, int D);
+
 /* Scatter the (scaled) state posteriors back to pdf ids, repeated ids add
  * (DynamicallyOrderedModelSet.accumulate, beer/models/modelset.py:148-154,
  * with the scale of HMM.accumulate, hmm.py:95), and the per-frame expected
