@@ -196,6 +196,8 @@ def evidence_spl(route):
 # BEER_HSMM_* of include/beer_hip.h: the limits and what `beer_hsmm_route` returns
 HSMM_MAX_DUR, HSMM_MAX_STATES = 128, 2048
 HSMM_BLOCK, HSMM_RING_LDS, HSMM_LOWDEG = 0x1000, 0x100, 0x200
+# ... and the two bin bits of `beer_hsmm_arcs_route`
+HSMM_ARCS_FRAME_LDS, HSMM_ARCS_UTT_LDS = 0x400, 0x800
 
 
 def hsmm_team(route):
@@ -459,6 +461,9 @@ SIGNATURES = {
                                    c_p, c_p],
     'beer_hsmm_viterbi': [c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p],
     'beer_hsmm_route': [c_i, c_p, c_i],                            # (host only: no stream)
+    'beer_hsmm_arc_posteriors': [c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p,
+                                 c_p, c_p, c_p, c_p, c_p, c_p],
+    'beer_hsmm_arcs_route': [c_i, c_p, c_i, c_i, c_i],             # (host only: no stream)
     'beer_hmm_arc_posteriors': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
     'beer_hmm_arcs_route': [c_i, c_p, c_i, c_i],                   # (host only: no stream)
     'beer_hmm_max_marginals': [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
@@ -525,6 +530,7 @@ SIZE_QUERIES = {
     'beer_hmm_maxmarg_scratch_doubles': [c_i, c_p],
     'beer_hmm_segments_scratch_doubles': [c_i, c_p],
     'beer_hsmm_scratch_doubles': [c_i, c_p, c_i],
+    'beer_hsmm_arcs_scratch_doubles': [c_i, c_p, c_i],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
     'beer_cmllr_workspace_bytes': [c_i, c_i, c_l],
 }

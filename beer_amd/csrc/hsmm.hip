@@ -1,6 +1,7 @@
 // Explicit state durations (hidden semi-Markov model): forward-backward and Viterbi over
 // (state, duration) for every utterance of a ragged batch (include/beer_hip.h:
-// beer_hsmm_forward_backward, beer_hsmm_viterbi -- the definitions are there).
+// beer_hsmm_forward_backward, beer_hsmm_viterbi, beer_hsmm_arc_posteriors -- the definitions
+// are there).
 //
 // One workgroup of 256 threads per utterance, at most 512 workgroups striding over the batch.
 // fp64 log space throughout.  The running scores of the segments in progress sit in a ring
@@ -20,6 +21,8 @@
 // nothing but the evidence.
 // The posteriors come out of the backward pass: with B_t(j), E_t(j) the posteriors that a segment
 // of j begins / ends at t, gamma_t = gamma_{t+1} - B_{t+1} + E_t from gamma_{T-1} = E_{T-1}.
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -95,10 +98,45 @@ __device__ __forceinline__ double hs_quant(double v) {
     return v > neg_inf() ? __builtin_rint(v * kHsQuant) / kHsQuant : 0.0;
 }
 
-template <typename T, bool VIT>
-__global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
-                                                          const T* __restrict__ pc_llhs,
-                                                          HsArgs a) {
+// Arc posteriors by category (beer_hsmm_arc_posteriors): what the ARCS form of the body takes
+// besides HsArgs.  Bins as in hmm_arcs.hip: fp64 in LDS behind the rows and the ring while they
+// fit (hsmm_arcs_plan), else the output rows themselves with global atomic adds.
+struct HsArcArgs {
+    beer_arc_map map;
+    int n_cat;
+    int frame_lds, utt_lds;              // a frame's / the utterance's bins are in LDS
+    size_t bins_at;                      // doubles from the start of LDS to the first bin
+    void* frame_out;
+    double* utt_out;
+    double* total_out;
+};
+
+// ... and what the other two forms take in its place: nothing, every member a constant
+struct HsNoArcs {
+    static constexpr int n_cat = 0, frame_lds = 0, utt_lds = 0;
+    static constexpr size_t bins_at = 0;
+    static constexpr void* frame_out = nullptr;
+    static constexpr double* utt_out = nullptr;
+    static constexpr double* total_out = nullptr;
+};
+
+// fp64 add to a bin in LDS, with the LDS's own instruction (ds_add_f64)
+__device__ __forceinline__ void hs_lds_add(double* p, double v) {
+    typedef __attribute__((address_space(3))) double lds_double;
+    __hip_atomic_fetch_add((lds_double*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+constexpr int kHsFrameCats = 1024;       // a frame's bins stay in LDS up to here ...
+constexpr int kHsUttCats = 4096;         // ... and the utterance's up to here
+
+// ARCS (never with VIT): the full CSR whatever the batch offers, and in phase A of the backward
+// pass every arc's posterior exp(end_t(j) + w_jk + bbeg_{t+1}(k) - Z) -- the term of bend_t(j)
+// that is in hand there, with E_t's own offset kapE -- folded into row t + 1.  false: the code
+// of beer_hsmm_forward_backward / beer_hsmm_viterbi, in which `arc` is never read.
+template <typename T, bool VIT, bool ARCS>
+__global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
+    beer_batch b, const T* __restrict__ pc_llhs, HsArgs a,
+    typename std::conditional<ARCS, HsArcArgs, HsNoArcs>::type arc) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -119,6 +157,9 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
     double* acc = ring + (size_t)SM * D;
     const int team = 1 << a.team_log2, nteams = kHsThreads / team;
     const int tj = tid >> a.team_log2, tl = tid & (team - 1);
+    const int n_cat = ARCS ? arc.n_cat : 0;
+    double* fbin = rows + (ARCS ? arc.bins_at : 0);          // [n_cat] a frame's bins
+    double* ubin = fbin + ((ARCS && arc.frame_lds) ? n_cat : 0);   // [n_cat] the utterance's
 
     for (int slot = blockIdx.x; slot < b.nutt; slot += gridDim.x) {
         __syncthreads();                                     // the rows of the last utterance
@@ -128,11 +169,15 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
         const int S = g.n_states;
         const int64_t f0 = b.frame_off[u];
         const int64_t T_ = b.frame_off[u + 1] - f0;
+        double* urow = (ARCS && arc.utt_out) ? arc.utt_out + (int64_t)u * n_cat : nullptr;
+        T* frows = (ARCS && arc.frame_out) ? (T*)arc.frame_out + f0 * n_cat : nullptr;
         if (T_ <= 0) {
             if (tid == 0) {
                 if (VIT) a.score[u] = 0.0;
                 else if (a.utt_evidence) a.utt_evidence[u] = 0.0;
             }
+            if (ARCS && urow)
+                for (int c = tid; c < n_cat; c += kHsThreads) urow[c] = 0.0;
             continue;
         }
         const int64_t e0 = b.llh_off[u];
@@ -148,7 +193,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
         int32_t* bp = reinterpret_cast<int32_t*>(region);    // Viterbi: (source, duration)
 
         // arcs: the low-degree image and its hubs, or the full CSR
-        const bool ld = !VIT && a.lowdeg && g.lowdeg != nullptr;
+        const bool ld = !VIT && !ARCS && a.lowdeg && g.lowdeg != nullptr;
         beer_graph_lowdeg L = {};
         if (ld) L = *g.lowdeg;
         const int n_hubs = ld ? (L.n_hubs < kHsMaxHubs ? L.n_hubs : kHsMaxHubs) : 0;
@@ -369,6 +414,12 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
         if (!(zs > neg_inf())) {
             for (int64_t i = tid; i < T_ * S; i += kHsThreads) gamma[i] = (T)0;
             if (tid == 0 && a.utt_evidence) a.utt_evidence[u] = neg_inf();
+            if (ARCS) {
+                if (frows)
+                    for (int64_t i = tid; i < T_ * n_cat; i += kHsThreads) frows[i] = (T)0;
+                if (urow)
+                    for (int c = tid; c < n_cat; c += kHsThreads) urow[c] = 0.0;
+            }
             continue;
         }
         const double Zs = zs + Nprev;
@@ -378,10 +429,57 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
             ring[i] = neg_inf();
             if (counts) acc[i] = 0.0;
         }
+        // ---- the bins (ARCS) ----
+        const bool f_lds = ARCS && frows && arc.frame_lds;
+        const bool u_lds = ARCS && arc.utt_lds;
+        // where the utterance's sum is kept when not in LDS: its row of utt_out, else total_out
+        double* usum = urow ? urow : (ARCS ? arc.total_out : nullptr);
+        const int32_t* cat = nullptr;
+        const int32_t* icat = nullptr;
+        T* frow = frows;                                     // the row the folds go to
+        if constexpr (ARCS) {
+            cat = arc.map.arc_cat + arc.map.arc_off[gi];
+            icat = arc.map.init_cat + arc.map.state_off[gi];
+            if (frows && !f_lds)
+                for (int64_t i = tid; i < T_ * n_cat; i += kHsThreads) frows[i] = (T)0;
+            if (f_lds)
+                for (int c = tid; c < n_cat; c += kHsThreads) fbin[c] = 0.0;
+            if (u_lds) {
+                for (int c = tid; c < n_cat; c += kHsThreads) ubin[c] = 0.0;
+            } else if (urow) {
+                for (int c = tid; c < n_cat; c += kHsThreads) urow[c] = 0.0;
+            }
+            __threadfence();
+        }
+        // a posterior goes to the frame's bin and, unless the row's writer passes it on (flush),
+        // to the utterance's
+        auto fold = [&](int c, double p) {
+            if (c < 0 || !(p > 0.0)) return;
+            if (f_lds) {
+                hs_lds_add(fbin + c, p);
+                return;
+            }
+            if (frows) unsafeAtomicAdd(frow + c, (T)p);
+            if (u_lds) hs_lds_add(ubin + c, p);
+            else if (usum) unsafeAtomicAdd(usum + c, p);
+        };
+        // a row leaves the LDS bins: thread c mod 256 owns bin c of the row and of the sums
+        auto flush = [&]() {
+            if (!f_lds) return;
+            for (int c = tid; c < n_cat; c += kHsThreads) {
+                const double v = fbin[c];
+                frow[c] = (T)v;
+                fbin[c] = 0.0;
+                if (u_lds) ubin[c] += v;
+                else if (urow) urow[c] += v;
+                else if (usum && v != 0.0) unsafeAtomicAdd(usum + c, v);
+            }
+        };
         __syncthreads();
 
         // ------------------------------ backward ------------------------------
         double npn = 0.0, Np1 = 0.0, Np2 = 0.0;              // n'_{t+1}, N'_{t+1}, N'_{t+2}
+        if (ARCS && frows) frow = frows + (T_ - 1) * n_cat;  // iteration t folds into row t + 1
         for (int64_t t = T_ - 1; t >= 0; --t) {
             const double ct = cfr[t];
             const double Nt1 = t >= 1 ? ncum[t - 1] : 0.0, Nt2 = t >= 2 ? ncum[t - 2] : 0.0;
@@ -413,9 +511,19 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
                     bend = (double)fin[j];
                 } else {
                     double m = neg_inf(), s = 0.0;
+                    // (ARCS) what every arc of j shares in its posterior's exponent
+                    const double pre = ARCS ? (endT[t * S + j] + lv[j]) + kapE : 0.0;
                     for (int e = out_ptr[j]; e < out_ptr[j + 1]; ++e) {
                         const int k = out_dst[e];
-                        if (k != j) hs_add(m, s, r0[k] + (double)out_w[e]);
+                        if (k != j) {
+                            const double x = r0[k] + (double)out_w[e];
+                            hs_add(m, s, x);
+                            if (ARCS) {
+                                const int c = cat[e];
+                                const double px = x + pre;
+                                if (c >= 0 && px > neg_inf()) fold(c, exp(px));
+                            }
+                        }
                     }
                     const int hs = n_hubs > 0 ? L.hub_src_id[j] : -1;
                     if (hs >= 0 && hs < n_hubs) {
@@ -438,6 +546,11 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
                 r1[j] = bend;
             }
             __syncthreads();
+            // (ARCS) row t + 1 is complete; the next fold lies behind the barrier of phase B
+            if (ARCS && t < T_ - 1) {
+                flush();
+                if (frows) frow -= n_cat;
+            }
             // B: the ring, bbeg_t, the begin posterior B_t and the duration counts
             const int kn = (int)(t % D);
             for (int jb = 0; jb < S; jb += nteams) {
@@ -499,6 +612,28 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(beer_batch b,
             npn = nt;
         }
         __syncthreads();
+        if (ARCS) {
+            // row 0: B_0(j) = sum_d q(j,0,d), which the last iteration left in `bprev`, by init_cat
+            frow = frows;
+            for (int j = tid; j < S; j += kHsThreads) fold(icat[j], bprev[j]);
+            __syncthreads();
+            flush();
+            __syncthreads();
+            if (u_lds) {
+                for (int c = tid; c < n_cat; c += kHsThreads) {
+                    const double v = ubin[c];
+                    if (urow) urow[c] = v;
+                    if (arc.total_out && v != 0.0) unsafeAtomicAdd(arc.total_out + c, v);
+                }
+            } else if (urow && arc.total_out) {
+                // (the row took atomic adds: read it where they landed)
+                __threadfence();
+                for (int c = tid; c < n_cat; c += kHsThreads) {
+                    const double v = unsafeAtomicAdd(urow + c, 0.0);
+                    if (v != 0.0) unsafeAtomicAdd(arc.total_out + c, v);
+                }
+            }
+        }
         if (a.entry_sum)
             for (int j = tid; j < S; j += kHsThreads) atomicAdd(a.entry_sum + j, ent[j]);
         if (counts) {
@@ -539,10 +674,10 @@ inline bool hsmm_plan(int dtype, const beer_batch* b, int D, HsmmPlan* p) {
 template <typename T, bool VIT>
 int hsmm_launch(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
                 void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, VIT>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, VIT, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL((hsmm_kernel<T, VIT>), dim3(p.grid), dim3(kHsThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, a);
+    hipLaunchKernelGGL((hsmm_kernel<T, VIT, false>), dim3(p.grid), dim3(kHsThreads), p.lds,
+                       as_stream(stream), *b, (const T*)pc_llhs, a, HsNoArcs{});
     BEER_LAUNCH_CHECK();
     return BEER_OK;
 }
@@ -555,6 +690,39 @@ template <typename T>
 int hsmm_launch_vit(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
                     void* stream) {
     return hsmm_launch<T, true>(b, p, pc_llhs, a, stream);
+}
+
+// The form of beer_hsmm_arc_posteriors (beer_hsmm_arcs_route packs it): the plan above without
+// the low-degree images, and the bins behind the rows and the ring while they fit
+struct HsmmArcsPlan {
+    HsmmPlan base;
+    int frame_lds, utt_lds;
+    size_t bins_at;
+};
+inline bool hsmm_arcs_plan(int dtype, const beer_batch* b, int D, int n_cat, bool want_frames,
+                           HsmmArcsPlan* p) {
+    if (!hsmm_plan(dtype, b, D, &p->base) || n_cat < 1) return false;
+    p->base.lowdeg = 0;
+    const size_t bins = 8 * (size_t)n_cat;
+    size_t lds = p->base.lds;
+    p->bins_at = lds / 8;
+    p->frame_lds = want_frames && n_cat <= kHsFrameCats && lds + bins <= (size_t)kMaxDynLds;
+    if (p->frame_lds) lds += bins;
+    p->utt_lds = n_cat <= kHsUttCats && lds + bins <= (size_t)kMaxDynLds;
+    if (p->utt_lds) lds += bins;
+    p->base.lds = lds;
+    return true;
+}
+
+template <typename T>
+int hsmm_launch_arcs(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
+                     const HsArcArgs& arc, void* stream) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    hipLaunchKernelGGL((hsmm_kernel<T, false, true>), dim3(p.grid), dim3(kHsThreads), p.lds,
+                       as_stream(stream), *b, (const T*)pc_llhs, a, arc);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
 }
 
 HsArgs hsmm_args(const HsmmPlan& p, const double* log_dur, const double* leave_w, int D,
@@ -608,6 +776,51 @@ int beer_hsmm_viterbi(int dtype, const beer_batch* b, const void* pc_llhs, const
     a.score = score;
     a.map_pdf = map_pdf;
     BEER_DISPATCH(dtype, hsmm_launch_vit, b, p, pc_llhs, a, stream);
+}
+
+int beer_hsmm_arc_posteriors(int dtype, const beer_batch* b, const void* pc_llhs,
+                             const double* log_dur, const double* leave_w, int D, int S_total,
+                             const beer_arc_map* map, int n_cat, double* ws, void* gamma,
+                             double* utt_evidence, double* dur_counts, double* entry_sum,
+                             double* gamma0_sum, void* frame_out, double* utt_out,
+                             double* total_out, void* stream) {
+    HsmmArcsPlan p;
+    BEER_REQUIRE(hsmm_arcs_plan(dtype, b, D, n_cat, frame_out != nullptr, &p));
+    BEER_REQUIRE(S_total >= 1);
+    BEER_REQUIRE(frame_out || utt_out || total_out);
+    BEER_REQUIRE(map && map->arc_cat && map->init_cat && map->arc_off && map->state_off);
+    if (b->nutt == 0) return BEER_OK;
+    BEER_REQUIRE(pc_llhs && log_dur && ws && gamma);
+    HsArgs a = hsmm_args(p.base, log_dur, leave_w, D, S_total, ws);
+    a.gamma = gamma;
+    a.utt_evidence = utt_evidence;
+    a.dur_counts = dur_counts;
+    a.entry_sum = entry_sum;
+    a.gamma0_sum = gamma0_sum;
+    HsArcArgs arc = {};
+    arc.map = *map;
+    arc.n_cat = n_cat;
+    arc.frame_lds = p.frame_lds;
+    arc.utt_lds = p.utt_lds;
+    arc.bins_at = p.bins_at;
+    arc.frame_out = frame_out;
+    arc.utt_out = utt_out;
+    arc.total_out = total_out;
+    BEER_DISPATCH(dtype, hsmm_launch_arcs, b, p.base, pc_llhs, a, arc, stream);
+}
+
+size_t beer_hsmm_arcs_scratch_doubles(int dtype, const beer_batch* b, int D) {
+    HsmmPlan p;
+    if (!hsmm_plan(dtype, b, D, &p)) return 0;
+    return p.ring_total;
+}
+
+int beer_hsmm_arcs_route(int dtype, const beer_batch* b, int D, int n_cat, int want_frames) {
+    HsmmArcsPlan p;
+    BEER_REQUIRE(hsmm_arcs_plan(dtype, b, D, n_cat, want_frames != 0, &p));
+    return BEER_HSMM_BLOCK | (p.base.ring_lds ? BEER_HSMM_RING_LDS : 0) |
+           (p.frame_lds ? BEER_HSMM_ARCS_FRAME_LDS : 0) |
+           (p.utt_lds ? BEER_HSMM_ARCS_UTT_LDS : 0) | p.base.team_log2;
 }
 
 size_t beer_hsmm_scratch_doubles(int dtype, const beer_batch* b, int D) {

@@ -1183,7 +1183,9 @@ def duration_route(batch, D):
     return route
 
 
-def _duration_args(batch, pc_llhs, log_dur, leave_w):
+def _duration_args(batch, pc_llhs, log_dur, leave_w, scratch='beer_hsmm_scratch_doubles'):
+    '''(D, S_total, the two tables on the device, the workspace) of an explicit-duration call,
+    checked; `scratch` names the size query of the entry point the workspace is for.'''
     S_total = log_dur.shape[0] if torch.is_tensor(log_dur) and log_dur.dim() == 2 else 0
     D = check_durations(log_dur, S_total, leave_w)
     if len(batch._pdf_ids_h) and int(batch._pdf_ids_h.max()) >= S_total:
@@ -1193,7 +1195,7 @@ def _duration_args(batch, pc_llhs, log_dur, leave_w):
     duration_route(batch, D)
     log_dur = _hip.on_device(log_dur)
     leave_w = None if leave_w is None else _hip.on_device(leave_w)
-    extra = _hip.lib().beer_hsmm_scratch_doubles(_hip.dtype_code(batch.dtype), batch.ref(), D)
+    extra = getattr(_hip.lib(), scratch)(_hip.dtype_code(batch.dtype), batch.ref(), D)
     ws = torch.empty(max(2 * batch.n_elems + 2 * batch.n_frames + extra, 1), dtype=torch.float64,
                      device=batch.device)
     return D, S_total, log_dur, leave_w, ws
@@ -1220,6 +1222,71 @@ def duration_forward_backward(batch, pc_llhs, log_dur, leave_w=None, want_counts
               _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, _hip.ptr(ws), _hip.ptr(gamma),
               _hip.ptr(evidence), _hip.ptr(counts), _hip.ptr(entry), _hip.ptr(g0))
     return gamma, evidence, counts, entry, g0
+
+
+def duration_arcs_route(batch, D, n_cat, per_frame=True):
+    '''beer_hsmm_arcs_route: the form `duration_arc_posteriors` takes (team, ring and the two bin
+    bits `_hip.HSMM_ARCS_FRAME_LDS` / `_hip.HSMM_ARCS_UTT_LDS`); HipInvalid -- naming the limit --
+    where it refuses.'''
+    route = _hip.lib().beer_hsmm_arcs_route(_hip.dtype_code(batch.dtype), batch.ref(), int(D),
+                                            int(n_cat), 1 if per_frame else 0)
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'explicit durations: {n_cat} arc categories with D = {D} on graphs of up to '
+            f'{batch.struct.max_states} states: at least one category, at most '
+            f'{_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
+            f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)')
+    return route
+
+
+def duration_arc_posteriors(batch, pc_llhs, log_dur, leave_w, arc_cat, init_cat, n_cat,
+                            per_frame=True, per_utt=False, total=False, want_counts=True):
+    '''Forward-backward over (state, duration) that also folds the arc every segment is entered
+    by into categories (`beer_hsmm_arc_posteriors`): (gamma, evidence, dur_counts, entry_sum,
+    gamma0_sum) as `duration_forward_backward` gives them, then (frame_out [n_frames, n_cat] of
+    the batch's dtype, utt_out [nutt, n_cat] fp64, total_out [n_cat] fp64), each None unless
+    asked for.  Row t >= 1 of an utterance holds per category the posterior that a segment
+    begins at t entered by an arc of that category, row 0 the first segment's state by
+    `init_cat`: a row sums to the posterior that a segment begins there, not to 1.  Categories
+    as for `arc_posteriors` (the full out-CSR; self-loops count nothing).'''
+    if not (per_frame or per_utt or total):
+        raise ValueError('duration_arc_posteriors: none of per_frame, per_utt and total is '
+                         'asked for')
+    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat,
+                                       per_frame, per_utt or total)
+    n_cat = int(n_cat)
+    D, S_total, log_dur, leave_w, ws = _duration_args(batch, pc_llhs, log_dur, leave_w,
+                                                      'beer_hsmm_arcs_scratch_doubles')
+    duration_arcs_route(batch, D, n_cat, per_frame)
+    dt, dev = batch.dtype, batch.device
+    dcode = _hip.dtype_code(dt)
+    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+    if arcs.device.type != 'cuda':
+        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+    if inits.device.type != 'cuda':
+        host['inits'] = inits
+    up = _hip.upload(host, dev)
+    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
+                       up['state_off'].data_ptr())
+    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
+    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    counts = entry = g0 = None
+    if want_counts:
+        counts = torch.zeros(S_total, D, dtype=torch.float64, device=dev)
+        if batch.shared_graph:
+            entry = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+            g0 = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+    frame = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev) if per_frame else None
+    utt = torch.empty(batch.nutt, n_cat, dtype=torch.float64, device=dev) if per_utt else None
+    tot = torch.zeros(n_cat, dtype=torch.float64, device=dev) if total else None
+    _hip.call('beer_hsmm_arc_posteriors', dcode, batch.ref(), _hip.ptr(pc_llhs),
+              _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, ctypes.byref(amap), n_cat,
+              _hip.ptr(ws), _hip.ptr(gamma), _hip.ptr(evidence), _hip.ptr(counts),
+              _hip.ptr(entry), _hip.ptr(g0), _hip.ptr(frame), _hip.ptr(utt), _hip.ptr(tot))
+    return gamma, evidence, counts, entry, g0, frame, utt, tot
 
 
 def duration_viterbi(batch, pc_llhs, log_dur, leave_w=None, map_pdf=False):

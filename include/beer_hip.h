@@ -1677,6 +1677,69 @@ size_t beer_hsmm_scratch_doubles(int dtype, const beer_batch* batch_h, int D);
 #define BEER_HSMM_TEAM(route) (1 << ((route) & 0xF))
 int beer_hsmm_route(int dtype, const beer_batch* batch_h, int D);
 
+/* Arc posteriors by category under explicit durations: beer_hsmm_forward_backward -- the same
+ * inputs, the same outputs (all nullable but `gamma`), the same arithmetic -- which also folds
+ * WHICH ARC every segment was entered by into the caller's categories (beer_arc_map, as
+ * beer_hmm_arc_posteriors reads it: `arc_cat` over the full out-CSR, hub and bigram arcs
+ * explicit in it; entries in [0, n_cat) or -1, the caller answers for the range).  With the
+ * symbols above:
+ *   frame_out  nullable, [n_frames, n_cat] of dtype, written (=):
+ *                row frame_off[u], category c:  sum over the states j with init_cat[j] = c of
+ *                                               sum_d q(j,0,d)
+ *                row frame_off[u] + t, t = 1 .. T-1:  sum over the arcs e = (i -> j), i != j,
+ *                     with arc_cat[e] = c of exp(end_{t-1}(i) + w_ij + bbeg_t(j) - Z)
+ *   utt_out    nullable, [nutt, n_cat] fp64, written (=): the sum of the utterance's rows
+ *   total_out  nullable, [n_cat] fp64, accumulated (+=): the sum over the whole batch (what a
+ *              model with n_cat = P^2 bigram categories reads: utt_out would be nutt P^2)
+ * A row does NOT sum to 1: with no category -1 it sums to B_t = sum_j sum_d q(j,t,d), the
+ * posterior that a segment begins at frame t (1 at t = 0).  An arc with src == dst contributes
+ * nothing whatever category it carries.
+ * The kernel always walks the full CSR, in both directions (the low-degree image hides the arcs
+ * behind its hubs).  An arc's posterior is formed in the backward pass where bend_t(i) is: its
+ * exponent is (end_t(i) - O_t) + w_ik + (bbeg_{t+1}(k) - Q_{t+1}) + ((N_{t-1} + N'_{t+2}) - Z),
+ * the stored values and the exact offset that E_t(i) itself uses, so nothing cancels; one more
+ * fp64 exp per arc and frame.  The arc terms of a state sum to its end posterior E_t(i) up to
+ * rounding; neither is renormalised by the other.
+ * Bins.  With used = 8 (8 S + 32) bytes of rows, plus 16 S D of ring when BEER_HSMM_RING_LDS,
+ * S = max_states: a frame's bins are fp64 in LDS, summed with LDS atomic adds and written as a
+ * row once per frame, when frame_out is given, n_cat <= 1024 and used + 8 n_cat <= 160 KiB
+ * (BEER_HSMM_ARCS_FRAME_LDS); else the rows of frame_out are zeroed and take global atomic adds
+ * in the dtype.  The utterance's bins are fp64 in LDS when n_cat <= 4096 and they fit behind
+ * that: used [+ 8 n_cat] + 8 n_cat <= 160 KiB (BEER_HSMM_ARCS_UTT_LDS); else its row of utt_out
+ * (without utt_out: total_out itself) takes the adds.  The order of atomic adds is not fixed: the
+ * last bits of frame_out, utt_out and total_out may differ between runs.  gamma and the evidence
+ * are the same bits on every run, and the bits beer_hsmm_forward_backward gives on its full-CSR
+ * route.
+ * Edges.  An utterance with Z = -inf: its rows and its utt_out row are zeros, nothing is added
+ * to total_out, and the shared outputs are as beer_hsmm_forward_backward documents.  T = 1: the
+ * init row alone.  No frames: nothing written to frame_out, zeros to utt_out.  -inf inputs are
+ * legal; inputs without NaN give no NaN.
+ * `ws` as for beer_hsmm_forward_backward, with beer_hsmm_arcs_scratch_doubles for its rings.
+ * BEER_EINVAL (everything is checked before anything is launched): where
+ * beer_hsmm_forward_backward refuses; n_cat < 1; a NULL map or map member; frame_out, utt_out
+ * and total_out all NULL. */
+int beer_hsmm_arc_posteriors(int dtype, const beer_batch* batch_h, const void* pc_llhs,
+                             const double* log_dur, const double* leave_w, int D, int S_total,
+                             const beer_arc_map* map, int n_cat, double* ws, void* gamma,
+                             double* utt_evidence, double* dur_counts, double* entry_sum,
+                             double* gamma0_sum, void* frame_out, double* utt_out,
+                             double* total_out, void* stream);
+
+/* Doubles `ws` of beer_hsmm_arc_posteriors must hold besides the two trellises and the two
+ * values per frame: beer_hsmm_scratch_doubles' value (the bins never live in `ws`). */
+size_t beer_hsmm_arcs_scratch_doubles(int dtype, const beer_batch* batch_h, int D);
+
+/* The form beer_hsmm_arc_posteriors takes (host only, from the launcher's own plan;
+ * `want_frames` != 0: frame_out is given):
+ *   BEER_HSMM_BLOCK | BEER_HSMM_RING_LDS | BEER_HSMM_ARCS_FRAME_LDS | BEER_HSMM_ARCS_UTT_LDS |
+ *   LOG2TEAM
+ * team and ring as beer_hsmm_route has them, never BEER_HSMM_LOWDEG, the two bin bits as
+ * defined above.  BEER_EINVAL exactly where beer_hsmm_arc_posteriors refuses the batch, D and
+ * n_cat. */
+#define BEER_HSMM_ARCS_FRAME_LDS 0x400
+#define BEER_HSMM_ARCS_UTT_LDS 0x800
+int beer_hsmm_arcs_route(int dtype, const beer_batch* batch_h, int D, int n_cat, int want_frames);
+
 /* Scatter the (scaled) state posteriors back to pdf ids, repeated ids add
  * (DynamicallyOrderedModelSet.accumulate, beer/models/modelset.py:148-154,
  * with the scale of HMM.accumulate, hmm.py:95), and the per-frame expected

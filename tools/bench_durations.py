@@ -1,6 +1,8 @@
 '''Explicit state durations (`hk.duration_forward_backward`, `hk.duration_viterbi`) beside the HMM
-forward-backward (`hk.forward_backward`) on the same batch and per-state log-likelihoods, in one
-process, float32: BASELINE config 3's phone loop (40 units x 3 states = 120 states, the pivot
+forward-backward (`hk.forward_backward`) on the same batch and per-state log-likelihoods, and
+beside them the arc posteriors under durations (`hk.duration_arc_posteriors`: the unit-start
+categories with the per-frame rows, and the P^2 bigram categories with the batch total alone), in
+one process, float32: BASELINE config 3's phone loop (40 units x 3 states = 120 states, the pivot
 declared as a hub), about 1 M frames in 300-frame utterances, at D = 16, 32 and 64; then one
 `accumulate_elbo` iteration of that loop with and without durations.
 
@@ -24,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import beer_amd as beer  # noqa: E402
 from beer_amd import hmm_kernels as hk  # noqa: E402
 from beer_amd.cli import hmm as hmm_cmds  # noqa: E402
+from beer_amd.models.sequence import unit_start_categories  # noqa: E402
 from benchlib.timers import ClockProbe  # noqa: E402
 from tools.bench_arc_posteriors import N_PHONES, TOPO  # noqa: E402
 from tools.bench_sample_paths import event_ms  # noqa: E402
@@ -40,6 +43,21 @@ def loop_model(max_duration=0):
     graph, start, end = hmm_cmds.decode_graph(hmm_cmds.loop_graph(names), units)
     return hmm_cmds.phone_loop(graph, start, end, ems, 'dirichlet',
                                max_duration=max_duration).float().cuda()
+
+
+def bigram_categories(model):
+    '(arc_cat, init_cat): i P + j on the arcs end_i -> start_j of the loop, -1 elsewhere.'
+    graph = model.graph
+    src, dst = (np.asarray(a, dtype=np.int64) for a in graph.out_arcs())
+    ends, starts = list(model.end_pdf.values()), list(model.start_pdf.values())
+    P = len(starts)
+    end_of = np.full(graph.n_states, -1, dtype=np.int64)
+    end_of[ends] = np.arange(P)
+    start_of = np.full(graph.n_states, -1, dtype=np.int64)
+    start_of[starts] = np.arange(P)
+    cat = np.where((end_of[src] >= 0) & (start_of[dst] >= 0) & (src != dst),
+                   end_of[src] * P + start_of[dst], -1)
+    return cat.astype(np.int32), np.full(graph.n_states, -1, dtype=np.int32)
 
 
 def main():
@@ -88,6 +106,20 @@ def main():
                      lambda: hk.duration_forward_backward(batch, pc_llhs, log_dur, leave_w),
                      route, beside='hmm forward_backward')
         print(json.dumps({'D': D, 'fb_gigaterms_per_s': round(2 * terms / med / 1e6, 2)}), flush=True)
+        if hasattr(hk, 'duration_arc_posteriors'):
+            # (the categories are uploaded once: the calls below time the launch, not the copies)
+            P = len(model.start_pdf)
+            for what, (arcs, inits), n_cat, kw in (
+                    ('unit starts, frame_out', unit_start_categories(
+                        model.graph, model.start_pdf, model.end_pdf), P, dict(per_frame=True)),
+                    ('bigram, total_out', bigram_categories(model), P * P,
+                     dict(per_frame=False, total=True))):
+                arcs, inits = torch.from_numpy(arcs).cuda(), torch.from_numpy(inits).cuda()
+                report(f'duration_arc_posteriors D={D} ({what})',
+                       lambda: hk.duration_arc_posteriors(batch, pc_llhs, log_dur, leave_w, arcs,
+                                                          inits, n_cat, **kw),
+                       hex(hk.duration_arcs_route(batch, D, n_cat, kw['per_frame'])),
+                       beside=f'duration_forward_backward D={D}', n_cat=n_cat)
         med = report(f'duration_viterbi D={D}',
                      lambda: hk.duration_viterbi(batch, pc_llhs, log_dur, leave_w),
                      route, beside='hmm viterbi')
