@@ -43,6 +43,17 @@ constexpr int kAxMaxFramesDefault = 4096;   // BEER_OPT_AX_MAXFRAMES (estep_bf16
 // call and the launch.
 constexpr int kMaxDynLds = 160 * 1024;
 
+// A launch that may take the whole LDS: the attribute, the launch and the launch check.
+// BEER_OK or -(hipError_t).
+template <typename K, typename... Args>
+int launch_full_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    BEER_LAUNCH_CHECK();
+    return BEER_OK;
+}
+
 constexpr double kLog2Pi = 1.8378770664093453;
 constexpr double kLog2 = 0.6931471805599453;
 constexpr double kLogPi = 1.1447298858494002;
@@ -149,6 +160,13 @@ __device__ __forceinline__ T wave_sum(T v) {
 template <typename T>
 __device__ __forceinline__ T wave_max(T v) {
     return wave_detail::allreduce(v, [](T x, T y) { return y > x ? y : x; });
+}
+
+// A wave's LDS writes are visible to its later reads in program order; the compiler must keep
+// that order (no instruction is emitted for this).
+__device__ __forceinline__ void wave_order() {
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
 }
 
 // Block reductions through LDS scratch of >= blockDim/64 elements.  All

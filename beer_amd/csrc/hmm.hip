@@ -16,7 +16,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
@@ -845,18 +845,10 @@ __device__ __forceinline__ float wave_fmax(float v) {
     return __builtin_bit_cast(float, i);
 }
 
+// ex: hmm_block.h's LinExp (NaN -> 0: the kernel flags utterances with NaN log-likelihoods, see
+// `gave_up`)
 template <typename T> struct Lin;
-template <> struct Lin<float> {
-    // exp(d) in fp64 range, relative error ~1e-7; d = -inf -> 0 (and NaN -> 0: the
-    // kernel flags utterances with NaN log-likelihoods, see `gave_up`)
-    static __device__ __forceinline__ double ex(double d) {
-        const double y = d * 1.4426950408889634074;
-        // (-inf and anything below 2^-1100 alike: 0 after the ldexp)
-        const double yc = __builtin_fmax(y, -1100.0);
-        const double n = __builtin_rint(yc);
-        const double r = (double)__builtin_amdgcn_exp2f((float)(yc - n));
-        return __builtin_amdgcn_ldexp(r, (int)n);
-    }
+template <> struct Lin<float> : LinExp<float> {
     // sum over the wave of non-negative terms <= ~1
     static __device__ __forceinline__ double wsum(double v) {
         const float s = wave_sum_scalar((float)v);
@@ -867,14 +859,9 @@ template <> struct Lin<float> {
         return wave_sum(v);
     }
 };
-template <> struct Lin<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
+template <> struct Lin<double> : LinExp<double> {
     static __device__ __forceinline__ double wsum(double v) { return wave_sum(v); }
 };
-// biased exponent of a non-negative double (0: zero or denormal)
-__device__ __forceinline__ int expo_field(double v) {
-    return (int)((__builtin_bit_cast(unsigned long long, v) >> 52) & 0x7ffull);
-}
 
 // OUTM (fused form): how a frame's posteriors go back to pdf ids -- 0: plain stores (every pdf id
 // of the graph distinct); 1: global atomic adds into a zero-filled array (repeated ids: an alignment
@@ -992,7 +979,6 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
     }
     // The wave's LDS writes are visible to its later reads in program order; the
     // compiler must keep that order (no instruction is emitted for this).
-#define BEER_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
 
     const T* llh = FUSED ? pc + f0 * (int64_t)S_total : pc + b.llh_off[u];
     const int64_t ll_stride = FUSED ? S_total : S;
@@ -1132,7 +1118,7 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
 #pragma unroll
             for (int p = 0; p < SPL; ++p) ll_ring[k][p] = load_ll(1 + k < T_ ? 1 + k : T_ - 1, p);
     }
-    BEER_WAVE_ORDER();
+    wave_order();
     auto forward_step = [&](int64_t t, const T (&ll)[SPL], double mt, bool scale_now) {
         double hub = 0.0;
         if (has_hub) {
@@ -1156,7 +1142,7 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
             if constexpr (!FUSED) sh_sum += (double)sh;        // (the fused launch reports no log p(X))
         }
         if constexpr (!FUSED) m_sum += mt;
-        BEER_WAVE_ORDER();                                // every read of the column is done
+        wave_order();                                // every read of the column is done
         {
             const __amdgpu_buffer_rsrc_t ar = al_row(t);
 #pragma unroll
@@ -1165,7 +1151,7 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
                 store_f64(a[p], ar, vo_a[p]);
             }
         }
-        BEER_WAVE_ORDER();
+        wave_order();
     };
     for (int t0 = 1; t0 < T_; t0 += PF) {
         const double mt = frames_max(ll_ring, PF);        // (frames past the end: the last one again)
@@ -1254,13 +1240,13 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
         }
         if constexpr (FUSED && OUTM == 2) {
             // the row is complete: out it goes (all S_total entries, zeros included), and clear
-            BEER_WAVE_ORDER();
+            wave_order();
             for (int e = lane; e < S_total; e += 64) {
                 const T v = orow_lds[e];
                 orow_lds[e] = (T)0;
                 store_word(v, orow, e * (int)sizeof(T));
             }
-            BEER_WAVE_ORDER();
+            wave_order();
         }
         if (FUSED && frame_llh) {
             // the frame's expected log-likelihood sum_s gamma_ts l_ts (hmm.py:87) while both
@@ -1276,10 +1262,10 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
             for (int p = 0; p < SPL; ++p)
                 lb_own[p] = R::ex((double)lt_cur[p] - mt) * beta[p];     // for frame t - 1
         }
-        BEER_WAVE_ORDER();                                 // lb fully read
+        wave_order();                                 // lb fully read
 #pragma unroll
         for (int p = 0; p < SPL; ++p) lds(own[p] + NS * 8) = lb_own[p];
-        BEER_WAVE_ORDER();
+        wave_order();
     };
     auto load_back = [&](int64_t tq, A_t (&av)[SPL], T (&lv)[SPL], double& hv) {
         const int64_t tc = tq > 0 ? tq : 0;                // (clamped: loaded, never used)
@@ -1349,7 +1335,6 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
             backward_step(t, a_t, lt_cur, hf_cur, mt, (k % kWvRescale) == kWvRescale - 1);
         }
     }
-#undef BEER_WAVE_ORDER
     if (lane == 0) hubf[T_ - 1] = gave_up ? 1.0 : 0.0;     // (hub values: slots 0 .. T-2)
     if (gave_up) return;
     if (gamma0_sum) {
@@ -1406,7 +1391,8 @@ __global__ __launch_bounds__(64 * kWvWaves, (kWvOcc - (CNT ? 1 : 0)) * 4 / kWvWa
 //  * absent arcs, absent hub links and lanes without a state carry the weight -inf;
 //  * the forward values are kept in fp64 (their size grows with the utterance).
 // ---------------------------------------------------------------------------
-// arithmetic of a log-sum-exp relative to an approximate maximum
+// arithmetic of a log-sum-exp relative to an approximate maximum (hmm_block.h's LogRel is the
+// same rule on an exact fp64 maximum, for the other families' kernels)
 template <typename T> struct Rel;
 template <> struct Rel<float> {
     typedef float r_t;
@@ -1560,7 +1546,6 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
     };
     // The wave's LDS writes are visible to its later reads in program order; the
     // compiler must keep that order (no instruction is emitted for this).
-#define BEER_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
 
     const T* llh = FUSED ? pc + f0 * (int64_t)S_total : pc + b.llh_off[u];
     const int64_t ll_stride = FUSED ? S_total : S;
@@ -1589,7 +1574,7 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
         if (st[p]) alpha[a_off[p]] = a;
         ll_next[p] = load_ll(T_ > 1 ? 1 : 0, p);
     }
-    BEER_WAVE_ORDER();
+    wave_order();
     for (int64_t t = 1; t < T_; ++t) {
         T ll[SPL];
 #pragma unroll
@@ -1611,13 +1596,13 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
             for (int k = 0; k < DEG; ++k) v[k] = lds(isrc[p][k]) + (double)iw[p][k];
             a[p] = (double)ll[p] + lane_lse(v, hub + (double)hd_w[p]);
         }
-        BEER_WAVE_ORDER();                                // every read of the column is done
+        wave_order();                                // every read of the column is done
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
             lds(own[p]) = st[p] ? a[p] : NINF;
             if (st[p]) alpha[t * S + a_off[p]] = a[p];
         }
-        BEER_WAVE_ORDER();
+        wave_order();
     }
 
     if (__builtin_amdgcn_ballot_w64(bad) != 0) {
@@ -1726,13 +1711,13 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
             const T fsum = wave_sum(fval);
             if (lane == 0) frame_llh[f0 + t] = fsum;
         }
-        BEER_WAVE_ORDER();                                 // lb fully read
+        wave_order();                                 // lb fully read
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
             lb_own[p] = st[p] ? (double)lt_cur[p] + beta[p] : NINF;     // for frame t - 1
             lds(own[p] + NS * 8) = lb_own[p];
         }
-        BEER_WAVE_ORDER();
+        wave_order();
     };
     {
         const int64_t t = T_ - 1;
@@ -1775,7 +1760,6 @@ __global__ __launch_bounds__(64 * kWvWaves) void fb_wave_log_kernel(
         }
         finish_frame(t, a_cur, lt_cur, beta, vout, hf_cur, true, hub);
     }
-#undef BEER_WAVE_ORDER
     if (lognorm_mean && lane == 0) lognorm_mean[u] = (T)(ln_acc / (double)T_);
     if (FUSED && utt_llh) {
         llh_acc = wave_sum(llh_acc);

@@ -34,68 +34,15 @@
 // second atomic.  The order of the adds is not fixed: results can differ in the last bits
 // from run to run.
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
 namespace {
 
 constexpr int kArcThreads = 256;
-constexpr int kArcRed = 16;                      // doubles of block-reduction scratch
-constexpr size_t kArcArcBytes = 64 * 1024;       // arcs stay in LDS below this total
-constexpr size_t kArcBinRows = 96 * 1024;        // bins are kept in LDS beside rows up to this
 constexpr int kArcFrameCats = 1024;              // a frame's bins stay in LDS up to here ...
 constexpr int kArcUttCats = 4096;                // ... and the utterance's up to here
-
-template <typename T> struct ARel;
-template <> struct ARel<float> {
-    static __device__ __forceinline__ double ex(double d) {
-        return (double)__builtin_amdgcn_exp2f((float)d * 1.44269504088896340736f);
-    }
-    static __device__ __forceinline__ double lg(double s) {
-        return (double)(__builtin_amdgcn_logf((float)s) * 0.69314718055994530942f);
-    }
-};
-template <> struct ARel<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-    static __device__ __forceinline__ double lg(double s) { return log(s); }
-};
-
-__device__ __forceinline__ double amax(double a, double b) { return b > a ? b : a; }
-
-template <typename T>
-__device__ __forceinline__ void arc_lse_add(double& m, double& s, double v) {
-    if (v > m) {
-        s = s * ARel<T>::ex(m - v) + 1.0;          // (m = -inf: s = 0 stays 0 * 0)
-        m = v;
-    } else if (v > neg_inf()) {
-        s += ARel<T>::ex(v - m);
-    }
-}
-
-// ln sum_j exp(val(j)) over the states j = tid, tid + blockDim, ... < S (-inf: nothing finite),
-// the same value in every thread.  Two barriers; a caller puts one more between two calls.
-template <typename T, typename F>
-__device__ __forceinline__ double arc_block_lse(int S, F val, double* red) {
-    const int tid = threadIdx.x, nt_ = blockDim.x;
-    const int lane = tid & 63, w = tid >> 6, nw = (nt_ + 63) >> 6;
-    double lm = neg_inf();
-    for (int j = tid; j < S; j += nt_) lm = amax(lm, val(j));
-    lm = wave_max(lm);
-    if (lane == 0) red[w] = lm;
-    __syncthreads();
-    double m = red[0];
-    for (int i = 1; i < nw; ++i) m = amax(m, red[i]);
-    const double base = m > neg_inf() ? m : 0.0;
-    double ls = 0.0;
-    for (int j = tid; j < S; j += nt_) ls += ARel<T>::ex(val(j) - base);
-    ls = wave_sum(ls);
-    if (lane == 0) red[kArcRed / 2 + w] = ls;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[kArcRed / 2 + i];
-    return s > 0.0 ? base + ARel<T>::lg(s) : neg_inf();
-}
 
 struct ArcForm {
     int arcs_in_lds, frame_lds, utt_lds;
@@ -129,7 +76,7 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
     double* cur = reinterpret_cast<double*>(smem);
     double* nxt = cur + b.max_states;
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kArcRed);        // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_end = l_ptr + b.max_states + 1;                         // [A] the arc's other end
     int32_t* l_cat = l_end + b.max_arcs;                               // [A] (backward only)
     T* l_w = reinterpret_cast<T*>(l_cat + b.max_arcs + ((b.max_states + 1) & 1));      // [A]
@@ -152,7 +99,7 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
     bool dead = false;
     for (int64_t t = 0;; ++t) {
         // (first barrier inside: every thread is done reading `cur`, the arc lists are staged)
-        const double c = arc_block_lse<T>(S, [&](int j) { return nxt[j]; }, red);
+        const double c = block_lse<T>(S, [&](int j) { return nxt[j]; }, red);
         dead = !(c > neg_inf());
         if (dead) break;
         if (tid == 0) norm[t] = c;
@@ -166,13 +113,13 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
         for (int j = tid; j < S; j += nt_) {
             double m = neg_inf(), s = 0.0;
             for (int e = a_ptr[j]; e < a_ptr[j + 1]; ++e)
-                arc_lse_add<T>(m, s, cur[a_end[e]] + (double)a_w[e]);
-            nxt[j] = (double)llh[(t + 1) * S + j] + (s > 0.0 ? m + ARel<T>::lg(s) : neg_inf());
+                lse_add<T>(m, s, cur[a_end[e]] + (double)a_w[e]);
+            nxt[j] = (double)llh[(t + 1) * S + j] + lse_value<T>(m, s);
         }
     }
     double tail = neg_inf();
     if (!dead) {
-        tail = arc_block_lse<T>(S, [&](int j) { return cur[j] + (double)fin[j]; }, red);
+        tail = block_lse<T>(S, [&](int j) { return cur[j] + (double)fin[j]; }, red);
         dead = !(tail > neg_inf());
     }
     if (dead) {                                            // (the same in every thread)
@@ -247,7 +194,7 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
     double* dnxt = cur;                                    // gamma_{t-1}, then d_{t-1}
     if (T_ == 1) {
         // (every thread reads and writes its own states of `cur`)
-        for (int j = tid; j < S; j += nt_) dnxt[j] = ARel<T>::ex(cur[j] + (double)fin[j] - tail);
+        for (int j = tid; j < S; j += nt_) dnxt[j] = LogRel<T>::ex(cur[j] + (double)fin[j] - tail);
     } else {
         const double cT = norm[T_ - 1];
         for (int j = tid; j < S; j += nt_)
@@ -263,7 +210,7 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
             double gam = 0.0;
             if (a > neg_inf()) {
                 for (int e = a_ptr[i]; e < a_ptr[i + 1]; ++e) {
-                    const double p = ARel<T>::ex(a + (double)a_w[e] + dcur[a_end[e]]);
+                    const double p = LogRel<T>::ex(a + (double)a_w[e] + dcur[a_end[e]]);
                     gam += p;
                     fold(cat[e], p);
                 }
@@ -277,7 +224,7 @@ __global__ __launch_bounds__(kArcThreads) void arc_posteriors_kernel(
             const double cp = norm[t - 1];
             for (int i = tid; i < S; i += nt_) {
                 const double gam = dnxt[i];
-                const double bw = gam > 0.0 ? ARel<T>::lg(gam / G) - arow[i] : neg_inf();
+                const double bw = gam > 0.0 ? LogRel<T>::lg(gam / G) - arow[i] : neg_inf();
                 dnxt[i] = (double)llh[(t - 1) * S + i] + bw - cp;
             }
         }
@@ -305,21 +252,18 @@ struct ArcPlan {
 };
 inline bool arc_plan(int dtype, const beer_batch* b, int n_cat, bool want_frames, bool with_utt,
                      ArcPlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        n_cat < 1 || (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b) || n_cat < 1) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
-    const size_t rows = (2 * S + kArcRed) * 8;                // two fp64 rows and the scratch
+    const size_t rows = block_rows_bytes(S);
     if (rows > (size_t)kMaxDynLds) return false;
     // the out-CSR of the largest graph with its categories (the in-CSR is smaller)
-    const size_t arcs = (S + 2 + 2 * A) * 4 + (A + 1) * w;
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, true, true);
     const size_t bins = 8 * (size_t)n_cat;
     size_t lds = rows;
-    p->form.arcs_in_lds = rows + arcs <= kArcArcBytes;
+    p->form.arcs_in_lds = rows + arcs <= kBlockArcBytes;
     if (p->form.arcs_in_lds) lds += arcs;
     // (at most 64 + 8 + 32 KiB with the arcs, 96 + 8 + 32 KiB without: within a CU's LDS)
-    const bool room = rows <= kArcBinRows;
+    const bool room = rows <= kBlockBinRows;
     p->form.frame_lds = want_frames && room && n_cat <= kArcFrameCats;
     if (p->form.frame_lds) lds += bins;
     p->form.utt_lds = room && n_cat <= kArcUttCats;
@@ -332,13 +276,9 @@ template <typename T>
 int arc_launch(const beer_batch* b, const ArcPlan& p, const void* pc_llhs,
                const beer_arc_map* map, int n_cat, double* ws, void* frame_out, double* utt_out,
                void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(arc_posteriors_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(arc_posteriors_kernel<T>, dim3(b->nutt), dim3(kArcThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, ws, (T*)frame_out,
-                       utt_out, p.form);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(arc_posteriors_kernel<T>, dim3(b->nutt), dim3(kArcThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, ws, (T*)frame_out,
+                           utt_out, p.form);
 }
 
 }  // namespace

@@ -30,7 +30,7 @@
 // Reference restated: beer/graph.py:270-326, beer/models/hmm.py:73-95,
 // beer/models/phoneloop.py:104-191.
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
@@ -40,25 +40,6 @@ constexpr int kBgMaxPhones = 128;      // BEER_BIGRAM_MAX_PHONES
 constexpr int kBgMaxStates = 512;      // BEER_BIGRAM_MAX_STATES
 constexpr int kBgMaxWaves = 8;         // waves (utterances) per workgroup
 constexpr int kBgVec = kBgMaxPhones;   // doubles of one block vector per wave
-
-template <typename T> struct BgExp;
-template <> struct BgExp<float> {
-    // exp(d) for float models: 2^n 2^f, n = rint(d log2 e), f in [-1/2, 1/2] formed in fp64,
-    // 2^f by v_exp_f32 -- relative error ~1e-7 whatever |d|; -inf -> 0
-    static __device__ __forceinline__ double ex(double d) {
-        const double y = __builtin_fmax(d * 1.4426950408889634074, -1100.0);
-        const double n = __builtin_rint(y);
-        const double r = (double)__builtin_amdgcn_exp2f((float)(y - n));
-        return __builtin_amdgcn_ldexp(r, (int)n);
-    }
-};
-template <> struct BgExp<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-};
-
-__device__ __forceinline__ int bg_expo(double v) {
-    return (int)((__builtin_bit_cast(unsigned long long, v) >> 52) & 0x7ffull);
-}
 
 // W is kept in fp64 for float models too: a bigram prior with concentrations 1 / P
 // (mkphoneloopbigram's dirichlet2) puts every block entry near -P, below float's range
@@ -108,7 +89,7 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
     const int32_t* __restrict__ order, int S_total, const T* __restrict__ pc, T scale,
     double* __restrict__ alpha_ws, double* __restrict__ uv_ws, T* __restrict__ out,
     int atomic_out, double* __restrict__ utt_llh, int32_t* __restrict__ flags) {
-    typedef BgExp<T> R;
+    typedef LinExp<T> R;
     constexpr int NS = 64 * SPL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int P = g.n_phones, S = g.n_states, ldw = P + 1;
@@ -186,7 +167,6 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
         bsrc[c] = bq[c] ? g.src[q] : 0;
         bdst[c] = bq[c] ? g.dst[q] : 0;
     }
-#define BEER_WAVE_ORDER() do { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
     auto col = [&](const double* v, int s) -> double { return s >= 0 ? v[s] : 0.0; };
     auto slot_of = [&](const double* v, int q) -> double { return q >= 0 ? v[q] : 0.0; };
     // vout[q'] = sum_i vin[i] W[i, q']  (forward)  or  sum_j W[q', j] vin[j]  (backward)
@@ -210,7 +190,7 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
     auto rescale = [&](double (&v)[SPL]) {
         int e = 0;
 #pragma unroll
-        for (int p = 0; p < SPL; ++p) { const int ep = bg_expo(v[p]); e = ep > e ? ep : e; }
+        for (int p = 0; p < SPL; ++p) { const int ep = expo_field(v[p]); e = ep > e ? ep : e; }
         e = wave_max(e);
         gave_up |= e < 1023 - 800 || e >= 0x7ff;
         const int sh = (e > 0 && e < 0x7ff) ? 1022 - e : 0;
@@ -259,16 +239,16 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
             }
         }
     }
-    BEER_WAVE_ORDER();
+    wave_order();
     for (int t = 1; t < T_; ++t) {
         T l[SPL];
         const double mt = load_ll(t, l);
 #pragma unroll
         for (int c = 0; c < 2; ++c)
             if (bq[c]) vin[lane + 64 * c] = cur[bsrc[c]];
-        BEER_WAVE_ORDER();
+        wave_order();
         block_product(false);
-        BEER_WAVE_ORDER();
+        wave_order();
         double a[SPL];
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
             a[p] = st[p] ? R::ex((double)l[p] - mt) * pred : 0.0;
         }
         rescale(a);
-        BEER_WAVE_ORDER();                                // every read of the column is done
+        wave_order();                                // every read of the column is done
         double* at = alpha + (int64_t)t * S;
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
@@ -287,7 +267,7 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
                 at[lane + 64 * p] = a[p];
             }
         }
-        BEER_WAVE_ORDER();
+        wave_order();
     }
 
     // ---- backward + posteriors ----
@@ -308,9 +288,9 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
                     uv_v[(int64_t)t * P + lane + 64 * c] = v;
                 }
             }
-            BEER_WAVE_ORDER();
+            wave_order();
             block_product(true);
-            BEER_WAVE_ORDER();
+            wave_order();
 #pragma unroll
             for (int p = 0; p < SPL; ++p) {
                 double acc = slot_of(vout, ext[p]);
@@ -350,25 +330,24 @@ __global__ __launch_bounds__(64 * kBgMaxWaves) void fb_bigram_kernel(
         }
         if (inner) {
             // u_t = a_t(src) / n_t, through the (now free) forward column
-            BEER_WAVE_ORDER();
+            wave_order();
 #pragma unroll
             for (int p = 0; p < SPL; ++p)
                 if (st[p]) cur[lane + 64 * p] = a_cur[p] * inv;
-            BEER_WAVE_ORDER();
+            wave_order();
 #pragma unroll
             for (int c = 0; c < 2; ++c)
                 if (bq[c]) uv_u[(int64_t)t * P + lane + 64 * c] = cur[bsrc[c]];
         }
         if (t > 0) {
             rescale(beta);
-            BEER_WAVE_ORDER();                            // lb fully read
+            wave_order();                            // lb fully read
 #pragma unroll
             for (int p = 0; p < SPL; ++p)
                 if (st[p]) lb[lane + 64 * p] = R::ex((double)l[p] - mt) * beta[p];
-            BEER_WAVE_ORDER();
+            wave_order();
         }
     }
-#undef BEER_WAVE_ORDER
     llh_acc = wave_sum(llh_acc);
     if (lane == 0) {
         flags[u] = gave_up ? 1 : 0;
@@ -390,29 +369,22 @@ int bigram_launch(const beer_bigram* g, int32_t nutt, int64_t n_frames, const in
     const size_t lds = wbytes + (size_t)waves * per_wave;
     const dim3 grid((unsigned)((nutt + waves - 1) / waves)), block(64 * waves);
 #define BEER_BG(SPL_, DEG_)                                                                      \
-    do {                                                                                         \
-        auto k = fb_bigram_kernel<T, WT, SPL_, DEG_>;                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k),                              \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);       \
-        hipLaunchKernelGGL(k, grid, block, lds, s, *g, nutt, n_frames, frame_off, order, S_total,          \
-                           (const T*)pc_all, (T)scale, alpha_ws, uv_ws, (T*)out, atomic_out,     \
-                           utt_llh, flags);                                                      \
-    } while (0)
+    return launch_full_lds(fb_bigram_kernel<T, WT, SPL_, DEG_>, grid, block, lds, s, *g, nutt,   \
+                           n_frames, frame_off, order, S_total, (const T*)pc_all, (T)scale,      \
+                           alpha_ws, uv_ws, (T*)out, atomic_out, utt_llh, flags)
 #define BEER_BG_DEG(SPL_)                                                                        \
     do {                                                                                         \
         if (deg == 2) BEER_BG(SPL_, 2);                                                          \
-        else if (deg == 4) BEER_BG(SPL_, 4);                                                     \
-        else BEER_BG(SPL_, 8);                                                                   \
+        if (deg == 4) BEER_BG(SPL_, 4);                                                          \
+        BEER_BG(SPL_, 8);                                                                        \
     } while (0)
     if (spl == 1) BEER_BG_DEG(1);
-    else if (spl == 2) BEER_BG_DEG(2);
-    else if (spl == 4) BEER_BG_DEG(4);
-    else if (spl == 5) BEER_BG_DEG(5);
-    else BEER_BG_DEG(8);
+    if (spl == 2) BEER_BG_DEG(2);
+    if (spl == 4) BEER_BG_DEG(4);
+    if (spl == 5) BEER_BG_DEG(5);
+    BEER_BG_DEG(8);
 #undef BEER_BG_DEG
 #undef BEER_BG
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
 }
 
 // What both entry points ask of the descriptor

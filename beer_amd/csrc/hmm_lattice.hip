@@ -21,50 +21,22 @@
 // am_t over the arcs into j is mm_t(j) bit for bit.
 //
 // Bins.  Folding is by maximum, so its order does not matter and the outputs are the same bits
-// on every run.  A bin is the order-preserving integer key of its value (mm_key below) under an
-// integer atomic max: 64-bit keys in LDS while the bins fit (a frame's, the utterance's, or
-// both; the thread that writes bin c of a row also owns bin c of the utterance), else the
-// output rows themselves hold keys of their own dtype, take global integer atomic max and are
-// decoded in place at the end -- the rows of an utterance belong to its workgroup alone.
+// on every run.  A bin is the order-preserving integer key of its value (hmm_block.h:
+// OrderedKey) under an integer atomic max: 64-bit keys in LDS while the bins fit (a frame's,
+// the utterance's, or both; the thread that writes bin c of a row also owns bin c of the
+// utterance), else the output rows themselves hold keys of their own dtype, take global integer
+// atomic max and are decoded in place at the end -- the rows of an utterance belong to its
+// workgroup alone.
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
 namespace {
 
 constexpr int kMmThreads = 256;
-constexpr int kMmRed = 16;                       // doubles of block-reduction scratch
-constexpr size_t kMmArcBytes = 64 * 1024;        // arcs stay in LDS below this total
-constexpr size_t kMmBinRows = 96 * 1024;         // bins are kept in LDS beside rows up to this
-constexpr int kMmBinCats = 2048;                 // ... and up to this many categories
+constexpr int kMmBinCats = 2048;                 // the bins stay in LDS up to this many categories
 constexpr int kMmTurn = 8;                       // out-rows from here on start at their own arc
-
-__device__ __forceinline__ double mmax(double a, double b) { return b > a ? b : a; }
-
-// Order-preserving keys: a < b as numbers exactly when key(a) < key(b) as signed integers
-// (-inf is the smallest key in use; NaN is outside the contract).
-template <typename V> struct MmKey;
-template <> struct MmKey<double> {
-    using K = long long;
-    static __device__ __forceinline__ K key(double v) {
-        const K b = __builtin_bit_cast(K, v);
-        return b >= 0 ? b : (b ^ 0x7fffffffffffffffLL);
-    }
-    static __device__ __forceinline__ double val(K k) {
-        return __builtin_bit_cast(double, k >= 0 ? k : (k ^ 0x7fffffffffffffffLL));
-    }
-};
-template <> struct MmKey<float> {
-    using K = int;
-    static __device__ __forceinline__ K key(float v) {
-        const K b = __builtin_bit_cast(K, v);
-        return b >= 0 ? b : (b ^ 0x7fffffff);
-    }
-    static __device__ __forceinline__ float val(K k) {
-        return __builtin_bit_cast(float, k >= 0 ? k : (k ^ 0x7fffffff));
-    }
-};
 
 struct MmForm {
     int arcs_in_lds, bins_lds;
@@ -76,8 +48,8 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
     double* __restrict__ ws, T* __restrict__ state_out, T* __restrict__ frame_out,
     double* __restrict__ utt_out, double* __restrict__ best_out, MmForm form) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using DK = MmKey<double>;
-    using TK = MmKey<T>;
+    using DK = OrderedKey<double>;
+    using TK = OrderedKey<T>;
     const int tid = threadIdx.x, nt_ = blockDim.x;
     const int u = b.order ? b.order[blockIdx.x] : (int)blockIdx.x;
     const int gid = b.graph_id[u];
@@ -102,7 +74,7 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
     double* cur = reinterpret_cast<double*>(smem);
     double* nxt = cur + b.max_states;
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kMmRed);         // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_end = l_ptr + b.max_states + 1;                         // [A] the arc's other end
     int32_t* l_cat = l_end + b.max_arcs;                               // [A] (with categories)
     const int n_int = b.max_states + 1 + (cats ? 2 : 1) * b.max_arcs;
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
         for (int j = tid; j < S; j += nt_) {
             double m = neg_inf();
             for (int e = a_ptr[j]; e < a_ptr[j + 1]; ++e)
-                m = mmax(m, cur[a_end[e]] + (double)a_w[e]);
+                m = dmax(m, cur[a_end[e]] + (double)a_w[e]);
             const double d = m + (double)llh[t * S + j];
             nxt[j] = d;
             dtr[t * S + j] = d;
@@ -141,7 +113,7 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
         double* sw = cur; cur = nxt; nxt = sw;
     }
     double part = neg_inf();
-    for (int j = tid; j < S; j += nt_) part = mmax(part, cur[j] + (double)fin[j]);
+    for (int j = tid; j < S; j += nt_) part = dmax(part, cur[j] + (double)fin[j]);
     const double best = block_max(part, red);              // (the same in every thread)
     if (tid == 0) best_out[u] = best;
     if (!(best > neg_inf())) {
@@ -240,7 +212,7 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
                 for (int k = e0; k < e1; ++k) {
                     const int j = a_end[e];
                     const double w = (double)a_w[e], l = lrow[j], ev = erow[j];
-                    m = mmax(m, w + (l + ev));
+                    m = dmax(m, w + (l + ev));
                     fold(cat[e], (((d + w) + l) + ev) - best);
                     if (++e == e1) e = e0;
                 }
@@ -248,7 +220,7 @@ __global__ __launch_bounds__(kMmThreads) void max_marginals_kernel(
                 for (int e = e0; e < e1; ++e) {
                     const int j = a_end[e];
                     const double w = (double)a_w[e], l = lrow[j], ev = erow[j];
-                    m = mmax(m, w + (l + ev));
+                    m = dmax(m, w + (l + ev));
                     if (cats) fold(cat[e], (((d + w) + l) + ev) - best);
                 }
             }
@@ -300,24 +272,21 @@ struct MmPlan {
 };
 inline bool mm_plan(int dtype, const beer_batch* b, int n_cat, bool want_state, bool want_frames,
                     bool want_utt, MmPlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b)) return false;
     if (!(want_state || want_frames || want_utt)) return false;
     const bool cats = want_frames || want_utt;
     if (cats && n_cat < 1) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
-    const size_t rows = (2 * S + kMmRed) * 8;                 // two fp64 rows and the scratch
+    const size_t rows = block_rows_bytes(S);
     if (rows > (size_t)kMaxDynLds) return false;
     // the out-CSR of the largest graph, with its categories when they are read (the in-CSR is
     // smaller)
-    const size_t arcs = (S + 2 + (cats ? 2 : 1) * A) * 4 + (A + 1) * w;
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, cats, true);
     size_t lds = rows;
-    p->form.arcs_in_lds = rows + arcs <= kMmArcBytes;
+    p->form.arcs_in_lds = rows + arcs <= kBlockArcBytes;
     if (p->form.arcs_in_lds) lds += arcs;
     // (at most 64 + 32 KiB with the arcs, 96 + 32 KiB without: within a CU's LDS)
-    p->form.bins_lds = cats && rows <= kMmBinRows && n_cat <= kMmBinCats;
+    p->form.bins_lds = cats && rows <= kBlockBinRows && n_cat <= kMmBinCats;
     if (p->form.bins_lds) lds += 8 * (size_t)n_cat * ((want_frames ? 1 : 0) + (want_utt ? 1 : 0));
     p->lds = lds;
     return true;
@@ -327,14 +296,10 @@ template <typename T>
 int mm_launch(const beer_batch* b, const MmPlan& p, const void* pc_llhs, const beer_arc_map* map,
               int n_cat, double* ws, void* state_out, void* frame_out, double* utt_out,
               double* best, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(max_marginals_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     const beer_arc_map none = {nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(max_marginals_kernel<T>, dim3(b->nutt), dim3(kMmThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, map ? *map : none, n_cat, ws,
-                       (T*)state_out, (T*)frame_out, utt_out, best, p.form);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(max_marginals_kernel<T>, dim3(b->nutt), dim3(kMmThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, map ? *map : none, n_cat, ws,
+                           (T*)state_out, (T*)frame_out, utt_out, best, p.form);
 }
 
 }  // namespace

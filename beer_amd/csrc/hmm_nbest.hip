@@ -25,15 +25,14 @@
 
 #include <math.h>
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
 namespace {
 
 constexpr int kNbThreads = 256;                   // at most; a multiple of 64 that covers S below it
-constexpr size_t kNbChunkBytes = 16 * 1024;       // the staged back-pointers stay below this ...
-constexpr size_t kNbArcBytes = 64 * 1024;         // ... and the arcs are in LDS below this total
+constexpr size_t kNbChunkBytes = 16 * 1024;       // the staged back-pointers stay below this
 constexpr int kNbSel = 16;                        // int32: where the k walks stand
 static_assert(kNbSel >= BEER_NBEST_MAX, "a slot per path");
 static_assert(BEER_NBEST_MAX <= 16, "the rank takes four bits of a back-pointer");
@@ -207,9 +206,7 @@ struct NbestPlan {
     size_t lds;              // dynamic LDS of the launch
 };
 inline bool nbest_plan(int dtype, const beer_batch* b, int32_t k, NbestPlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        (dtype != BEER_F32 && dtype != BEER_F64) || k < 1 || k > BEER_NBEST_MAX)
-        return false;
+    if (!block_batch_ok(dtype, b) || k < 1 || k > BEER_NBEST_MAX) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
     const size_t w = dtype == BEER_F32 ? 4 : 8;
     const size_t cols = 2 * S * k * w;                        // two score columns [k][S]
@@ -217,8 +214,8 @@ inline bool nbest_plan(int dtype, const beer_batch* b, int32_t k, NbestPlan* p) 
     p->chunk = 32 * row <= kNbChunkBytes ? 32 : (8 * row <= kNbChunkBytes ? 8 : 2);
     const size_t base = cols + 4 * kNbSel + p->chunk * row;
     if (base > (size_t)kMaxDynLds) return false;
-    const size_t arcs = (S + 2 + A) * 4 + A * w;
-    p->arcs_in_lds = base + arcs <= kNbArcBytes;
+    const size_t arcs = csr_bytes(S, A, w, false, false);
+    p->arcs_in_lds = base + arcs <= kBlockArcBytes;
     p->lds = base + (p->arcs_in_lds ? arcs : 0);
     p->K = BEER_NBEST_LIST(k);
     const size_t t64 = (S + 63) / 64 * 64;
@@ -229,13 +226,9 @@ inline bool nbest_plan(int dtype, const beer_batch* b, int32_t k, NbestPlan* p) 
 template <typename T, int K, bool ARCS_LDS>
 int nbest_launch_form(const beer_batch* b, const NbestPlan& p, const void* pc_llhs, int32_t k,
                       int32_t* bt_ws, int64_t* paths, double* scores, int map_pdf, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nbest_kernel<T, K, ARCS_LDS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL((nbest_kernel<T, K, ARCS_LDS>), dim3(b->nutt), dim3(p.threads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, (int)k, p.chunk, bt_ws, paths,
-                       scores, map_pdf);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(nbest_kernel<T, K, ARCS_LDS>, dim3(b->nutt), dim3(p.threads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, (int)k, p.chunk, bt_ws, paths,
+                           scores, map_pdf);
 }
 
 template <typename T, int K>

@@ -20,7 +20,7 @@
 // (and state 0 where a row has no arc) -- Viterbi's "all -inf -> 0".  Weights are formed
 // relative to the row's largest term, which leaves the ratios as they are.
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
@@ -29,52 +29,12 @@ namespace {
 constexpr int kSmpQuadThreads = 512;     // forward pass: four lanes per state ...
 constexpr int kSmpThreads = 256;         // ... or one thread per state (strided beyond)
 constexpr int kSmpWaves = 4;             // draw: samples of one utterance per workgroup
-constexpr int kSmpRed = 16;              // doubles of block-reduction scratch: 8 waves, twice
-static_assert(kSmpQuadThreads / 64 <= kSmpRed / 2, "a slot per wave in either half");
+static_assert(kSmpQuadThreads / 64 <= kBlockRed / 2, "a slot per wave in either half");
 constexpr size_t kSmpChunkBytes = 32 * 1024;   // what a chunk of trellis rows may take
-constexpr size_t kSmpArcBytes = 64 * 1024;     // arcs stay in LDS below this total
-
-// exp / log of a log-sum-exp relative to its maximum, in the model's precision (hmm.hip:
-// Rel<T>::ex / lg); differences, sums and the trellis stay fp64
-template <typename T> struct SRel;
-template <> struct SRel<float> {
-    static __device__ __forceinline__ double ex(double d) {
-        return (double)__builtin_amdgcn_exp2f((float)d * 1.44269504088896340736f);
-    }
-    static __device__ __forceinline__ double lg(double s) {
-        return (double)(__builtin_amdgcn_logf((float)s) * 0.69314718055994530942f);
-    }
-};
-template <> struct SRel<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-    static __device__ __forceinline__ double lg(double s) { return log(s); }
-};
-
-__device__ __forceinline__ double dmax(double a, double b) { return b > a ? b : a; }
 
 // ---------------------------------------------------------------------------
 // forward pass
 // ---------------------------------------------------------------------------
-// A log-sum-exp as the pair (m, s): sum = s * exp(m), m the largest term so far (-inf and 0:
-// no finite term yet).  One walk over an arc list instead of two (maximum, then sum): the walk
-// is a chain of dependent LDS reads and sets the time of a frame.
-template <typename T>
-__device__ __forceinline__ void lse_add(double& m, double& s, double v) {
-    if (v > m) {
-        s = s * SRel<T>::ex(m - v) + 1.0;          // (m = -inf: s = 0 stays 0 * 0)
-        m = v;
-    } else if (v > neg_inf()) {
-        s += SRel<T>::ex(v - m);
-    }
-}
-// ... and of two such pairs
-template <typename T>
-__device__ __forceinline__ void lse_join(double& m, double& s, double om, double os) {
-    const double M = dmax(m, om);
-    if (M > neg_inf())
-        s = (s > 0.0 ? s * SRel<T>::ex(m - M) : 0.0) + (os > 0.0 ? os * SRel<T>::ex(om - M) : 0.0);
-    m = M;
-}
 // nxt -> normalised -> cur and the trellis row `row`
 template <typename T>
 __device__ __forceinline__ void smp_normalise(int S, const double* nxt, double* cur, double* red,
@@ -82,6 +42,7 @@ __device__ __forceinline__ void smp_normalise(int S, const double* nxt, double* 
     const int tid = threadIdx.x, nt_ = blockDim.x;
     const int lane = tid & 63, w = tid >> 6, nw = (nt_ + 63) >> 6;
     __syncthreads();                                   // nxt written, cur read by everyone
+    // block_lse's body, kept here: with lz taken from block_lse's value the kernel's code changes.
     // (maxima in red[0 .. 7], sums in red[8 .. 15]: a barrier each, and two more between a
     //  frame's reads and the next frame's writes of either half)
     double lm = neg_inf();
@@ -93,13 +54,13 @@ __device__ __forceinline__ void smp_normalise(int S, const double* nxt, double* 
     for (int i = 1; i < nw; ++i) m = dmax(m, red[i]);
     const double base = m > neg_inf() ? m : 0.0;
     double ls = 0.0;
-    for (int j = tid; j < S; j += nt_) ls += SRel<T>::ex(nxt[j] - base);
+    for (int j = tid; j < S; j += nt_) ls += LogRel<T>::ex(nxt[j] - base);
     ls = wave_sum(ls);
-    if (lane == 0) red[kSmpRed / 2 + w] = ls;
+    if (lane == 0) red[kBlockRed / 2 + w] = ls;
     __syncthreads();
     double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[kSmpRed / 2 + i];
-    const double lz = s > 0.0 ? base + SRel<T>::lg(s) : 0.0;   // nothing reachable: all stay -inf
+    for (int i = 0; i < nw; ++i) s += red[kBlockRed / 2 + i];
+    const double lz = s > 0.0 ? base + LogRel<T>::lg(s) : 0.0;   // nothing reachable: all stay -inf
     for (int j = tid; j < S; j += nt_) {
         const double a = nxt[j] - lz;
         cur[j] = a;
@@ -123,7 +84,7 @@ __global__ __launch_bounds__(kSmpQuadThreads) void sample_forward_kernel(
     double* cur = reinterpret_cast<double*>(smem);
     double* nxt = cur + b.max_states;
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kSmpRed);        // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_src = l_ptr + b.max_states + 1;                         // [A]
     T* l_w = reinterpret_cast<T*>(l_src + b.max_arcs + ((b.max_states + 1 + b.max_arcs) & 1));
     const int32_t* in_ptr = g.in_ptr;
@@ -154,14 +115,14 @@ __global__ __launch_bounds__(kSmpQuadThreads) void sample_forward_kernel(
             for (int e = e0; e < e1; e += 4) lse_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
             lse_join<T>(m, s, wave_detail::dpp<double, 0xB1>(m), wave_detail::dpp<double, 0xB1>(s));
             lse_join<T>(m, s, wave_detail::dpp<double, 0x4E>(m), wave_detail::dpp<double, 0x4E>(s));
-            if (pj >= 0) nxt[qj] = (double)ll_cur + (s > 0.0 ? m + SRel<T>::lg(s) : neg_inf());
+            if (pj >= 0) nxt[qj] = (double)ll_cur + lse_value<T>(m, s);
         } else {
             for (int j = tid; j < S; j += nt_) {
                 double m = neg_inf(), s = 0.0;
                 for (int e = in_ptr[j]; e < in_ptr[j + 1]; ++e)
                     lse_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
                 const double ll = one ? (double)ll_cur : (double)llh[t * S + j];
-                nxt[j] = ll + (s > 0.0 ? m + SRel<T>::lg(s) : neg_inf());
+                nxt[j] = ll + lse_value<T>(m, s);
             }
         }
         smp_normalise<T>(S, nxt, cur, red, alpha + t * S);
@@ -199,7 +160,7 @@ __device__ __forceinline__ int smp_pick(int n, F term, double uu, int lane) {
         double tot = 0.0;
 #pragma unroll
         for (int i = 0; i < BEER_SEG; ++i) {
-            v[i] = SRel<T>::ex(v[i] - m);
+            v[i] = LogRel<T>::ex(v[i] - m);
             tot += v[i];
         }
         if (!(tot > 0.0) || !(tot < __builtin_huge_val())) return 0;
@@ -226,7 +187,7 @@ __device__ __forceinline__ int smp_pick(int n, F term, double uu, int lane) {
     double tot = 0.0;
     for (int base = 0; base < n; base += 64) {
         const int i = base + lane;
-        if (i < n) tot += SRel<T>::ex(term(i) - m);
+        if (i < n) tot += LogRel<T>::ex(term(i) - m);
     }
     tot = wave_sum(tot);
     if (!(tot > 0.0) || !(tot < __builtin_huge_val())) return 0;
@@ -235,7 +196,7 @@ __device__ __forceinline__ int smp_pick(int n, F term, double uu, int lane) {
     int last = 0;
     for (int base = 0; base < n; base += 64) {
         const int i = base + lane;
-        const double x = i < n ? SRel<T>::ex(term(i) - m) : 0.0;
+        const double x = i < n ? LogRel<T>::ex(term(i) - m) : 0.0;
         const double incl = carry + wave_incl_scan(x, lane);
         const unsigned long long nz = __builtin_amdgcn_ballot_w64(x > 0.0);
         const unsigned long long hit = __builtin_amdgcn_ballot_w64(x > 0.0 && incl > target);
@@ -314,18 +275,15 @@ struct SamplePlan {
     size_t fwd_lds, draw_lds;
 };
 inline bool sample_plan(int dtype, const beer_batch* b, int32_t nsamples, SamplePlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        nsamples < 1 || (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b) || nsamples < 1) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
     const size_t row = 8 * S + 8 * kSmpWaves;                 // a trellis row and its uniforms
     p->chunk = 32 * row <= kSmpChunkBytes ? 32 : (8 * row <= kSmpChunkBytes ? 8 : 2);
-    const size_t fwd = (2 * S + kSmpRed) * 8, draw = p->chunk * row;
-    const size_t arcs = (S + 2 + A) * 4 + A * w;
+    const size_t fwd = block_rows_bytes(S), draw = p->chunk * row;
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, false, false);
     const size_t base = fwd > draw ? fwd : draw;
     if (base > (size_t)kMaxDynLds) return false;
-    p->arcs_in_lds = base + arcs <= kSmpArcBytes;
+    p->arcs_in_lds = base + arcs <= kBlockArcBytes;
     p->quad = 4 * S <= (size_t)kSmpQuadThreads;
     p->waves = nsamples == 1 ? 1 : kSmpWaves;
     if ((nsamples + p->waves - 1) / p->waves > 65535) return false;
@@ -338,20 +296,15 @@ template <typename T>
 int sample_launch(const beer_batch* b, const SamplePlan& p, const void* pc_llhs,
                   const double* uniforms, int32_t nsamples, double* alpha_ws, int64_t* path,
                   int map_pdf, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sample_forward_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(sample_forward_kernel<T>, dim3(b->nutt),
-                       dim3(p.quad ? kSmpQuadThreads : kSmpThreads), p.fwd_lds, as_stream(stream),
-                       *b, (const T*)pc_llhs, alpha_ws, p.arcs_in_lds);
-    BEER_LAUNCH_CHECK();
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sample_draw_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(sample_draw_kernel<T>,
-                       dim3(b->nutt, (unsigned)((nsamples + p.waves - 1) / p.waves)),
-                       dim3(64 * p.waves), p.draw_lds, as_stream(stream), *b, alpha_ws, uniforms,
-                       nsamples, path, map_pdf, p.arcs_in_lds, p.chunk);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    const int rc = launch_full_lds(sample_forward_kernel<T>, dim3(b->nutt),
+                                   dim3(p.quad ? kSmpQuadThreads : kSmpThreads), p.fwd_lds,
+                                   as_stream(stream), *b, (const T*)pc_llhs, alpha_ws,
+                                   p.arcs_in_lds);
+    if (rc != BEER_OK) return rc;
+    return launch_full_lds(sample_draw_kernel<T>,
+                           dim3(b->nutt, (unsigned)((nsamples + p.waves - 1) / p.waves)),
+                           dim3(64 * p.waves), p.draw_lds, as_stream(stream), *b, alpha_ws,
+                           uniforms, nsamples, path, map_pdf, p.arcs_in_lds, p.chunk);
 }
 
 }  // namespace

@@ -35,7 +35,7 @@
 
 #include <limits>
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
@@ -46,57 +46,7 @@ constexpr int kEvWaveStates = 256;       // ... up to four states a lane
 constexpr size_t kEvWaveBytes = 16 * 1024;        // ... and this much LDS per wave
 constexpr int kEvQuadThreads = 512;      // workgroup form: four lanes per state ...
 constexpr int kEvThreads = 256;          // ... or one thread per state (strided beyond)
-constexpr int kEvRed = 16;               // doubles of block-reduction scratch: 8 waves, twice
-static_assert(kEvQuadThreads / 64 <= kEvRed / 2, "a slot per wave in either half");
-constexpr size_t kEvArcBytes = 64 * 1024;         // workgroup form: arcs stay in LDS below this total
-
-// exp / log of a log-sum-exp relative to its maximum, in the model's precision (hmm.hip:
-// Rel<T>::ex / lg); differences and sums stay fp64
-template <typename T> struct ERel;
-template <> struct ERel<float> {
-    static __device__ __forceinline__ double ex(double d) {
-        return (double)__builtin_amdgcn_exp2f((float)d * 1.44269504088896340736f);
-    }
-    static __device__ __forceinline__ double lg(double s) {
-        return (double)(__builtin_amdgcn_logf((float)s) * 0.69314718055994530942f);
-    }
-};
-template <> struct ERel<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-    static __device__ __forceinline__ double lg(double s) { return log(s); }
-};
-
-__device__ __forceinline__ double emax(double a, double b) { return b > a ? b : a; }
-
-// A log-sum-exp as the pair (m, s): sum = s * exp(m), m the largest term so far (-inf and 0:
-// no finite term yet) -- one walk over an arc list instead of two
-template <typename T>
-__device__ __forceinline__ void ev_add(double& m, double& s, double v) {
-    if (v > m) {
-        s = s * ERel<T>::ex(m - v) + 1.0;          // (m = -inf: s = 0 stays 0 * 0)
-        m = v;
-    } else if (v > neg_inf()) {
-        s += ERel<T>::ex(v - m);
-    }
-}
-template <typename T>
-__device__ __forceinline__ void ev_join(double& m, double& s, double om, double os) {
-    const double M = emax(m, om);
-    if (M > neg_inf())
-        s = (s > 0.0 ? s * ERel<T>::ex(m - M) : 0.0) + (os > 0.0 ? os * ERel<T>::ex(om - M) : 0.0);
-    m = M;
-}
-template <typename T>
-__device__ __forceinline__ double ev_value(double m, double s) {
-    return s > 0.0 ? m + ERel<T>::lg(s) : neg_inf();
-}
-
-// The wave's LDS writes are visible to its later reads in program order; the compiler must
-// keep that order (no instruction is emitted for this).
-__device__ __forceinline__ void ev_wave_order() {
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
+static_assert(kEvQuadThreads / 64 <= kBlockRed / 2, "a slot per wave in either half");
 
 // ---------------------------------------------------------------------------
 // one wave per utterance
@@ -106,31 +56,16 @@ template <typename T, int SPL>
 __device__ __forceinline__ double ev_wave_lse(const double (&v)[SPL]) {
     double m = v[0];
 #pragma unroll
-    for (int p = 1; p < SPL; ++p) m = emax(m, v[p]);
+    for (int p = 1; p < SPL; ++p) m = dmax(m, v[p]);
     m = wave_max(m);
     const double base = m > neg_inf() ? m : 0.0;
     double s = 0.0;
 #pragma unroll
-    for (int p = 0; p < SPL; ++p) s += ERel<T>::ex(v[p] - base);
+    for (int p = 0; p < SPL; ++p) s += LogRel<T>::ex(v[p] - base);
     s = wave_sum(s);
-    return s > 0.0 ? base + ERel<T>::lg(s) : neg_inf();
+    return lse_value<T>(base, s);
 }
 
-// exp(d) over fp64's range with the mantissa in the model's precision (hmm.hip: Lin<T>::ex):
-// d = -inf and anything below 2^-1100 give 0
-template <typename T> struct ELin;
-template <> struct ELin<float> {
-    static __device__ __forceinline__ double ex(double d) {
-        const double y = d * 1.4426950408889634074;
-        const double yc = __builtin_fmax(y, -1100.0);
-        const double n = __builtin_rint(yc);
-        const double r = (double)__builtin_amdgcn_exp2f((float)(yc - n));
-        return __builtin_amdgcn_ldexp(r, (int)n);
-    }
-};
-template <> struct ELin<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-};
 // a frame's normaliser below this has left the range in which the scaled recursion is exact
 constexpr double kEvMinNorm = 0x1p-800;
 
@@ -180,13 +115,13 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
     bool lost = false;
     for (int e = lane; e < A; e += 64) {
         const T w = in_w[e];
-        const T W = (T)ELin<T>::ex((double)w);
+        const T W = (T)LinExp<T>::ex((double)w);
         l_src[e] = g.in_src[e];
         l_w[e] = W;
         lost |= (double)w > neg_inf() && !(W >= std::numeric_limits<T>::min());
     }
     const bool scaled = __builtin_amdgcn_ballot_w64(lost) == 0;          // (wave-uniform)
-    ev_wave_order();
+    wave_order();
     // the lane's states j = lane + 64 p (lanes without one carry nothing and an empty arc list)
     bool st[SPL];
     int e0[SPL], e1[SPL];
@@ -206,7 +141,7 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
             const int j = lane + 64 * p;
-            r[p] = st[p] ? ELin<T>::ex((double)init[j]) : 0.0;
+            r[p] = st[p] ? LinExp<T>::ex((double)init[j]) : 0.0;
             ll_next[p] = st[p] ? llh[j] : (T)0;
         }
         double total = 0.0;
@@ -225,17 +160,17 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
                     for (int e = e0[p]; e < e1[p]; ++e) acc += cur[l_src[e]] * (double)l_w[e];
                     r[p] = acc;
                 }
-                ev_wave_order();                            // the row is read: it may be rewritten
+                wave_order();                            // the row is read: it may be rewritten
             }
             double m = neg_inf();
 #pragma unroll
-            for (int p = 0; p < SPL; ++p) m = emax(m, r[p] > 0.0 ? (double)ll[p] : neg_inf());
+            for (int p = 0; p < SPL; ++p) m = dmax(m, r[p] > 0.0 ? (double)ll[p] : neg_inf());
             m = wave_max(m);
             if (!(m > neg_inf()) || !(m < __builtin_huge_val())) { ok = false; break; }
             double n = 0.0;
 #pragma unroll
             for (int p = 0; p < SPL; ++p) {
-                q[p] = r[p] > 0.0 ? r[p] * ELin<T>::ex((double)ll[p] - m) : 0.0;
+                q[p] = r[p] > 0.0 ? r[p] * LinExp<T>::ex((double)ll[p] - m) : 0.0;
                 n += q[p];
             }
             n = wave_sum(n);
@@ -249,13 +184,13 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
                 q[p] *= inv;
                 cur[lane + 64 * p] = q[p];
             }
-            ev_wave_order();
+            wave_order();
         }
         if (ok) {
             double v = 0.0;
 #pragma unroll
             for (int p = 0; p < SPL; ++p)
-                if (st[p]) v += q[p] * ELin<T>::ex((double)fin[lane + 64 * p]);
+                if (st[p]) v += q[p] * LinExp<T>::ex((double)fin[lane + 64 * p]);
             v = wave_sum(v);
             if (v >= kEvMinNorm && v < __builtin_huge_val()) {
                 if (lane == 0) utt_evidence[u] = total + log(v);
@@ -266,7 +201,7 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
 
     // ---- the same utterance in log space ----
     for (int e = lane; e < A; e += 64) l_w[e] = in_w[e];
-    ev_wave_order();
+    wave_order();
     double a[SPL];
 #pragma unroll
     for (int p = 0; p < SPL; ++p) {
@@ -287,7 +222,7 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
             a[p] -= lz;
             cur[lane + 64 * p] = a[p];
         }
-        ev_wave_order();
+        wave_order();
         if (t + 1 >= T_) break;
         T ll_cur[SPL];
 #pragma unroll
@@ -298,10 +233,10 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
 #pragma unroll
         for (int p = 0; p < SPL; ++p) {
             double m = neg_inf(), s = 0.0;
-            for (int e = e0[p]; e < e1[p]; ++e) ev_add<T>(m, s, cur[l_src[e]] + (double)l_w[e]);
-            a[p] = st[p] ? (double)ll_cur[p] + ev_value<T>(m, s) : neg_inf();
+            for (int e = e0[p]; e < e1[p]; ++e) lse_add<T>(m, s, cur[l_src[e]] + (double)l_w[e]);
+            a[p] = st[p] ? (double)ll_cur[p] + lse_value<T>(m, s) : neg_inf();
         }
-        ev_wave_order();                                    // the row is read: it may be rewritten
+        wave_order();                                    // the row is read: it may be rewritten
     }
     double v[SPL];
 #pragma unroll
@@ -313,31 +248,6 @@ __global__ __launch_bounds__(64 * kEvWaves) void evidence_wave_kernel(
 // ---------------------------------------------------------------------------
 // one workgroup per utterance
 // ---------------------------------------------------------------------------
-// ln sum_j exp(val(j)) over the states j = j0, j0 + step, ... < S of every thread (-inf: nothing
-// finite), the same value in every thread.  Two barriers: the waves' maxima go through
-// red[0 .. 7], their sums through red[8 .. 15]; a caller puts one more barrier between two calls.
-template <typename T, typename F>
-__device__ __forceinline__ double ev_block_lse(int S, int j0, int step, F val, double* red) {
-    const int tid = threadIdx.x, nt_ = blockDim.x;
-    const int lane = tid & 63, w = tid >> 6, nw = (nt_ + 63) >> 6;
-    double lm = neg_inf();
-    for (int j = j0; j < S; j += step) lm = emax(lm, val(j));
-    lm = wave_max(lm);
-    if (lane == 0) red[w] = lm;
-    __syncthreads();
-    double m = red[0];
-    for (int i = 1; i < nw; ++i) m = emax(m, red[i]);
-    const double base = m > neg_inf() ? m : 0.0;
-    double ls = 0.0;
-    for (int j = j0; j < S; j += step) ls += ERel<T>::ex(val(j) - base);
-    ls = wave_sum(ls);
-    if (lane == 0) red[kEvRed / 2 + w] = ls;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[kEvRed / 2 + i];
-    return s > 0.0 ? base + ERel<T>::lg(s) : neg_inf();
-}
-
 template <typename T>
 __global__ __launch_bounds__(kEvQuadThreads) void evidence_block_kernel(
     beer_batch b, const T* __restrict__ pc_llhs, double* __restrict__ utt_evidence,
@@ -359,7 +269,7 @@ __global__ __launch_bounds__(kEvQuadThreads) void evidence_block_kernel(
     double* cur = reinterpret_cast<double*>(smem);                     // â_{t-1}
     double* nxt = cur + b.max_states;                                  // a_t
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kEvRed);         // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_src = l_ptr + b.max_states + 1;                         // [A]
     T* l_w = reinterpret_cast<T*>(l_src + b.max_arcs + ((b.max_states + 1 + b.max_arcs) & 1));
     const int32_t* in_ptr = g.in_ptr;
@@ -386,7 +296,7 @@ __global__ __launch_bounds__(kEvQuadThreads) void evidence_block_kernel(
     double* fev = frame_evidence ? frame_evidence + f0 : nullptr;
     for (int64_t t = 0;; ++t) {
         // (first barrier inside: every thread is done reading `cur`, the arc lists are staged)
-        const double c = ev_block_lse<T>(S, j0, step, [&](int j) { return nxt[j]; }, red);
+        const double c = block_lse<T>(S, j0, step, [&](int j) { return nxt[j]; }, red);
         const double lz = c > neg_inf() ? c : 0.0;          // nothing reachable: all stay -inf
         total += c;
         if (fev && tid == 0) fev[t] = c;
@@ -398,21 +308,21 @@ __global__ __launch_bounds__(kEvQuadThreads) void evidence_block_kernel(
         if (quad) {
             const int e0 = qj < S ? in_ptr[qj] + qp : 0, e1 = qj < S ? in_ptr[qj + 1] : 0;
             double m = neg_inf(), s = 0.0;
-            for (int e = e0; e < e1; e += 4) ev_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
-            ev_join<T>(m, s, wave_detail::dpp<double, 0xB1>(m), wave_detail::dpp<double, 0xB1>(s));
-            ev_join<T>(m, s, wave_detail::dpp<double, 0x4E>(m), wave_detail::dpp<double, 0x4E>(s));
-            if (pj >= 0) nxt[qj] = (double)ll_cur + ev_value<T>(m, s);
+            for (int e = e0; e < e1; e += 4) lse_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
+            lse_join<T>(m, s, wave_detail::dpp<double, 0xB1>(m), wave_detail::dpp<double, 0xB1>(s));
+            lse_join<T>(m, s, wave_detail::dpp<double, 0x4E>(m), wave_detail::dpp<double, 0x4E>(s));
+            if (pj >= 0) nxt[qj] = (double)ll_cur + lse_value<T>(m, s);
         } else {
             for (int j = tid; j < S; j += nt_) {
                 double m = neg_inf(), s = 0.0;
                 for (int e = in_ptr[j]; e < in_ptr[j + 1]; ++e)
-                    ev_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
+                    lse_add<T>(m, s, cur[in_src[e]] + (double)in_w[e]);
                 const double ll = one ? (double)ll_cur : (double)llh[(t + 1) * S + j];
-                nxt[j] = ll + ev_value<T>(m, s);
+                nxt[j] = ll + lse_value<T>(m, s);
             }
         }
     }
-    const double tail = ev_block_lse<T>(S, j0, step,
+    const double tail = block_lse<T>(S, j0, step,
                                         [&](int j) { return cur[j] + (double)fin[j]; }, red);
     if (tid == 0) utt_evidence[u] = total + tail;
 }
@@ -426,14 +336,11 @@ struct EvidencePlan {
     int wave_stride;         // wave form: bytes of a wave's slice
 };
 inline bool evidence_plan(int dtype, const beer_batch* b, EvidencePlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b)) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
-    const size_t rows = (2 * S + kEvRed) * 8;                 // two fp64 rows and the scratch
+    const size_t rows = block_rows_bytes(S);
     if (rows > (size_t)kMaxDynLds) return false;
-    const size_t arcs = (S + 2 + A) * 4 + A * w;
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, false, false);
     const int spl = S <= 64 ? 1 : (S <= 128 ? 2 : 4);
     const size_t slice = 8 * 64 * (size_t)spl + arcs;         // the row of a wave and its arcs
     p->spl = 0;
@@ -445,7 +352,7 @@ inline bool evidence_plan(int dtype, const beer_batch* b, EvidencePlan* p) {
         p->lds = (size_t)kEvWaves * p->wave_stride;
         return true;
     }
-    p->arcs_in_lds = rows + arcs <= kEvArcBytes;
+    p->arcs_in_lds = rows + arcs <= kBlockArcBytes;
     p->quad = 4 * S <= (size_t)kEvQuadThreads;
     p->lds = rows + (p->arcs_in_lds ? arcs : 0);
     return true;
@@ -454,13 +361,9 @@ inline bool evidence_plan(int dtype, const beer_batch* b, EvidencePlan* p) {
 template <typename T, int SPL>
 int evidence_launch_wave(const beer_batch* b, const EvidencePlan& p, const void* pc_llhs,
                          double* utt_evidence, double* frame_evidence, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(evidence_wave_kernel<T, SPL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL((evidence_wave_kernel<T, SPL>), dim3((b->nutt + kEvWaves - 1) / kEvWaves),
-                       dim3(64 * kEvWaves), p.lds, as_stream(stream), *b, (const T*)pc_llhs,
-                       utt_evidence, frame_evidence, p.wave_stride);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(evidence_wave_kernel<T, SPL>, dim3((b->nutt + kEvWaves - 1) / kEvWaves),
+                           dim3(64 * kEvWaves), p.lds, as_stream(stream), *b, (const T*)pc_llhs,
+                           utt_evidence, frame_evidence, p.wave_stride);
 }
 
 template <typename T>
@@ -472,13 +375,9 @@ int evidence_launch(const beer_batch* b, const EvidencePlan& p, const void* pc_l
         return evidence_launch_wave<T, 2>(b, p, pc_llhs, utt_evidence, frame_evidence, stream);
     if (p.spl == 4)
         return evidence_launch_wave<T, 4>(b, p, pc_llhs, utt_evidence, frame_evidence, stream);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(evidence_block_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(evidence_block_kernel<T>, dim3(b->nutt),
-                       dim3(p.quad ? kEvQuadThreads : kEvThreads), p.lds, as_stream(stream), *b,
-                       (const T*)pc_llhs, utt_evidence, frame_evidence, p.arcs_in_lds);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(evidence_block_kernel<T>, dim3(b->nutt),
+                           dim3(p.quad ? kEvQuadThreads : kEvThreads), p.lds, as_stream(stream), *b,
+                           (const T*)pc_llhs, utt_evidence, frame_evidence, p.arcs_in_lds);
 }
 
 }  // namespace

@@ -25,44 +25,15 @@
 //     workgroup runs the same max_dur steps with one barrier each (the fold of step k goes to
 //     slot k & 1 and is written out and reset during step k + 1).
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
 namespace {
 
 constexpr int kSgThreads = 256;
-constexpr int kSgRed = 16;                       // doubles of block-reduction scratch
-constexpr size_t kSgArcBytes = 64 * 1024;        // arcs stay in LDS below this total
-constexpr size_t kSgBinRows = 96 * 1024;         // bins are kept in LDS beside rows up to this
-constexpr int kSgBinCats = 2048;                 // ... and up to this many categories
+constexpr int kSgBinCats = 2048;                 // a frame's bins stay in LDS up to here
 constexpr int kSgTurn = 8;                       // out-rows from here on start at their own arc
-constexpr size_t kSgTeamBytes = 64 * 1024;       // the rows and slots of a workgroup's teams
-
-__device__ __forceinline__ double smax(double a, double b) { return b > a ? b : a; }
-
-// Order-preserving keys, as in hmm_lattice.hip: a < b exactly when key(a) < key(b).
-template <typename V> struct SgKey;
-template <> struct SgKey<double> {
-    using K = long long;
-    static __device__ __forceinline__ K key(double v) {
-        const K b = __builtin_bit_cast(K, v);
-        return b >= 0 ? b : (b ^ 0x7fffffffffffffffLL);
-    }
-    static __device__ __forceinline__ double val(K k) {
-        return __builtin_bit_cast(double, k >= 0 ? k : (k ^ 0x7fffffffffffffffLL));
-    }
-};
-template <> struct SgKey<float> {
-    using K = int;
-    static __device__ __forceinline__ K key(float v) {
-        const K b = __builtin_bit_cast(K, v);
-        return b >= 0 ? b : (b ^ 0x7fffffff);
-    }
-    static __device__ __forceinline__ float val(K k) {
-        return __builtin_bit_cast(float, k >= 0 ? k : (k ^ 0x7fffffff));
-    }
-};
 
 struct SgForm {
     int arcs_in_lds, bins_lds;
@@ -74,8 +45,8 @@ __global__ __launch_bounds__(kSgThreads) void segment_trellis_kernel(
     double* __restrict__ d_out, double* __restrict__ x_out, double* __restrict__ ws,
     T* __restrict__ frame_out, double* __restrict__ best_out, SgForm form) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using DK = SgKey<double>;
-    using TK = SgKey<T>;
+    using DK = OrderedKey<double>;
+    using TK = OrderedKey<T>;
     const int tid = threadIdx.x, nt_ = blockDim.x;
     const int u = b.order ? b.order[blockIdx.x] : (int)blockIdx.x;
     const int gid = b.graph_id[u];
@@ -96,7 +67,7 @@ __global__ __launch_bounds__(kSgThreads) void segment_trellis_kernel(
     double* cur = reinterpret_cast<double*>(smem);
     double* nxt = cur + b.max_states;
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kSgRed);         // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_end = l_ptr + b.max_states + 1;                         // [A] the arc's other end
     int32_t* l_cat = l_end + b.max_arcs;                               // [A]
     const int n_int = b.max_states + 1 + 2 * b.max_arcs;
@@ -125,7 +96,7 @@ __global__ __launch_bounds__(kSgThreads) void segment_trellis_kernel(
         for (int j = tid; j < S; j += nt_) {
             double m = neg_inf();
             for (int e = a_ptr[j]; e < a_ptr[j + 1]; ++e)
-                m = smax(m, cur[a_end[e]] + (double)a_w[e]);
+                m = dmax(m, cur[a_end[e]] + (double)a_w[e]);
             const double d = m + (double)llh[t * S + j];
             nxt[j] = d;
             dtr[t * S + j] = d;
@@ -134,7 +105,7 @@ __global__ __launch_bounds__(kSgThreads) void segment_trellis_kernel(
         double* sw = cur; cur = nxt; nxt = sw;
     }
     double part = neg_inf();
-    for (int j = tid; j < S; j += nt_) part = smax(part, cur[j] + (double)fin[j]);
+    for (int j = tid; j < S; j += nt_) part = dmax(part, cur[j] + (double)fin[j]);
     const double best = block_max(part, red);              // (the same in every thread)
     if (tid == 0) best_out[u] = best;
     if (!(best > neg_inf())) {
@@ -215,8 +186,8 @@ __global__ __launch_bounds__(kSgThreads) void segment_trellis_kernel(
                 const int c = cat[e];
                 const double w = (double)a_w[e], l = lrow[j], ev = erow[j];
                 const double on = w + (l + ev);
-                m = smax(m, on);
-                if (c >= 0) xm = smax(xm, on);
+                m = dmax(m, on);
+                if (c >= 0) xm = dmax(xm, on);
                 fold(c, (((d + w) + l) + ev) - best);
                 if (++e == e1) e = e0;
             }
@@ -257,7 +228,7 @@ __global__ __launch_bounds__(kSgThreads) void segment_margins_kernel(
     const int32_t* __restrict__ entry_cat, const int64_t* __restrict__ entry_off,
     int64_t n_entries, int max_dur, T* __restrict__ out, int L, int row) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using DK = SgKey<double>;
+    using DK = OrderedKey<double>;
     const int tid = threadIdx.x;
     const int team = tid / L, lane = tid - team * L;
     double* r0 = reinterpret_cast<double*>(smem) + (size_t)team * (2 * row + 2);
@@ -309,7 +280,7 @@ __global__ __launch_bounds__(kSgThreads) void segment_margins_kernel(
                 } else {
                     const double l = (double)llh[s * S + j];
                     for (int a = sm.ent_ptr[m0 + m]; a < sm.ent_ptr[m0 + m + 1]; ++a)
-                        r = smax(r, (dtr[(s - 1) * S + sm.ent_src[a]] + (double)w[sm.ent_arc[a]]) + l);
+                        r = dmax(r, (dtr[(s - 1) * S + sm.ent_src[a]] + (double)w[sm.ent_arc[a]]) + l);
                 }
                 r0[m] = r;
             }
@@ -346,9 +317,9 @@ __global__ __launch_bounds__(kSgThreads) void segment_margins_kernel(
                 if (more) {
                     double r = neg_inf();
                     if (n0 > 0) r = (cur[s0] + w0) + lv;
-                    if (n0 > 1) r = smax(r, (cur[s1] + w1) + lv);
+                    if (n0 > 1) r = dmax(r, (cur[s1] + w1) + lv);
                     for (int a = a0 + 2; a < a0 + n0; ++a)
-                        r = smax(r, (cur[sm.in_src[a]] + (double)w[sm.in_arc[a]]) + lv);
+                        r = dmax(r, (cur[sm.in_src[a]] + (double)w[sm.in_arc[a]]) + lv);
                     nxt[lane] = r;
                 }
                 xv = xn;
@@ -356,12 +327,12 @@ __global__ __launch_bounds__(kSgThreads) void segment_margins_kernel(
             }
             for (int m = lane + L; m < M; m += L) {             // (closures beyond 256 states)
                 const int j = sm.members[m0 + m];
-                part = smax(part, cur[m] + xtr[t * S + j]);
+                part = dmax(part, cur[m] + xtr[t * S + j]);
                 if (more) {
                     const double l = (double)llh[(t + 1) * S + j];
                     double r = neg_inf();
                     for (int a = sm.in_ptr[m0 + m]; a < sm.in_ptr[m0 + m + 1]; ++a)
-                        r = smax(r, (cur[sm.in_src[a]] + (double)w[sm.in_arc[a]]) + l);
+                        r = dmax(r, (cur[sm.in_src[a]] + (double)w[sm.in_arc[a]]) + l);
                     nxt[m] = r;
                 }
             }
@@ -390,46 +361,31 @@ struct SgPlan {
     size_t team_lds;         // dynamic LDS of the expand launch
 };
 inline bool sg_plan(int dtype, const beer_batch* b, int n_cat, int max_closure, SgPlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b)) return false;
     if (n_cat < 1 || max_closure < 0 || max_closure > b->max_states) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
-    const size_t rows = (2 * S + kSgRed) * 8;                 // two fp64 rows and the scratch
+    const size_t rows = block_rows_bytes(S);
     if (rows > (size_t)kMaxDynLds) return false;
-    const size_t arcs = (S + 2 + 2 * A) * 4 + (A + 1) * w;    // the out-CSR with its categories
+    // the out-CSR with its categories
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, true, true);
     size_t lds = rows;
-    p->form.arcs_in_lds = rows + arcs <= kSgArcBytes;
+    p->form.arcs_in_lds = rows + arcs <= kBlockArcBytes;
     if (p->form.arcs_in_lds) lds += arcs;
-    p->form.bins_lds = rows <= kSgBinRows && n_cat <= kSgBinCats;
+    p->form.bins_lds = rows <= kBlockBinRows && n_cat <= kSgBinCats;
     if (p->form.bins_lds) lds += 8 * (size_t)n_cat;
     p->lds = lds;
-    int team = 4;
-    while (team < kSgThreads && team < max_closure) team *= 2;
-    p->team = team;
-    p->row = max_closure > 1 ? max_closure : 1;
-    p->team_lds = (size_t)(kSgThreads / team) * (2 * (size_t)p->row + 2) * 8;
-    return p->team_lds <= kSgTeamBytes;
-}
-
-inline int sg_log2(int v) {
-    int n = 0;
-    while ((1 << n) < v) ++n;
-    return n;
+    // per team two rows of the closure and two key slots
+    return team_plan(max_closure, kSgThreads, 2, 2, kBlockTeamBytes, &p->team, &p->row,
+                     &p->team_lds);
 }
 
 template <typename T>
 int sg_trellis_launch(const beer_batch* b, const SgPlan& p, const void* pc_llhs,
                       const beer_arc_map* map, int n_cat, double* d, double* x, double* ws,
                       void* frame_out, double* best, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(segment_trellis_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(segment_trellis_kernel<T>, dim3(b->nutt), dim3(kSgThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, d, x, ws,
-                       (T*)frame_out, best, p.form);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(segment_trellis_kernel<T>, dim3(b->nutt), dim3(kSgThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, d, x, ws,
+                           (T*)frame_out, best, p.form);
 }
 
 template <typename T>
@@ -438,16 +394,12 @@ int sg_margins_launch(const beer_batch* b, const SgPlan& p, const void* pc_llhs,
                       const double* best, const int64_t* entry_frame, const int32_t* entry_cat,
                       const int64_t* entry_off, int64_t n_entries, int max_dur, void* out,
                       void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(segment_margins_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     const int64_t teams = kSgThreads / p.team;
     const int64_t blocks = (n_entries + teams - 1) / teams;
-    hipLaunchKernelGGL(segment_margins_kernel<T>, dim3((unsigned)blocks), dim3(kSgThreads),
-                       p.team_lds, as_stream(stream), *b, (const T*)pc_llhs, *sm, n_cat, d, x, best,
-                       entry_frame, entry_cat, entry_off, n_entries, max_dur, (T*)out, p.team,
-                       p.row);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(segment_margins_kernel<T>, dim3((unsigned)blocks), dim3(kSgThreads),
+                           p.team_lds, as_stream(stream), *b, (const T*)pc_llhs, *sm, n_cat, d, x,
+                           best, entry_frame, entry_cat, entry_off, n_entries, max_dur, (T*)out,
+                           p.team, p.row);
 }
 
 }  // namespace
@@ -497,7 +449,7 @@ int beer_hmm_segments_route(int dtype, const beer_batch* b, int n_cat, int max_c
     SgPlan p;
     BEER_REQUIRE(sg_plan(dtype, b, n_cat, max_closure, &p));
     return BEER_SEGMENTS_BLOCK | (p.form.arcs_in_lds ? BEER_SEGMENTS_ARCS_LDS : 0) |
-           (p.form.bins_lds ? BEER_SEGMENTS_BINS_LDS : 0) | sg_log2(p.team);
+           (p.form.bins_lds ? BEER_SEGMENTS_BINS_LDS : 0) | ceil_log2(p.team);
 }
 
 }  // extern "C"

@@ -32,69 +32,15 @@
 // Arithmetic: hmm.hip's rule -- sums, differences, the trellises and the folds are fp64, exp / log
 // are in the model's precision.
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
 namespace {
 
 constexpr int kSpThreads = 256;
-constexpr int kSpRed = 16;                       // doubles of block-reduction scratch
-constexpr size_t kSpArcBytes = 64 * 1024;        // arcs stay in LDS below this total
-constexpr size_t kSpBinRows = 96 * 1024;         // bins are kept in LDS beside rows up to this
-constexpr int kSpBinCats = 1024;                 // ... and up to this many categories
-constexpr size_t kSpTeamBytes = 64 * 1024;       // the rows and slots of a workgroup's teams
+constexpr int kSpBinCats = 1024;                 // a frame's bins stay in LDS up to here
 constexpr int kSpSlots = 8;                      // doubles of a team's slots: 2 steps x 4 waves
-
-template <typename T> struct PRel;
-template <> struct PRel<float> {
-    static __device__ __forceinline__ double ex(double d) {
-        return (double)__builtin_amdgcn_exp2f((float)d * 1.44269504088896340736f);
-    }
-    static __device__ __forceinline__ double lg(double s) {
-        return (double)(__builtin_amdgcn_logf((float)s) * 0.69314718055994530942f);
-    }
-};
-template <> struct PRel<double> {
-    static __device__ __forceinline__ double ex(double d) { return exp(d); }
-    static __device__ __forceinline__ double lg(double s) { return log(s); }
-};
-
-__device__ __forceinline__ double pmax(double a, double b) { return b > a ? b : a; }
-
-template <typename T>
-__device__ __forceinline__ void sp_lse_add(double& m, double& s, double v) {
-    if (v > m) {
-        s = s * PRel<T>::ex(m - v) + 1.0;          // (m = -inf: s = 0 stays 0 * 0)
-        m = v;
-    } else if (v > neg_inf()) {
-        s += PRel<T>::ex(v - m);
-    }
-}
-
-// ln sum_j exp(val(j)) over the states j = tid, tid + blockDim, ... < S (-inf: nothing finite),
-// the same value in every thread.  Two barriers; a caller puts one more between two calls.
-template <typename T, typename F>
-__device__ __forceinline__ double sp_block_lse(int S, F val, double* red) {
-    const int tid = threadIdx.x, nt_ = blockDim.x;
-    const int lane = tid & 63, w = tid >> 6, nw = (nt_ + 63) >> 6;
-    double lm = neg_inf();
-    for (int j = tid; j < S; j += nt_) lm = pmax(lm, val(j));
-    lm = wave_max(lm);
-    if (lane == 0) red[w] = lm;
-    __syncthreads();
-    double m = red[0];
-    for (int i = 1; i < nw; ++i) m = pmax(m, red[i]);
-    const double base = m > neg_inf() ? m : 0.0;
-    double ls = 0.0;
-    for (int j = tid; j < S; j += nt_) ls += PRel<T>::ex(val(j) - base);
-    ls = wave_sum(ls);
-    if (lane == 0) red[kSpRed / 2 + w] = ls;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[kSpRed / 2 + i];
-    return s > 0.0 ? base + PRel<T>::lg(s) : neg_inf();
-}
 
 // The sum of v over the L lanes of a team (L a power of two, 4 .. 64: the team lies within a
 // wave), by the stages of wave_sum up to L: a fixed order, the same value in every lane of the team.
@@ -148,7 +94,7 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
     double* cur = reinterpret_cast<double*>(smem);
     double* nxt = cur + b.max_states;
     double* red = nxt + b.max_states;
-    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kSpRed);         // [S + 1]
+    int32_t* l_ptr = reinterpret_cast<int32_t*>(red + kBlockRed);      // [S + 1]
     int32_t* l_end = l_ptr + b.max_states + 1;                         // [A] the arc's other end
     int32_t* l_cat = l_end + b.max_arcs;                               // [A] (backward only)
     T* l_w = reinterpret_cast<T*>(l_cat + b.max_arcs + ((b.max_states + 1) & 1));      // [A]
@@ -170,7 +116,7 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
     double total = 0.0;                                    // sum_t c_t (the same in every thread)
     for (int64_t t = 0;; ++t) {
         // (first barrier inside: every thread is done reading `cur`, the arc lists are staged)
-        const double c = sp_block_lse<T>(S, [&](int j) { return nxt[j]; }, red);
+        const double c = block_lse<T>(S, [&](int j) { return nxt[j]; }, red);
         dead = !(c > neg_inf());
         if (dead) break;
         total += c;
@@ -185,13 +131,13 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
         for (int j = tid; j < S; j += nt_) {
             double m = neg_inf(), s = 0.0;
             for (int e = a_ptr[j]; e < a_ptr[j + 1]; ++e)
-                sp_lse_add<T>(m, s, cur[a_end[e]] + (double)a_w[e]);
-            nxt[j] = (double)llh[(t + 1) * S + j] + (s > 0.0 ? m + PRel<T>::lg(s) : neg_inf());
+                lse_add<T>(m, s, cur[a_end[e]] + (double)a_w[e]);
+            nxt[j] = (double)llh[(t + 1) * S + j] + lse_value<T>(m, s);
         }
     }
     double tail = neg_inf();
     if (!dead) {
-        tail = sp_block_lse<T>(S, [&](int j) { return cur[j] + (double)fin[j]; }, red);
+        tail = block_lse<T>(S, [&](int j) { return cur[j] + (double)fin[j]; }, red);
         dead = !(tail > neg_inf());
     }
     if (dead) {                                            // (the same in every thread)
@@ -245,7 +191,7 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
     for (int j = tid; j < S; j += nt_) ytr[(T_ - 1) * S + j] = (double)fin[j] - tail;
     if (T_ == 1) {
         // (every thread reads and writes its own states of `cur`)
-        for (int j = tid; j < S; j += nt_) dnxt[j] = PRel<T>::ex(cur[j] + (double)fin[j] - tail);
+        for (int j = tid; j < S; j += nt_) dnxt[j] = LogRel<T>::ex(cur[j] + (double)fin[j] - tail);
     } else {
         const double cT = norm[T_ - 1];
         for (int j = tid; j < S; j += nt_)
@@ -263,7 +209,7 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
             if (a > neg_inf()) {
                 for (int e = a_ptr[i]; e < a_ptr[i + 1]; ++e) {
                     const int c = cat[e];
-                    const double p = PRel<T>::ex(a + (double)a_w[e] + dcur[a_end[e]]);
+                    const double p = LogRel<T>::ex(a + (double)a_w[e] + dcur[a_end[e]]);
                     gam += p;
                     if (c >= 0) on += p;
                     fold(c, p);
@@ -279,10 +225,10 @@ __global__ __launch_bounds__(kSpThreads) void segpost_trellis_kernel(
         for (int i = tid; i < S; i += nt_) {
             const double a = arow[i];
             const double on = yrow[i];
-            yrow[i] = on > 0.0 ? PRel<T>::lg(on / G) - a : neg_inf();
+            yrow[i] = on > 0.0 ? LogRel<T>::lg(on / G) - a : neg_inf();
             if (t > 1) {
                 const double gam = dnxt[i];
-                const double bw = gam > 0.0 ? PRel<T>::lg(gam / G) - a : neg_inf();
+                const double bw = gam > 0.0 ? LogRel<T>::lg(gam / G) - a : neg_inf();
                 dnxt[i] = (double)llh[(t - 1) * S + i] + bw - cp;
             }
         }
@@ -364,7 +310,7 @@ __global__ __launch_bounds__(kSpThreads) void segment_posteriors_kernel(
                     } else {
                         const double gs = ((double)llh[s * S + j] - cs) - a;
                         for (int e = sm.ent_ptr[m0 + m]; e < sm.ent_ptr[m0 + m + 1]; ++e)
-                            rho += PRel<T>::ex((atr[(s - 1) * S + sm.ent_src[e]] +
+                            rho += LogRel<T>::ex((atr[(s - 1) * S + sm.ent_src[e]] +
                                                 (double)w[sm.ent_arc[e]]) + gs);
                     }
                 }
@@ -409,15 +355,15 @@ __global__ __launch_bounds__(kSpThreads) void segment_posteriors_kernel(
                     gnn = ((double)llh[(t + 2) * S + j0] - norm[t + 2]) - ann;
                 }
                 const double rho = rcur[lane];
-                if (rho > 0.0) part = rho * PRel<T>::ex(ev);
+                if (rho > 0.0) part = rho * LogRel<T>::ex(ev);
                 if (more) {
                     double r = 0.0;
                     if (an > neg_inf()) {
-                        if (n0 > 0) r = rcur[s0] * PRel<T>::ex((acur[s0] + w0) + gn);
-                        if (n0 > 1) r += rcur[s1] * PRel<T>::ex((acur[s1] + w1) + gn);
+                        if (n0 > 0) r = rcur[s0] * LogRel<T>::ex((acur[s0] + w0) + gn);
+                        if (n0 > 1) r += rcur[s1] * LogRel<T>::ex((acur[s1] + w1) + gn);
                         for (int a = a0 + 2; a < a0 + n0; ++a) {
                             const int i = sm.in_src[a];
-                            r += rcur[i] * PRel<T>::ex((acur[i] + (double)w[sm.in_arc[a]]) + gn);
+                            r += rcur[i] * LogRel<T>::ex((acur[i] + (double)w[sm.in_arc[a]]) + gn);
                         }
                     }
                     rnxt[lane] = r;
@@ -430,7 +376,7 @@ __global__ __launch_bounds__(kSpThreads) void segment_posteriors_kernel(
             for (int m = lane + L; m < M; m += L) {             // (closures beyond 256 states)
                 const int j = sm.members[m0 + m];
                 const double rho = rcur[m];
-                if (rho > 0.0) part += rho * PRel<T>::ex(acur[m] + ytr[t * S + j]);
+                if (rho > 0.0) part += rho * LogRel<T>::ex(acur[m] + ytr[t * S + j]);
                 if (more) {
                     const double a = atr[(t + 1) * S + j];
                     double r = 0.0;
@@ -438,7 +384,7 @@ __global__ __launch_bounds__(kSpThreads) void segment_posteriors_kernel(
                         const double gj = ((double)llh[(t + 1) * S + j] - norm[t + 1]) - a;
                         for (int e = sm.in_ptr[m0 + m]; e < sm.in_ptr[m0 + m + 1]; ++e) {
                             const int i = sm.in_src[e];
-                            r += rcur[i] * PRel<T>::ex((acur[i] + (double)w[sm.in_arc[e]]) + gj);
+                            r += rcur[i] * LogRel<T>::ex((acur[i] + (double)w[sm.in_arc[e]]) + gj);
                         }
                     }
                     rnxt[m] = r;
@@ -481,46 +427,31 @@ struct SpPlan {
     size_t team_lds;         // dynamic LDS of the expand launch
 };
 inline bool sp_plan(int dtype, const beer_batch* b, int n_cat, int max_closure, SpPlan* p) {
-    if (!b || b->nutt < 0 || b->max_states < 1 || b->max_states > 32767 || b->max_arcs < 0 ||
-        (dtype != BEER_F32 && dtype != BEER_F64))
-        return false;
+    if (!block_batch_ok(dtype, b)) return false;
     if (n_cat < 1 || max_closure < 0 || max_closure > b->max_states) return false;
     const size_t S = (size_t)b->max_states, A = (size_t)b->max_arcs;
-    const size_t w = dtype == BEER_F32 ? 4 : 8;
-    const size_t rows = (2 * S + kSpRed) * 8;                 // two fp64 rows and the scratch
+    const size_t rows = block_rows_bytes(S);
     if (rows > (size_t)kMaxDynLds) return false;
-    const size_t arcs = (S + 2 + 2 * A) * 4 + (A + 1) * w;    // the out-CSR with its categories
+    // the out-CSR with its categories
+    const size_t arcs = csr_bytes(S, A, dtype == BEER_F32 ? 4 : 8, true, true);
     size_t lds = rows;
-    p->form.arcs_in_lds = rows + arcs <= kSpArcBytes;
+    p->form.arcs_in_lds = rows + arcs <= kBlockArcBytes;
     if (p->form.arcs_in_lds) lds += arcs;
-    p->form.bins_lds = rows <= kSpBinRows && n_cat <= kSpBinCats;
+    p->form.bins_lds = rows <= kBlockBinRows && n_cat <= kSpBinCats;
     if (p->form.bins_lds) lds += 8 * (size_t)n_cat;
     p->lds = lds;
-    int team = 4;
-    while (team < kSpThreads && team < max_closure) team *= 2;
-    p->team = team;
-    p->row = max_closure > 1 ? max_closure : 1;
-    p->team_lds = (size_t)(kSpThreads / team) * (4 * (size_t)p->row + kSpSlots) * 8;
-    return p->team_lds <= kSpTeamBytes;
-}
-
-inline int sp_log2(int v) {
-    int n = 0;
-    while ((1 << n) < v) ++n;
-    return n;
+    // per team rho and â of the closure, twice, and the slots of the fold
+    return team_plan(max_closure, kSpThreads, 4, kSpSlots, kBlockTeamBytes, &p->team, &p->row,
+                     &p->team_lds);
 }
 
 template <typename T>
 int sp_trellis_launch(const beer_batch* b, const SpPlan& p, const void* pc_llhs,
                       const beer_arc_map* map, int n_cat, double* alpha, double* y, double* norm,
                       void* frame_out, double* evidence, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(segpost_trellis_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL(segpost_trellis_kernel<T>, dim3(b->nutt), dim3(kSpThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, alpha, y, norm,
-                       (T*)frame_out, evidence, p.form);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(segpost_trellis_kernel<T>, dim3(b->nutt), dim3(kSpThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, *map, n_cat, alpha, y, norm,
+                           (T*)frame_out, evidence, p.form);
 }
 
 template <typename T>
@@ -529,16 +460,12 @@ int sp_expand_launch(const beer_batch* b, const SpPlan& p, const void* pc_llhs,
                      const double* norm, const double* evidence, const int64_t* entry_frame,
                      const int32_t* entry_cat, const int64_t* entry_off, int64_t n_entries,
                      int max_dur, void* out, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(segment_posteriors_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     const int64_t teams = kSpThreads / p.team;
     const int64_t blocks = (n_entries + teams - 1) / teams;
-    hipLaunchKernelGGL(segment_posteriors_kernel<T>, dim3((unsigned)blocks), dim3(kSpThreads),
-                       p.team_lds, as_stream(stream), *b, (const T*)pc_llhs, *sm, n_cat, alpha, y,
-                       norm, evidence, entry_frame, entry_cat, entry_off, n_entries, max_dur,
-                       (T*)out, p.team, p.row);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(segment_posteriors_kernel<T>, dim3((unsigned)blocks), dim3(kSpThreads),
+                           p.team_lds, as_stream(stream), *b, (const T*)pc_llhs, *sm, n_cat, alpha,
+                           y, norm, evidence, entry_frame, entry_cat, entry_off, n_entries, max_dur,
+                           (T*)out, p.team, p.row);
 }
 
 }  // namespace
@@ -581,7 +508,7 @@ int beer_hmm_segposts_route(int dtype, const beer_batch* b, int n_cat, int max_c
     SpPlan p;
     BEER_REQUIRE(sp_plan(dtype, b, n_cat, max_closure, &p));
     return BEER_SEGPOSTS_BLOCK | (p.form.arcs_in_lds ? BEER_SEGPOSTS_ARCS_LDS : 0) |
-           (p.form.bins_lds ? BEER_SEGPOSTS_BINS_LDS : 0) | sp_log2(p.team);
+           (p.form.bins_lds ? BEER_SEGPOSTS_BINS_LDS : 0) | ceil_log2(p.team);
 }
 
 }  // extern "C"

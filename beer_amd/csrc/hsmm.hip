@@ -24,7 +24,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "hmm_block.h"
 
 using namespace beer;
 
@@ -56,20 +56,8 @@ struct HsArgs {
     int map_pdf;
 };
 
-__device__ __forceinline__ double hmax(double a, double b) { return b > a ? b : a; }
+// (fp64 throughout: a log-sum-exp is hmm_block.h's pair, lse_add<double> / lse_value<double>)
 
-// log-sum-exp as the pair (m, s): sum = s exp(m)
-__device__ __forceinline__ void hs_add(double& m, double& s, double v) {
-    if (v > m) {
-        s = s * exp(m - v) + 1.0;                       // (m = -inf: s = 0 stays 0)
-        m = v;
-    } else if (v > neg_inf()) {
-        s += exp(v - m);
-    }
-}
-__device__ __forceinline__ double hs_value(double m, double s) {
-    return s > 0.0 ? m + log(s) : neg_inf();
-}
 // Viterbi: the larger value, the smaller index among equals
 __device__ __forceinline__ void hs_best(double& m, int& arg, double v, int i) {
     if (v > m || (v == m && v > neg_inf() && i < arg)) { m = v; arg = i; }
@@ -83,7 +71,7 @@ __device__ __forceinline__ void hs_block_max2(double& a, double& b, double* red)
     if (lane == 0) { red[w] = a; red[8 + w] = b; }
     __syncthreads();
     a = red[0]; b = red[8];
-    for (int i = 1; i < kHsThreads / 64; ++i) { a = hmax(a, red[i]); b = hmax(b, red[8 + i]); }
+    for (int i = 1; i < kHsThreads / 64; ++i) { a = dmax(a, red[i]); b = dmax(b, red[8 + i]); }
 }
 __device__ __forceinline__ double hs_block_sum(double a, double* red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
         double cN, dummy = neg_inf();
         {
             double m = neg_inf();
-            for (int j = tid; j < S; j += kHsThreads) m = hmax(m, (double)llh[j]);
+            for (int j = tid; j < S; j += kHsThreads) m = dmax(m, (double)llh[j]);
             hs_block_max2(m, dummy, red);
             cN = m > neg_inf() ? __builtin_rint(m) : 0.0;
         }
@@ -232,7 +220,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                     double m = neg_inf();
                     for (int p = p0 + lane; p < p1; p += 64) {
                         const int i = L.src_list[p];
-                        m = hmax(m, r1[i] + (double)hsw[i]);
+                        m = dmax(m, r1[i] + (double)hsw[i]);
                     }
                     m = wave_max(m);
                     const double base = m > neg_inf() ? m : 0.0;
@@ -242,7 +230,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         s += exp(r1[i] + (double)hsw[i] - base);
                     }
                     s = wave_sum(s);
-                    if (lane == 0) hubv[h] = s > 0.0 ? base + log(s) : neg_inf();
+                    if (lane == 0) hubv[h] = lse_value<double>(base, s);
                 }
                 __syncthreads();
             }
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                     double m = neg_inf(), s = 0.0;
                     for (int e = in_ptr[j]; e < in_ptr[j + 1]; ++e) {
                         const int i = in_src[e];
-                        if (i != j) hs_add(m, s, r1[i] + (double)in_w[e]);
+                        if (i != j) lse_add<double>(m, s, r1[i] + (double)in_w[e]);
                     }
                     const int hd = n_hubs > 0 ? L.hub_dst_id[j] : -1;
                     if (hd >= 0 && hd < n_hubs) {
@@ -270,13 +258,13 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                             // j feeds the hub that feeds it: the hub's value without j's own term
                             for (int p = L.src_ptr[hd]; p < L.src_ptr[hd + 1]; ++p) {
                                 const int i = L.src_list[p];
-                                if (i != j) hs_add(m, s, r1[i] + (double)hsw[i] + (double)hdw[j]);
+                                if (i != j) lse_add<double>(m, s, r1[i] + (double)hsw[i] + (double)hdw[j]);
                             }
                         } else {
-                            hs_add(m, s, hubv[hd] + (double)hdw[j]);
+                            lse_add<double>(m, s, hubv[hd] + (double)hdw[j]);
                         }
                     }
-                    bg = hs_value(m, s);
+                    bg = lse_value<double>(m, s);
                 }
                 r2[j] = bg;
                 if (VIT) bp[2 * (t * S + j)] = src;
@@ -303,7 +291,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         if (dd < 0) dd += D;
                         const double v = id < 0 ? neg_inf() : r + lam[dd];
                         if (VIT) hs_best(m, darg, v, dd + 1);
-                        else m = hmax(m, v);
+                        else m = dmax(m, v);
                     }
                 }
                 for (int o = team >> 1; o > 0; o >>= 1) {
@@ -312,7 +300,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         const int od = __shfl_xor(darg, o);
                         hs_best(m, darg, om, od);
                     } else {
-                        m = hmax(m, om);
+                        m = dmax(m, om);
                     }
                 }
                 double endv = m;
@@ -327,7 +315,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         }
                     }
                     for (int o = team >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
-                    endv = s > 0.0 ? base + log(s) : neg_inf();
+                    endv = lse_value<double>(base, s);
                 }
                 if (valid && tl == 0) {
                     r0[j] = endv;
@@ -340,8 +328,8 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
             // R: n_t and c_{t+1}
             double nm = neg_inf(), cm = neg_inf();
             for (int j = tid; j < S; j += kHsThreads) {
-                nm = hmax(nm, r0[j]);
-                if (t + 1 < T_) cm = hmax(cm, (double)llh[(t + 1) * S + j]);
+                nm = dmax(nm, r0[j]);
+                if (t + 1 < T_) cm = dmax(cm, (double)llh[(t + 1) * S + j]);
             }
             hs_block_max2(nm, cm, red);
             const double nt = hs_quant(nm);
@@ -402,13 +390,14 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
         double zs;
         {
             double m = neg_inf(), dm = neg_inf();
-            for (int j = tid; j < S; j += kHsThreads) m = hmax(m, r0[j] + (double)fin[j]);
+            for (int j = tid; j < S; j += kHsThreads) m = dmax(m, r0[j] + (double)fin[j]);
             hs_block_max2(m, dm, red);
             __syncthreads();
             const double base = m > neg_inf() ? m : 0.0;
             double s = 0.0;
             for (int j = tid; j < S; j += kHsThreads) s += exp(r0[j] + (double)fin[j] - base);
             s = hs_block_sum(s, red);
+            // (written out, as in block_lse: through lse_value the branch order changes)
             zs = s > 0.0 ? base + log(s) : neg_inf();
         }
         if (!(zs > neg_inf())) {
@@ -490,7 +479,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                     double m = neg_inf();
                     for (int p = p0 + lane; p < p1; p += 64) {
                         const int k = L.dst_list[p];
-                        m = hmax(m, r0[k] + (double)hdw[k]);
+                        m = dmax(m, r0[k] + (double)hdw[k]);
                     }
                     m = wave_max(m);
                     const double base = m > neg_inf() ? m : 0.0;
@@ -500,7 +489,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         s += exp(r0[k] + (double)hdw[k] - base);
                     }
                     s = wave_sum(s);
-                    if (lane == 0) hubv[h] = s > 0.0 ? base + log(s) : neg_inf();
+                    if (lane == 0) hubv[h] = lse_value<double>(base, s);
                 }
                 __syncthreads();
             }
@@ -517,7 +506,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         const int k = out_dst[e];
                         if (k != j) {
                             const double x = r0[k] + (double)out_w[e];
-                            hs_add(m, s, x);
+                            lse_add<double>(m, s, x);
                             if (ARCS) {
                                 const int c = cat[e];
                                 const double px = x + pre;
@@ -530,13 +519,13 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         if (L.hub_dst_id[j] == hs) {
                             for (int p = L.dst_ptr[hs]; p < L.dst_ptr[hs + 1]; ++p) {
                                 const int k = L.dst_list[p];
-                                if (k != j) hs_add(m, s, r0[k] + (double)hdw[k] + (double)hsw[j]);
+                                if (k != j) lse_add<double>(m, s, r0[k] + (double)hdw[k] + (double)hsw[j]);
                             }
                         } else {
-                            hs_add(m, s, hubv[hs] + (double)hsw[j]);
+                            lse_add<double>(m, s, hubv[hs] + (double)hsw[j]);
                         }
                     }
-                    bend = hs_value(m, s) + lv[j];
+                    bend = lse_value<double>(m, s) + lv[j];
                 }
                 const double ex = endT[t * S + j] + bend + kapE;
                 const double E = ex > neg_inf() ? exp(ex) : 0.0;
@@ -568,10 +557,10 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                         V[k] = r;
                         int dd = k - kn;
                         if (dd < 0) dd += D;
-                        m = hmax(m, id < 0 ? neg_inf() : r + lam[dd]);
+                        m = dmax(m, id < 0 ? neg_inf() : r + lam[dd]);
                     }
                 }
-                for (int o = team >> 1; o > 0; o >>= 1) m = hmax(m, __shfl_xor(m, o));
+                for (int o = team >> 1; o > 0; o >>= 1) m = dmax(m, __shfl_xor(m, o));
                 const double base = m > neg_inf() ? m : 0.0;
                 double s = 0.0;
                 if (valid && id >= 0 && m > neg_inf()) {
@@ -588,7 +577,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
                     for (int o = team >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
                     if (tl == 0) {
                         const double Bv = s * F;
-                        r0[j] = s > 0.0 ? base + log(s) : neg_inf();
+                        r0[j] = lse_value<double>(base, s);
                         bprev[j] = Bv;
                         if (t == 0) {
                             if (a.gamma0_sum) atomicAdd(a.gamma0_sum + j, Bv);
@@ -604,7 +593,7 @@ __global__ __launch_bounds__(kHsThreads) void hsmm_kernel(
             __syncthreads();
             // R: n'_t
             double nm = neg_inf(), dm = neg_inf();
-            for (int j = tid; j < S; j += kHsThreads) nm = hmax(nm, r0[j]);
+            for (int j = tid; j < S; j += kHsThreads) nm = dmax(nm, r0[j]);
             hs_block_max2(nm, dm, red);
             const double nt = hs_quant(nm);
             Np2 = Np1;
@@ -674,12 +663,8 @@ inline bool hsmm_plan(int dtype, const beer_batch* b, int D, HsmmPlan* p) {
 template <typename T, bool VIT>
 int hsmm_launch(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
                 void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, VIT, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL((hsmm_kernel<T, VIT, false>), dim3(p.grid), dim3(kHsThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, a, HsNoArcs{});
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(hsmm_kernel<T, VIT, false>, dim3(p.grid), dim3(kHsThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, a, HsNoArcs{});
 }
 template <typename T>
 int hsmm_launch_fb(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
@@ -717,12 +702,8 @@ inline bool hsmm_arcs_plan(int dtype, const beer_batch* b, int D, int n_cat, boo
 template <typename T>
 int hsmm_launch_arcs(const beer_batch* b, const HsmmPlan& p, const void* pc_llhs, const HsArgs& a,
                      const HsArcArgs& arc, void* stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hsmm_kernel<T, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    hipLaunchKernelGGL((hsmm_kernel<T, false, true>), dim3(p.grid), dim3(kHsThreads), p.lds,
-                       as_stream(stream), *b, (const T*)pc_llhs, a, arc);
-    BEER_LAUNCH_CHECK();
-    return BEER_OK;
+    return launch_full_lds(hsmm_kernel<T, false, true>, dim3(p.grid), dim3(kHsThreads), p.lds,
+                           as_stream(stream), *b, (const T*)pc_llhs, a, arc);
 }
 
 HsArgs hsmm_args(const HsmmPlan& p, const double* log_dur, const double* leave_w, int D,
