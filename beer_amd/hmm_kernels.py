@@ -19,7 +19,8 @@ __all__ = ['HmmBatch', 'gather', 'forward_backward', 'viterbi', 'path_posteriors
            'max_marginals', 'maxmarg_route', 'SegmentMap', 'segment_map', 'segments_route',
            'segment_margins', 'segments_within', 'check_segments', 'segposts_route',
            'segment_posteriors', 'segments_above', 'check_segment_posteriors',
-           'check_durations', 'duration_route', 'duration_forward_backward', 'duration_viterbi']
+           'check_durations', 'duration_route', 'duration_forward_backward', 'duration_viterbi',
+           'duration_arcs_route', 'duration_arc_posteriors']
 
 
 class HmmBatch:
@@ -163,6 +164,15 @@ def _route(dtype, desc, want_xi, have_hub_flow):
     'beer_hmm_fb_route: the kernel family (and its launch shape) the C entry points pick.'
     return _hip.lib().beer_hmm_fb_route(_hip.dtype_code(dtype), ctypes.byref(desc),
                                         int(want_xi), int(have_hub_flow))
+
+
+def _route_or_refuse(query, batch, args, refusal):
+    '''What the C route query `query` answers for the batch and the scalars `args`: the form the
+    family's kernels take.  HipInvalid with the text `refusal()` builds where C refuses.'''
+    route = getattr(_hip.lib(), query)(_hip.dtype_code(batch.dtype), batch.ref(), *args)
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(refusal())
+    return route
 
 
 def _workspace(batch, desc=None, want_xi=False, packed=True):
@@ -526,13 +536,10 @@ def nbest_route(batch, k):
     '''beer_hmm_nbest_route: the form `viterbi_nbest` runs on (the frames of back-pointers the
     back-trace stages at a time, arcs in LDS or not); HipInvalid where it refuses.'''
     k = check_nbest(k, 'nbest_route')
-    route = _hip.lib().beer_hmm_nbest_route(_hip.dtype_code(batch.dtype), batch.ref(), k)
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'viterbi_nbest: {k} paths on graphs of up to {batch.struct.max_states} states: at '
-            'most 32767 states, and two score columns [S][k] with two frames of back-pointers '
-            "[S][k] in the CU's 160 KB of LDS")
-    return route
+    return _route_or_refuse('beer_hmm_nbest_route', batch, (k,), lambda: (
+        f'viterbi_nbest: {k} paths on graphs of up to {batch.struct.max_states} states: at '
+        'most 32767 states, and two score columns [S][k] with two frames of back-pointers '
+        "[S][k] in the CU's 160 KB of LDS"))
 
 
 def viterbi_nbest(batch, pc_llhs, k, map_pdf=False):
@@ -577,14 +584,10 @@ def sample_uniforms(sample):
 def sample_route(batch, nsamples=1):
     '''beer_hmm_sample_route: the forms `sample_paths` runs on (frame chunk, arcs in LDS, four
     lanes per state in the forward pass, samples per workgroup); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_sample_route(_hip.dtype_code(batch.dtype), batch.ref(),
-                                             int(nsamples))
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'sample_paths: {nsamples} samples on graphs of up to {batch.struct.max_states} '
-            "states: at least one sample, and two fp64 trellis rows in the CU's 160 KB of LDS "
-            '(about 10000 states)')
-    return route
+    return _route_or_refuse('beer_hmm_sample_route', batch, (int(nsamples),), lambda: (
+        f'sample_paths: {nsamples} samples on graphs of up to {batch.struct.max_states} '
+        "states: at least one sample, and two fp64 trellis rows in the CU's 160 KB of LDS "
+        '(about 10000 states)'))
 
 
 def sample_paths(batch, pc_llhs, uniforms=None, nsamples=1, generator=None, map_pdf=False,
@@ -621,12 +624,9 @@ def evidence_route(batch):
     '''beer_hmm_evidence_route: the form `log_evidence` runs on (one wave per utterance with
     1 / 2 / 4 states a lane, or one workgroup per utterance with its arcs in LDS and four lanes
     per state or not); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_evidence_route(_hip.dtype_code(batch.dtype), batch.ref())
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'log_evidence: graphs of up to {batch.struct.max_states} states: two fp64 rows '
-            "must fit the CU's 160 KB of LDS (about 10000 states)")
-    return route
+    return _route_or_refuse('beer_hmm_evidence_route', batch, (), lambda: (
+        f'log_evidence: graphs of up to {batch.struct.max_states} states: two fp64 rows '
+        "must fit the CU's 160 KB of LDS (about 10000 states)"))
 
 
 def log_evidence(batch, pc_llhs, per_frame=False):
@@ -646,14 +646,11 @@ def log_evidence(batch, pc_llhs, per_frame=False):
 def arcs_route(batch, n_cat, per_frame=True):
     '''beer_hmm_arcs_route: the form `arc_posteriors` runs on (arcs in LDS or not, a frame's
     bins in LDS or not, the utterance's bins in LDS or not); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_arcs_route(_hip.dtype_code(batch.dtype), batch.ref(), int(n_cat),
-                                           1 if per_frame else 0)
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'arc_posteriors: {n_cat} categories on graphs of up to {batch.struct.max_states} '
-            "states: at least one category, and two fp64 rows in the CU's 160 KB of LDS (about "
-            '10000 states)')
-    return route
+    args = (int(n_cat), 1 if per_frame else 0)
+    return _route_or_refuse('beer_hmm_arcs_route', batch, args, lambda: (
+        f'arc_posteriors: {n_cat} categories on graphs of up to {batch.struct.max_states} '
+        "states: at least one category, and two fp64 rows in the CU's 160 KB of LDS (about "
+        '10000 states)'))
 
 
 def check_arc_categories(n_arcs, n_states, arc_cat, init_cat, n_cat, per_frame=True,
@@ -696,6 +693,26 @@ def check_arc_categories(n_arcs, n_states, arc_cat, init_cat, n_cat, per_frame=T
     return tuple(out)
 
 
+def _arc_map(batch, arcs, inits):
+    '''(beer_arc_map, keep) of the checked categories `arcs` / `inits` (`check_arc_categories`):
+    the offsets of every distinct graph and whichever of the two arrays is still on the host go
+    to the device in one upload; an empty arc array gets an element, so that its pointer is not
+    NULL.  `keep` holds the tensors the structure points into: the caller keeps it until the
+    launch that reads the structure has been queued.'''
+    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
+    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
+    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
+    if arcs.device.type != 'cuda':
+        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
+    if inits.device.type != 'cuda':
+        host['inits'] = inits
+    up = _hip.upload(host, batch.device)
+    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
+    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
+                       up['state_off'].data_ptr())
+    return amap, (up, arcs, inits)
+
+
 def arc_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, per_frame=True, per_utt=False):
     '''(frame_out [n_frames, n_cat] of the batch's dtype or None, utt_out [nutt, n_cat] fp64 or
     None), on the device: the posterior of every arc at every frame folded into categories
@@ -715,17 +732,7 @@ def arc_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, per_frame=True, per
         return (torch.empty(0, n_cat, dtype=batch.dtype, device=dev) if per_frame else None,
                 torch.empty(0, n_cat, dtype=torch.float64, device=dev) if per_utt else None)
     dcode = _hip.dtype_code(batch.dtype)
-    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
-    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
-    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
-    if arcs.device.type != 'cuda':
-        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
-    if inits.device.type != 'cuda':
-        host['inits'] = inits
-    up = _hip.upload(host, dev)
-    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
-    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
-                       up['state_off'].data_ptr())
+    amap, keep = _arc_map(batch, arcs, inits)               # (`keep` lives until the call)
     extra = _hip.lib().beer_hmm_arcs_scratch_doubles(dcode, batch.ref())
     ws = torch.empty(batch.n_frames + batch.n_elems + extra, dtype=torch.float64, device=dev)
     frame = torch.empty(batch.n_frames, n_cat, dtype=batch.dtype, device=dev) \
@@ -739,15 +746,11 @@ def arc_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, per_frame=True, per
 def maxmarg_route(batch, n_cat=0, states=True, per_frame=False, per_utt=False):
     '''beer_hmm_maxmarg_route: the form `max_marginals` runs on (arcs in LDS or not, the bins in
     LDS or in the output rows); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_maxmarg_route(_hip.dtype_code(batch.dtype), batch.ref(),
-                                              int(n_cat), 1 if states else 0,
-                                              1 if per_frame else 0, 1 if per_utt else 0)
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'max_marginals: {n_cat} categories on graphs of up to {batch.struct.max_states} '
-            'states: at least one output, at least one category for the outputs by category, '
-            "and two fp64 rows in the CU's 160 KB of LDS (about 10000 states)")
-    return route
+    args = (int(n_cat), 1 if states else 0, 1 if per_frame else 0, 1 if per_utt else 0)
+    return _route_or_refuse('beer_hmm_maxmarg_route', batch, args, lambda: (
+        f'max_marginals: {n_cat} categories on graphs of up to {batch.struct.max_states} '
+        'states: at least one output, at least one category for the outputs by category, '
+        "and two fp64 rows in the CU's 160 KB of LDS (about 10000 states)"))
 
 
 def max_marginals(batch, pc_llhs, arc_cat=None, init_cat=None, n_cat=0, states=True,
@@ -784,19 +787,10 @@ def max_marginals(batch, pc_llhs, arc_cat=None, init_cat=None, n_cat=0, states=T
     if batch.nutt == 0:
         return best, state, frame, utt
     dcode = _hip.dtype_code(batch.dtype)
-    amap = None
+    amap = keep = None                                      # (no categories: no map)
     if arcs is not None:
-        arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
-        state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
-        host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
-        if arcs.device.type != 'cuda':
-            host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
-        if inits.device.type != 'cuda':
-            host['inits'] = inits
-        up = _hip.upload(host, dev)
-        arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
-        amap = ctypes.byref(_hip.ArcMap(arcs.data_ptr(), inits.data_ptr(),
-                                        up['arc_off'].data_ptr(), up['state_off'].data_ptr()))
+        amap, keep = _arc_map(batch, arcs, inits)           # (`keep` lives until the call)
+        amap = ctypes.byref(amap)
     extra = _hip.lib().beer_hmm_maxmarg_scratch_doubles(dcode, batch.ref())
     ws = torch.empty(max(batch.n_elems + extra, 1), dtype=torch.float64, device=dev)
     _hip.call('beer_hmm_max_marginals', dcode, batch.ref(), _hip.ptr(pc_llhs), amap, n_cat,
@@ -915,15 +909,21 @@ def segments_route(batch, n_cat, max_closure=0):
     '''beer_hmm_segments_route: the form `segment_margins` runs on (the trellis kernel's arcs
     and bins in LDS or not, and in the low bits the team size of the expand kernel,
     `_hip.segments_team`); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_segments_route(_hip.dtype_code(batch.dtype), batch.ref(),
-                                               int(n_cat), int(max_closure))
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'segment_margins: {n_cat} categories with closures of up to {max_closure} states on '
-            f'graphs of up to {batch.struct.max_states} states: at least one category, two fp64 '
-            "rows of the graph in the CU's 160 KB of LDS (about 10000 states), and two fp64 rows "
-            'of the largest closure in 64 KB (4095 states)')
-    return route
+    args = (int(n_cat), int(max_closure))
+    return _route_or_refuse('beer_hmm_segments_route', batch, args, lambda: (
+        f'segment_margins: {n_cat} categories with closures of up to {max_closure} states on '
+        f'graphs of up to {batch.struct.max_states} states: at least one category, two fp64 '
+        "rows of the graph in the CU's 160 KB of LDS (about 10000 states), and two fp64 rows "
+        'of the largest closure in 64 KB (4095 states)'))
+
+
+def _check_max_dur(max_dur, what):
+    'max_dur as an int, or None where it is; ValueError unless it is an integer >= 1.'
+    if max_dur is None:
+        return None
+    if int(max_dur) != max_dur or max_dur < 1:
+        raise ValueError(f'{what}: max_dur is an integer >= 1, not {max_dur}')
+    return int(max_dur)
 
 
 def check_segments(beam, max_dur, what='segment_margins'):
@@ -931,16 +931,55 @@ def check_segments(beam, max_dur, what='segment_margins'):
     beam = float(beam)
     if not beam >= 0.:
         raise ValueError(f'{what}: the beam is a number >= 0 (inf: everything), not {beam}')
-    if max_dur is not None:
-        if int(max_dur) != max_dur or max_dur < 1:
-            raise ValueError(f'{what}: max_dur is an integer >= 1, not {max_dur}')
-        max_dur = int(max_dur)
-    return beam, max_dur
+    return beam, _check_max_dur(max_dur, what)
 
 
 def _within(values, beam):
     'values >= -beam, and finite (beam = inf keeps every finite cell).'
     return (values >= -beam) & (values > -float('inf'))
+
+
+def _segment_args(what, batch, arc_cat, init_cat, n_cat, max_dur, seg_map):
+    '''(arcs, inits, n_cat, seg_map) of `segment_margins` / `segment_posteriors`, checked on the
+    host in this order: `max_dur` is given, the categories (`check_arc_categories`), the segment
+    map -- built here when None -- is of the batch's graphs and these categories.'''
+    if max_dur is None:
+        raise ValueError(f'{what}: max_dur is an integer >= 1, not None')
+    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat)
+    n_cat = int(n_cat)
+    if seg_map is None:
+        seg_map = segment_map(batch.source_graphs, arcs.cpu(), inits.cpu(), n_cat)
+    if seg_map.n_cat != n_cat or seg_map.n_graphs != len(batch.n_states):
+        raise ValueError(f'{what}: a segment map of {seg_map.n_graphs} graphs and '
+                         f'{seg_map.n_cat} categories for {len(batch.n_states)} and {n_cat}')
+    return arcs, inits, n_cat, seg_map
+
+
+def _no_entries(batch, max_dur):
+    '(entry_frame, entry_cat, seg) of a batch without utterances.'
+    dev = batch.device
+    return (torch.empty(0, dtype=torch.int64, device=dev),
+            torch.empty(0, dtype=torch.int32, device=dev),
+            torch.empty(0, max_dur, dtype=batch.dtype, device=dev))
+
+
+def _entries_of(at):
+    '(entry_frame int64, entry_cat int32) of the rows `torch.nonzero` found in `starts`.'
+    return at[:, 0].contiguous(), at[:, 1].to(torch.int32)
+
+
+def _entry_rows(batch, entry_frame, max_dur):
+    '''(entry_off [nutt + 1]: where the entries of every utterance begin, seg [n_entries, max_dur]
+    of the batch's dtype, to be filled) for entries sorted by frame.'''
+    return (torch.searchsorted(entry_frame, batch.bufs['frame_off']),
+            torch.empty(len(entry_frame), max_dur, dtype=batch.dtype, device=batch.device))
+
+
+def _segments_where(keep, entry_frame, entry_cat, seg):
+    '(start, end, unit, value float64) of the cells of `seg` that `keep` marks, in row-major order.'
+    at = torch.nonzero(keep)
+    start = entry_frame[at[:, 0]]
+    return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
 
 
 def segment_margins(batch, pc_llhs, arc_cat, init_cat, n_cat, beam, max_dur, seg_map=None):
@@ -959,34 +998,16 @@ def segment_margins(batch, pc_llhs, arc_cat, init_cat, n_cat, beam, max_dur, seg
     waits for the device.  ValueError, before any device work: a negative or NaN beam,
     max_dur < 1, bad categories.'''
     beam, max_dur = check_segments(beam, max_dur)
-    if max_dur is None:
-        raise ValueError('segment_margins: max_dur is an integer >= 1, not None')
-    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat)
-    n_cat = int(n_cat)
-    if seg_map is None:
-        seg_map = segment_map(batch.source_graphs, arcs.cpu(), inits.cpu(), n_cat)
-    if seg_map.n_cat != n_cat or seg_map.n_graphs != len(batch.n_states):
-        raise ValueError(f'segment_margins: a segment map of {seg_map.n_graphs} graphs and '
-                         f'{seg_map.n_cat} categories for {len(batch.n_states)} and {n_cat}')
+    arcs, inits, n_cat, seg_map = _segment_args('segment_margins', batch, arc_cat, init_cat,
+                                                n_cat, max_dur, seg_map)
     dev, dt = batch.device, batch.dtype
     segments_route(batch, n_cat, seg_map.max_closure)
     best = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
     starts = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev)
     if batch.nutt == 0:
-        return best, starts, torch.empty(0, dtype=torch.int64, device=dev), \
-            torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, max_dur, dtype=dt, device=dev)
+        return (best, starts) + _no_entries(batch, max_dur)
     dcode = _hip.dtype_code(dt)
-    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
-    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
-    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
-    if arcs.device.type != 'cuda':
-        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
-    if inits.device.type != 'cuda':
-        host['inits'] = inits
-    up = _hip.upload(host, dev)
-    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
-    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
-                       up['state_off'].data_ptr())
+    amap, keep = _arc_map(batch, arcs, inits)               # (`keep` lives until the call)
     extra = _hip.lib().beer_hmm_segments_scratch_doubles(dcode, batch.ref())
     trellis = torch.empty(2 * batch.n_elems + extra + 1, dtype=torch.float64, device=dev)
     d, x, ws = trellis[:batch.n_elems], trellis[batch.n_elems:2 * batch.n_elems], \
@@ -994,39 +1015,32 @@ def segment_margins(batch, pc_llhs, arc_cat, init_cat, n_cat, beam, max_dur, seg
     _hip.call('beer_hmm_segment_trellis', dcode, batch.ref(), _hip.ptr(pc_llhs),
               ctypes.byref(amap), n_cat, _hip.ptr(d), _hip.ptr(x), _hip.ptr(ws), _hip.ptr(starts),
               _hip.ptr(best))
-    at = torch.nonzero(_within(starts, beam))               # (row-major; waits for the device)
-    entry_frame = at[:, 0].contiguous()
-    entry_cat = at[:, 1].to(torch.int32)
-    entry_off = torch.searchsorted(entry_frame, batch.bufs['frame_off'])
-    seg = torch.empty(len(at), max_dur, dtype=dt, device=dev)
+    # (row-major; waits for the device)
+    entry_frame, entry_cat = _entries_of(torch.nonzero(_within(starts, beam)))
+    entry_off, seg = _entry_rows(batch, entry_frame, max_dur)
     _hip.call('beer_hmm_segment_margins', dcode, batch.ref(), _hip.ptr(pc_llhs),
               ctypes.byref(seg_map.struct(dev)), n_cat, _hip.ptr(d), _hip.ptr(x), _hip.ptr(best),
-              _hip.ptr(entry_frame), _hip.ptr(entry_cat), _hip.ptr(entry_off), len(at), max_dur,
-              _hip.ptr(seg))
+              _hip.ptr(entry_frame), _hip.ptr(entry_cat), _hip.ptr(entry_off), len(entry_frame),
+              max_dur, _hip.ptr(seg))
     return best, starts, entry_frame, entry_cat, seg
 
 
 def segments_within(entry_frame, entry_cat, seg, beam):
     '''(start int64, end int64, unit int32, margin float64) of the cells of `segment_margins`'
     `seg` that are >= -beam, sorted by (start, unit, end); the frames indexed as `entry_frame`.'''
-    at = torch.nonzero(_within(seg, float(beam)))
-    start = entry_frame[at[:, 0]]
-    return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
+    return _segments_where(_within(seg, float(beam)), entry_frame, entry_cat, seg)
 
 
 def segposts_route(batch, n_cat, max_closure=0):
     '''beer_hmm_segposts_route: the form `segment_posteriors` runs on (the trellis kernel's arcs
     and bins in LDS or not, and in the low bits the team size of the expand kernel,
     `_hip.segposts_team`); HipInvalid where it refuses.'''
-    route = _hip.lib().beer_hmm_segposts_route(_hip.dtype_code(batch.dtype), batch.ref(),
-                                               int(n_cat), int(max_closure))
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'segment_posteriors: {n_cat} categories with closures of up to {max_closure} states '
-            f'on graphs of up to {batch.struct.max_states} states: at least one category, two '
-            "fp64 rows of the graph in the CU's 160 KB of LDS (about 10000 states), and four fp64 "
-            'rows of the largest closure in 64 KB (2046 states)')
-    return route
+    args = (int(n_cat), int(max_closure))
+    return _route_or_refuse('beer_hmm_segposts_route', batch, args, lambda: (
+        f'segment_posteriors: {n_cat} categories with closures of up to {max_closure} states '
+        f'on graphs of up to {batch.struct.max_states} states: at least one category, two '
+        "fp64 rows of the graph in the CU's 160 KB of LDS (about 10000 states), and four fp64 "
+        'rows of the largest closure in 64 KB (2046 states)'))
 
 
 def check_segment_posteriors(min_post, max_dur, what='segment_posteriors'):
@@ -1035,11 +1049,7 @@ def check_segment_posteriors(min_post, max_dur, what='segment_posteriors'):
     min_post = float(min_post)
     if not 0. <= min_post <= 1.:
         raise ValueError(f'{what}: min_post is a probability in [0, 1], not {min_post}')
-    if max_dur is not None:
-        if int(max_dur) != max_dur or max_dur < 1:
-            raise ValueError(f'{what}: max_dur is an integer >= 1, not {max_dur}')
-        max_dur = int(max_dur)
-    return min_post, max_dur
+    return min_post, _check_max_dur(max_dur, what)
 
 
 def _above(values, min_post):
@@ -1086,15 +1096,8 @@ def segment_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, min_post, max_d
     categories, a segment map of another shape, unsorted or out-of-range entries.'''
     what = 'segment_posteriors'
     min_post, max_dur = check_segment_posteriors(min_post, max_dur)
-    if max_dur is None:
-        raise ValueError(f'{what}: max_dur is an integer >= 1, not None')
-    arcs, inits = check_arc_categories(batch.n_arcs, batch.n_states, arc_cat, init_cat, n_cat)
-    n_cat = int(n_cat)
-    if seg_map is None:
-        seg_map = segment_map(batch.source_graphs, arcs.cpu(), inits.cpu(), n_cat)
-    if seg_map.n_cat != n_cat or seg_map.n_graphs != len(batch.n_states):
-        raise ValueError(f'{what}: a segment map of {seg_map.n_graphs} graphs and '
-                         f'{seg_map.n_cat} categories for {len(batch.n_states)} and {n_cat}')
+    arcs, inits, n_cat, seg_map = _segment_args(what, batch, arc_cat, init_cat, n_cat, max_dur,
+                                                seg_map)
     if entries is not None:
         entries = _check_entries(entries, batch.n_frames, n_cat, what)
     dev, dt = batch.device, batch.dtype
@@ -1102,20 +1105,9 @@ def segment_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, min_post, max_d
     evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
     starts = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev)
     if batch.nutt == 0:
-        return evidence, starts, torch.empty(0, dtype=torch.int64, device=dev), \
-            torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, max_dur, dtype=dt, device=dev)
+        return (evidence, starts) + _no_entries(batch, max_dur)
     dcode = _hip.dtype_code(dt)
-    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
-    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
-    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
-    if arcs.device.type != 'cuda':
-        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
-    if inits.device.type != 'cuda':
-        host['inits'] = inits
-    up = _hip.upload(host, dev)
-    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
-    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
-                       up['state_off'].data_ptr())
+    amap, keep = _arc_map(batch, arcs, inits)               # (`keep` lives until the call)
     # the two trellises and the normalisers (an element more: no pointer is NULL)
     trellis = torch.empty(2 * batch.n_elems + batch.n_frames + 1, dtype=torch.float64, device=dev)
     alpha, y, norm = trellis[:batch.n_elems], trellis[batch.n_elems:2 * batch.n_elems], \
@@ -1124,13 +1116,11 @@ def segment_posteriors(batch, pc_llhs, arc_cat, init_cat, n_cat, min_post, max_d
               ctypes.byref(amap), n_cat, _hip.ptr(alpha), _hip.ptr(y), _hip.ptr(norm),
               _hip.ptr(starts), _hip.ptr(evidence))
     if entries is None:
-        at = torch.nonzero(_above(starts, min_post))        # (row-major; waits for the device)
-        entry_frame = at[:, 0].contiguous()
-        entry_cat = at[:, 1].to(torch.int32)
+        # (row-major; waits for the device)
+        entry_frame, entry_cat = _entries_of(torch.nonzero(_above(starts, min_post)))
     else:
         entry_frame, entry_cat = (e.to(dev).contiguous() for e in entries)
-    entry_off = torch.searchsorted(entry_frame, batch.bufs['frame_off'])
-    seg = torch.empty(len(entry_frame), max_dur, dtype=dt, device=dev)
+    entry_off, seg = _entry_rows(batch, entry_frame, max_dur)
     _hip.call('beer_hmm_segment_posteriors', dcode, batch.ref(), _hip.ptr(pc_llhs),
               ctypes.byref(seg_map.struct(dev)), n_cat, _hip.ptr(alpha), _hip.ptr(y),
               _hip.ptr(norm), _hip.ptr(evidence), _hip.ptr(entry_frame), _hip.ptr(entry_cat),
@@ -1142,9 +1132,7 @@ def segments_above(entry_frame, entry_cat, seg, min_post):
     '''(start int64, end int64, unit int32, post float64) of the cells of `segment_posteriors`'
     `seg` that are >= min_post and > 0, sorted by (start, unit, end); the frames indexed as
     `entry_frame`.'''
-    at = torch.nonzero(_above(seg, float(min_post)))
-    start = entry_frame[at[:, 0]]
-    return start, start + at[:, 1], entry_cat[at[:, 0]], seg[at[:, 0], at[:, 1]].double()
+    return _segments_where(_above(seg, float(min_post)), entry_frame, entry_cat, seg)
 
 
 def check_durations(log_dur, S_total, leave_w=None):
@@ -1174,13 +1162,10 @@ def duration_route(batch, D):
     '''beer_hsmm_route: the form the explicit-duration kernels take for this batch and D (the
     team of lanes per state, ring in LDS or not, low-degree images or the full CSR); HipInvalid
     -- naming the limit -- where they refuse.'''
-    route = _hip.lib().beer_hsmm_route(_hip.dtype_code(batch.dtype), batch.ref(), int(D))
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'explicit durations: D = {D} on graphs of up to {batch.struct.max_states} states: at '
-            f'most {_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
-            f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)')
-    return route
+    return _route_or_refuse('beer_hsmm_route', batch, (int(D),), lambda: (
+        f'explicit durations: D = {D} on graphs of up to {batch.struct.max_states} states: at '
+        f'most {_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
+        f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)'))
 
 
 def _duration_args(batch, pc_llhs, log_dur, leave_w, scratch='beer_hsmm_scratch_doubles'):
@@ -1201,6 +1186,22 @@ def _duration_args(batch, pc_llhs, log_dur, leave_w, scratch='beer_hsmm_scratch_
     return D, S_total, log_dur, leave_w, ws
 
 
+def _duration_outputs(batch, S_total, D, want_counts):
+    '''(gamma packed, evidence [nutt] fp64, dur_counts [S_total, D], entry_sum [S], gamma0_sum [S])
+    of an explicit-duration forward-backward: the counts zero-filled fp64, None unless
+    `want_counts`, the last two also None unless the batch shares one graph.'''
+    dev = batch.device
+    gamma = torch.empty(batch.n_elems, dtype=batch.dtype, device=dev)
+    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
+    counts = entry = g0 = None
+    if want_counts:
+        counts = torch.zeros(S_total, D, dtype=torch.float64, device=dev)
+        if batch.shared_graph:
+            entry = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+            g0 = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+    return gamma, evidence, counts, entry, g0
+
+
 def duration_forward_backward(batch, pc_llhs, log_dur, leave_w=None, want_counts=True):
     '''Forward-backward over (state, duration) (`beer_hsmm_forward_backward`): (gamma packed,
     evidence [nutt] fp64, dur_counts [S_total, D] fp64 or None, entry_sum [S] fp64 or None,
@@ -1209,18 +1210,11 @@ def duration_forward_backward(batch, pc_llhs, log_dur, leave_w=None, want_counts
     `want_counts`: the duration counts and -- when the batch shares one graph -- the segment
     entries per state from the second frame on and in the first frame.'''
     D, S_total, log_dur, leave_w, ws = _duration_args(batch, pc_llhs, log_dur, leave_w)
-    dt, dev = batch.dtype, batch.device
-    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
-    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
-    counts = entry = g0 = None
-    if want_counts:
-        counts = torch.zeros(S_total, D, dtype=torch.float64, device=dev)
-        if batch.shared_graph:
-            entry = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
-            g0 = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
-    _hip.call('beer_hsmm_forward_backward', _hip.dtype_code(dt), batch.ref(), _hip.ptr(pc_llhs),
-              _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, _hip.ptr(ws), _hip.ptr(gamma),
-              _hip.ptr(evidence), _hip.ptr(counts), _hip.ptr(entry), _hip.ptr(g0))
+    gamma, evidence, counts, entry, g0 = _duration_outputs(batch, S_total, D, want_counts)
+    _hip.call('beer_hsmm_forward_backward', _hip.dtype_code(batch.dtype), batch.ref(),
+              _hip.ptr(pc_llhs), _hip.ptr(log_dur), _hip.ptr(leave_w), D, S_total, _hip.ptr(ws),
+              _hip.ptr(gamma), _hip.ptr(evidence), _hip.ptr(counts), _hip.ptr(entry),
+              _hip.ptr(g0))
     return gamma, evidence, counts, entry, g0
 
 
@@ -1228,15 +1222,12 @@ def duration_arcs_route(batch, D, n_cat, per_frame=True):
     '''beer_hsmm_arcs_route: the form `duration_arc_posteriors` takes (team, ring and the two bin
     bits `_hip.HSMM_ARCS_FRAME_LDS` / `_hip.HSMM_ARCS_UTT_LDS`); HipInvalid -- naming the limit --
     where it refuses.'''
-    route = _hip.lib().beer_hsmm_arcs_route(_hip.dtype_code(batch.dtype), batch.ref(), int(D),
-                                            int(n_cat), 1 if per_frame else 0)
-    if route == _hip.EINVAL:
-        raise _hip.HipInvalid(
-            f'explicit durations: {n_cat} arc categories with D = {D} on graphs of up to '
-            f'{batch.struct.max_states} states: at least one category, at most '
-            f'{_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
-            f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)')
-    return route
+    args = (int(D), int(n_cat), 1 if per_frame else 0)
+    return _route_or_refuse('beer_hsmm_arcs_route', batch, args, lambda: (
+        f'explicit durations: {n_cat} arc categories with D = {D} on graphs of up to '
+        f'{batch.struct.max_states} states: at least one category, at most '
+        f'{_hip.HSMM_MAX_DUR} frames a stay (BEER_HSMM_MAX_DUR) and '
+        f'{_hip.HSMM_MAX_STATES} states a graph (BEER_HSMM_MAX_STATES)'))
 
 
 def duration_arc_posteriors(batch, pc_llhs, log_dur, leave_w, arc_cat, init_cat, n_cat,
@@ -1260,25 +1251,8 @@ def duration_arc_posteriors(batch, pc_llhs, log_dur, leave_w, arc_cat, init_cat,
     duration_arcs_route(batch, D, n_cat, per_frame)
     dt, dev = batch.dtype, batch.device
     dcode = _hip.dtype_code(dt)
-    arc_off = np.concatenate([[0], np.cumsum(batch.n_arcs)[:-1]]).astype(np.int64)
-    state_off = np.concatenate([[0], np.cumsum(batch.n_states)[:-1]]).astype(np.int64)
-    host = {'arc_off': torch.from_numpy(arc_off), 'state_off': torch.from_numpy(state_off)}
-    if arcs.device.type != 'cuda':
-        host['arcs'] = arcs if arcs.numel() else torch.zeros(1, dtype=torch.int32)
-    if inits.device.type != 'cuda':
-        host['inits'] = inits
-    up = _hip.upload(host, dev)
-    arcs, inits = up.get('arcs', arcs), up.get('inits', inits)
-    amap = _hip.ArcMap(arcs.data_ptr(), inits.data_ptr(), up['arc_off'].data_ptr(),
-                       up['state_off'].data_ptr())
-    gamma = torch.empty(batch.n_elems, dtype=dt, device=dev)
-    evidence = torch.empty(batch.nutt, dtype=torch.float64, device=dev)
-    counts = entry = g0 = None
-    if want_counts:
-        counts = torch.zeros(S_total, D, dtype=torch.float64, device=dev)
-        if batch.shared_graph:
-            entry = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
-            g0 = torch.zeros(batch.n_states[0], dtype=torch.float64, device=dev)
+    amap, keep = _arc_map(batch, arcs, inits)               # (`keep` lives until the call)
+    gamma, evidence, counts, entry, g0 = _duration_outputs(batch, S_total, D, want_counts)
     frame = torch.empty(batch.n_frames, n_cat, dtype=dt, device=dev) if per_frame else None
     utt = torch.empty(batch.nutt, n_cat, dtype=torch.float64, device=dev) if per_utt else None
     tot = torch.zeros(n_cat, dtype=torch.float64, device=dev) if total else None

@@ -705,6 +705,59 @@ def _no_durations(model, what):
         model._refuse_durations(what)
 
 
+def _shard_args(what, utterances, inference_graphs):
+    '''The utterances of a shard as `pack_utterances` takes them -- a packed (X, lengths) pair as
+    it is, anything else as a list -- once there is one inference graph per utterance (ValueError
+    if not).'''
+    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
+        isinstance(utterances[0], torch.Tensor)
+    if not packed:
+        utterances = list(utterances)
+    if inference_graphs is not None:
+        nutt = len(utterances[1]) if packed else len(utterances)
+        if len(inference_graphs) != nutt:
+            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
+                             'utterances')
+    return utterances
+
+
+def _unit_shard(what, model):
+    '''(n_units, categories) of a phone loop, ValueError for a model without units:
+    `categories(batch)` are the unit-start categories of a sub-batch's distinct graphs, (one
+    arc_cat per graph, one init_cat per graph), every graph's built once for as long as the
+    caller keeps the function.'''
+    if not hasattr(model, 'start_pdf'):
+        raise ValueError(f'{what}: a phone loop (a model with units), not '
+                         f'{type(model).__name__}')
+    cats = {}
+
+    def categories(batch):
+        for graph in batch.distinct_graphs:
+            if id(graph) not in cats:
+                cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+        pairs = [cats[id(graph)] for graph in batch.distinct_graphs]
+        return [p[0] for p in pairs], [p[1] for p in pairs]
+
+    return len(model.start_pdf), categories
+
+
+def _split_segments(batch, run_lengths, start, end, unit, value):
+    '''The segments of a sub-batch, sorted by start frame, as one (start, end, unit, value) per
+    utterance, the frames counted from the utterance's first.'''
+    first = batch.bufs['frame_off']
+    utt = torch.searchsorted(first[1:].contiguous(), start, right=True)
+    counts = torch.bincount(utt, minlength=len(run_lengths)).tolist()
+    start, end = start - first[utt], end - first[utt]
+    return list(zip(*(torch.split(v, counts) for v in
+                      (start.to(torch.int32), end.to(torch.int32), unit, value))))
+
+
+def _cat_or_empty(parts, *shape):
+    'The float64 results of the sub-batches as one tensor; [0, *shape] for a shard of none.'
+    return torch.cat(parts) if parts else \
+        torch.zeros(0, *shape, dtype=torch.float64, device=_hip.require_device())
+
+
 def decode_batch(model, utterances, inference_graphs=None, scale=1., max_frames=1 << 20,
                  predictive=False):
     '''Viterbi pdf-id paths for a shard: list of int64 tensors, one per
@@ -768,27 +821,19 @@ def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_f
     `predictive`: the emissions are the posterior-predictive densities (held-out likelihood);
     the arcs of the graphs are used as they stand (fixed, or E[ln a] / E[ln pi] where
     learned), as in `HMM.log_evidence`.'''
-    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
-        isinstance(utterances[0], torch.Tensor)
-    if not packed:
-        utterances = list(utterances)
-    if inference_graphs is not None:
-        nutt = len(utterances[1]) if packed else len(utterances)
-        if len(inference_graphs) != nutt:
-            raise ValueError(f'log_evidence_batch: {len(inference_graphs)} inference graphs for '
-                             f'{nutt} utterances')
+    utterances = _shard_args('log_evidence_batch', utterances, inference_graphs)
     totals, frames = [], []
     if getattr(model, 'durations', None) is not None:
         if per_frame:
             model._refuse_durations('log_evidence_batch(per_frame=True)')
         tables = model._duration_tables()
+        # (a packed shard is still the tuple it came as; anything else is a list by now)
+        trellis = 16 + utterances[0].element_size() if isinstance(utterances, tuple) else 24
         for batch, pc_llhs, _ in _search_batches(model, utterances, inference_graphs, scale,
-                                                 max_frames, 16, 16 + utterances[0].element_size()
-                                                 if packed else 24, predictive=predictive):
+                                                 max_frames, 16, trellis, predictive=predictive):
             totals.append(hk.duration_forward_backward(batch, pc_llhs, *tables,
                                                        want_counts=False)[1])
-        return torch.cat(totals) if totals else \
-            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())
+        return _cat_or_empty(totals)
     # decode_batch's scratch without the trellis; a float64 per frame besides
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 if per_frame else 0, 0,
@@ -797,8 +842,7 @@ def log_evidence_batch(model, utterances, inference_graphs=None, scale=1., per_f
         totals.append(utt)
         if per_frame:
             frames += list(torch.split(frame, run_lengths))
-    total = torch.cat(totals) if totals else \
-        torch.zeros(0, dtype=torch.float64, device=_hip.require_device())
+    total = _cat_or_empty(totals)
     return (total, frames) if per_frame else total
 
 
@@ -837,46 +881,20 @@ def unit_segments_batch(model, utterances, beam=10., max_dur=None, inference_gra
     what = 'unit_segments_batch'
     beam, max_dur = hk.check_segments(beam, max_dur, what)
     _no_durations(model, what)
-    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
-        isinstance(utterances[0], torch.Tensor)
-    if not packed:
-        utterances = list(utterances)
-    if inference_graphs is not None:
-        nutt = len(utterances[1]) if packed else len(utterances)
-        if len(inference_graphs) != nutt:
-            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
-                             'utterances')
-    if not hasattr(model, 'start_pdf'):
-        raise ValueError(f'{what}: a phone loop (a model with units), not '
-                         f'{type(model).__name__}')
-    n_units = len(model.start_pdf)
-    cats = {}                       # the categories of every distinct graph, built once per call
-
-    def categories(graph):
-        if id(graph) not in cats:
-            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
-        return cats[id(graph)]
-
+    utterances = _shard_args(what, utterances, inference_graphs)
+    n_units, categories = _unit_shard(what, model)
     out, bests = [], []
     # decode_batch's scratch with two fp64 trellises (d and X) in place of the back-pointers; a
     # row of start margins per frame besides (sized for float64).  The segment rows of the
     # entries within the beam come on top: n_entries * max_dur values.
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 + 8 * n_units, 16):
-        pairs = [categories(g) for g in batch.distinct_graphs]
         dur = max(max(run_lengths), 1) if max_dur is None else max_dur
-        best, _, frame, unit, seg = hk.segment_margins(
-            batch, pc_llhs, [p[0] for p in pairs], [p[1] for p in pairs], n_units, beam, dur)
+        best, _, frame, unit, seg = hk.segment_margins(batch, pc_llhs, *categories(batch),
+                                                       n_units, beam, dur)
         bests.append(best)
-        start, end, unit, margin = hk.segments_within(frame, unit, seg, beam)
-        first = batch.bufs['frame_off']
-        utt = torch.searchsorted(first[1:].contiguous(), start, right=True)
-        counts = torch.bincount(utt, minlength=len(run_lengths)).tolist()
-        start, end = start - first[utt], end - first[utt]
-        out += list(zip(*(torch.split(v, counts) for v in
-                          (start.to(torch.int32), end.to(torch.int32), unit, margin))))
-    return (torch.cat(bests) if bests else
-            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
+        out += _split_segments(batch, run_lengths, *hk.segments_within(frame, unit, seg, beam))
+    return _cat_or_empty(bests), out
 
 
 def _segment_posteriors_batches(what, model, utterances, min_post, max_dur, inference_graphs,
@@ -884,35 +902,16 @@ def _segment_posteriors_batches(what, model, utterances, min_post, max_dur, infe
     '''(batch, lengths, `hk.segment_posteriors`' outputs) per sub-batch of a shard, under the
     unit-start categories; the arguments are checked before the first sub-batch is built.'''
     _no_durations(model, what)
-    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
-        isinstance(utterances[0], torch.Tensor)
-    if not packed:
-        utterances = list(utterances)
-    if inference_graphs is not None:
-        nutt = len(utterances[1]) if packed else len(utterances)
-        if len(inference_graphs) != nutt:
-            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
-                             'utterances')
-    if not hasattr(model, 'start_pdf'):
-        raise ValueError(f'{what}: a phone loop (a model with units), not '
-                         f'{type(model).__name__}')
-    n_units = len(model.start_pdf)
-    cats = {}                       # the categories of every distinct graph, built once per call
-
-    def categories(graph):
-        if id(graph) not in cats:
-            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
-        return cats[id(graph)]
-
+    utterances = _shard_args(what, utterances, inference_graphs)
+    n_units, categories = _unit_shard(what, model)
     # decode_batch's scratch with two fp64 trellises (â and Y) in place of the back-pointers; a
     # normaliser and a row of start posteriors per frame besides (sized for float64).  The
     # segment rows of the entries come on top: n_entries * max_dur values.
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 + 8 * n_units, 16):
-        pairs = [categories(g) for g in batch.distinct_graphs]
         dur = max(max(run_lengths), 1) if max_dur is None else max_dur
-        yield batch, run_lengths, hk.segment_posteriors(
-            batch, pc_llhs, [p[0] for p in pairs], [p[1] for p in pairs], n_units, min_post, dur)
+        yield batch, run_lengths, hk.segment_posteriors(batch, pc_llhs, *categories(batch),
+                                                        n_units, min_post, dur)
 
 
 def unit_segment_posteriors_batch(model, utterances, min_post=1e-3, max_dur=None,
@@ -928,15 +927,8 @@ def unit_segment_posteriors_batch(model, utterances, min_post=1e-3, max_dur=None
     for batch, run_lengths, (evidence, _, frame, unit, seg) in _segment_posteriors_batches(
             what, model, utterances, min_post, max_dur, inference_graphs, scale, max_frames):
         totals.append(evidence)
-        start, end, unit, post = hk.segments_above(frame, unit, seg, min_post)
-        first = batch.bufs['frame_off']
-        utt = torch.searchsorted(first[1:].contiguous(), start, right=True)
-        counts = torch.bincount(utt, minlength=len(run_lengths)).tolist()
-        start, end = start - first[utt], end - first[utt]
-        out += list(zip(*(torch.split(v, counts) for v in
-                          (start.to(torch.int32), end.to(torch.int32), unit, post))))
-    return (torch.cat(totals) if totals else
-            torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
+        out += _split_segments(batch, run_lengths, *hk.segments_above(frame, unit, seg, min_post))
+    return _cat_or_empty(totals), out
 
 
 def unit_durations_batch(model, utterances, max_dur, inference_graphs=None, scale=1.,
@@ -965,53 +957,30 @@ def unit_durations_batch(model, utterances, max_dur, inference_graphs=None, scal
 def _unit_arcs_batch(what, model, utterances, inference_graphs, scale, max_frames, per_frame,
                      margins=False):
     _no_durations(model, what)
-    packed = isinstance(utterances, tuple) and len(utterances) == 2 and \
-        isinstance(utterances[0], torch.Tensor)
-    if not packed:
-        utterances = list(utterances)
-    if inference_graphs is not None:
-        nutt = len(utterances[1]) if packed else len(utterances)
-        if len(inference_graphs) != nutt:
-            raise ValueError(f'{what}: {len(inference_graphs)} inference graphs for {nutt} '
-                             'utterances')
-    if not hasattr(model, 'start_pdf'):
-        raise ValueError(f'{what}: a phone loop (a model with units), not '
-                         f'{type(model).__name__}')
-    n_units = len(model.start_pdf)
-    cats = {}                       # the categories of every distinct graph, built once per call
-
-    def categories(graph):
-        if id(graph) not in cats:
-            cats[id(graph)] = unit_start_categories(graph, model.start_pdf, model.end_pdf)
-        return cats[id(graph)]
-
+    utterances = _shard_args(what, utterances, inference_graphs)
+    n_units, categories = _unit_shard(what, model)
     out, bests = [], []
     # decode_batch's scratch with the fp64 trellis in place of the back-pointers; a normaliser
     # and the output row per frame besides (sized for float64)
     row = 8 * n_units if per_frame else 0
     for batch, pc_llhs, run_lengths in _search_batches(model, utterances, inference_graphs, scale,
                                                        max_frames, 8 + row, 8):
-        pairs = [categories(g) for g in batch.distinct_graphs]
         if margins:
-            best, _, frame, utt = hk.max_marginals(batch, pc_llhs, [p[0] for p in pairs],
-                                                   [p[1] for p in pairs], n_units, states=False,
-                                                   per_frame=True)
+            best, _, frame, utt = hk.max_marginals(batch, pc_llhs, *categories(batch), n_units,
+                                                   states=False, per_frame=True)
             bests.append(best)
         else:
-            frame, utt = hk.arc_posteriors(batch, pc_llhs, [p[0] for p in pairs],
-                                           [p[1] for p in pairs], n_units, per_frame=per_frame,
-                                           per_utt=not per_frame)
+            frame, utt = hk.arc_posteriors(batch, pc_llhs, *categories(batch), n_units,
+                                           per_frame=per_frame, per_utt=not per_frame)
         if per_frame:
             out += list(torch.split(frame, run_lengths))
         else:
             out.append(utt)
     if margins:
-        return (torch.cat(bests) if bests else
-                torch.zeros(0, dtype=torch.float64, device=_hip.require_device())), out
+        return _cat_or_empty(bests), out
     if per_frame:
         return out
-    return torch.cat(out) if out else \
-        torch.zeros(0, n_units, dtype=torch.float64, device=_hip.require_device())
+    return _cat_or_empty(out, n_units)
 
 
 def _paths_batch(model, utterances, inference_graphs, scale, max_frames, extra_bytes, search,

@@ -639,19 +639,40 @@ class HMM(DiscreteLatentModel):
             return self._emissions().predictive_log_likelihood(stats)
         return self._emissions().expected_log_likelihood(stats)
 
+    def _search_batch(self, data, inference_graph, predictive=False):
+        '''(batch, pc_all, n_frames) of a search over one utterance: the `HmmBatch` of `data` on
+        the inference graph (None: the model's own), the emission log-likelihoods by pdf id
+        [n_frames, S_total] and its length.  A graph bound to the model's learned transitions
+        gets E[ln a] on its arcs first.  Host-side argument checks come before this call.'''
+        graph = self.graph if inference_graph is None else inference_graph
+        stats = self.sufficient_statistics(data)
+        pc_all = self._emission_llhs(stats, predictive)
+        if getattr(getattr(graph, '_set', None), 'is_bound', False):
+            self._bound_set(graph).refresh(pc_all.dtype)
+        return self._batch_of_one(graph, len(stats), pc_all.dtype), pc_all, len(stats)
+
+    def _search_input(self, data, inference_graph, scale, predictive=False):
+        '''(batch, pc_llhs, n_frames): `_search_batch` with the log-likelihoods gathered by state
+        and multiplied by `scale`, packed as the HMM kernels read them.'''
+        batch, pc_all, n_frames = self._search_batch(data, inference_graph, predictive)
+        return batch, hk.gather(batch, pc_all, scale), n_frames
+
+    def _checked_categories(self, inference_graph, arc_cat, init_cat, n_cat, per_frame=True,
+                            per_utt=False):
+        '''The categories of the arcs and states of one graph as `hk.arc_posteriors` takes them,
+        checked on the host (`hk.check_arc_categories`).'''
+        graph = self.graph if inference_graph is None else inference_graph
+        src, _ = graph.out_arcs()
+        return hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
+                                       per_frame, per_utt)
+
     def decode(self, data, inference_graph=None, scale=1., predictive=False):
         '''Viterbi path mapped to pdf ids, LongTensor on the host (hmm.py:105-114).
         `predictive` (not in the reference): the emissions are the posterior-predictive
         densities (`predictive_log_likelihood` of the emission model) in place of the expected
         log-likelihoods.  The arcs of the graph are used as they stand -- fixed log-probabilities,
         or E[ln a] and E[ln pi] where they are learned: predictive arc weights are not formed.'''
-        graph = self.graph if inference_graph is None else inference_graph
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emission_llhs(stats, predictive)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        pc_llhs = hk.gather(batch, pc_all, scale)
+        batch, pc_llhs, _ = self._search_input(data, inference_graph, scale, predictive)
         if self.durations is not None:
             return hk.duration_viterbi(batch, pc_llhs, *self._duration_tables(),
                                        map_pdf=True)[0].cpu()
@@ -666,13 +687,7 @@ class HMM(DiscreteLatentModel):
         reference.  Otherwise as `decode`.'''
         self._refuse_durations('decode_nbest')
         k = hk.check_nbest(k, 'decode_nbest')
-        graph = self.graph if inference_graph is None else inference_graph
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        pc_llhs = hk.gather(batch, pc_all, scale)
+        batch, pc_llhs, _ = self._search_input(data, inference_graph, scale)
         paths, scores = hk.viterbi_nbest(batch, pc_llhs, k, map_pdf=True)
         return paths.cpu(), scores[0].cpu()
 
@@ -681,13 +696,7 @@ class HMM(DiscreteLatentModel):
         [nsamples, T] on the host.  `generator`: a device torch.Generator for the uniforms
         (default: the device's global one).  Otherwise as `decode`.'''
         self._refuse_durations('sample_path')
-        graph = self.graph if inference_graph is None else inference_graph
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        pc_llhs = hk.gather(batch, pc_all, scale)
+        batch, pc_llhs, _ = self._search_input(data, inference_graph, scale)
         return hk.sample_paths(batch, pc_llhs, nsamples=nsamples, generator=generator,
                                map_pdf=True).cpu()
 
@@ -700,12 +709,8 @@ class HMM(DiscreteLatentModel):
         the emissions are the posterior-predictive densities -- the held-out likelihood of a
         Bayesian model, never below the default's value; the arcs stay as they are (fixed, or
         E[ln a] / E[ln pi] where learned).  Otherwise as `decode`.'''
-        graph = self.graph if inference_graph is None else inference_graph
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emission_llhs(stats, predictive)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
+        # (the gather is launched here, not in `_search_input`: the refusal comes before it)
+        batch, pc_all, _ = self._search_batch(data, inference_graph, predictive)
         if self.durations is not None:
             if per_frame:
                 self._refuse_durations('log_evidence(per_frame=True)')
@@ -724,17 +729,11 @@ class HMM(DiscreteLatentModel):
         the graph's states; entries are in [0, n_cat) or -1 (count nothing).  Not in the
         reference.  Otherwise as `decode`.'''
         self._refuse_durations('arc_posteriors')
-        graph = self.graph if inference_graph is None else inference_graph
-        src, _ = graph.out_arcs()
-        cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
-                                       per_frame, not per_frame)
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        frame, utt = hk.arc_posteriors(batch, hk.gather(batch, pc_all, scale), *cats, n_cat,
-                                       per_frame=per_frame, per_utt=not per_frame)
+        cats = self._checked_categories(inference_graph, arc_cat, init_cat, n_cat, per_frame,
+                                        not per_frame)
+        batch, pc_llhs, _ = self._search_input(data, inference_graph, scale)
+        frame, utt = hk.arc_posteriors(batch, pc_llhs, *cats, n_cat, per_frame=per_frame,
+                                       per_utt=not per_frame)
         return frame if per_frame else utt[0]
 
     def max_marginals(self, data, inference_graph=None, scale=1.):
@@ -743,14 +742,9 @@ class HMM(DiscreteLatentModel):
         (`hmm_kernels.max_marginals`): 0 along `decode`'s path, negative off it, -inf where no
         path passes.  Not in the reference.  Otherwise as `decode`.'''
         self._refuse_durations('max_marginals')
-        graph = self.graph if inference_graph is None else inference_graph
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        best, state, _, _ = hk.max_marginals(batch, hk.gather(batch, pc_all, scale))
-        return best[0], state.view(len(stats), -1)
+        batch, pc_llhs, n_frames = self._search_input(data, inference_graph, scale)
+        best, state, _, _ = hk.max_marginals(batch, pc_llhs)
+        return best[0], state.view(n_frames, -1)
 
     def arc_max_marginals(self, data, arc_cat, init_cat, n_cat, inference_graph=None, scale=1.,
                           per_frame=True):
@@ -762,18 +756,11 @@ class HMM(DiscreteLatentModel):
         path.  The categories are those of `arc_posteriors`.  Not in the reference.  Otherwise
         as `decode`.'''
         self._refuse_durations('max_marginals')
-        graph = self.graph if inference_graph is None else inference_graph
-        src, _ = graph.out_arcs()
-        cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_cat,
-                                       per_frame, not per_frame)
-        stats = self.sufficient_statistics(data)
-        pc_all = self._emissions().expected_log_likelihood(stats)
-        if getattr(getattr(graph, '_set', None), 'is_bound', False):
-            self._bound_set(graph).refresh(pc_all.dtype)
-        batch = self._batch_of_one(graph, len(stats), pc_all.dtype)
-        best, _, frame, utt = hk.max_marginals(batch, hk.gather(batch, pc_all, scale), *cats,
-                                               n_cat, states=False, per_frame=per_frame,
-                                               per_utt=not per_frame)
+        cats = self._checked_categories(inference_graph, arc_cat, init_cat, n_cat, per_frame,
+                                        not per_frame)
+        batch, pc_llhs, _ = self._search_input(data, inference_graph, scale)
+        best, _, frame, utt = hk.max_marginals(batch, pc_llhs, *cats, n_cat, states=False,
+                                               per_frame=per_frame, per_utt=not per_frame)
         return best[0], (frame if per_frame else utt[0])
 
     def posteriors(self, data, inference_graph=None, scale=1.0):
@@ -841,6 +828,14 @@ def _unit_start_margins(model, data, inference_graph=None, scale=1.):
                                    inference_graph=inference_graph, scale=scale)
 
 
+def _checked_unit_categories(model, inference_graph):
+    '(the unit-start categories of the graph, checked as `hk.segment_margins` takes them, n_units).'
+    graph = model.graph if inference_graph is None else inference_graph
+    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
+    n_units = len(model.start_pdf)
+    return model._checked_categories(inference_graph, arc_cat, init_cat, n_units), n_units
+
+
 def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, scale=1.):
     '''(best, start, end, unit, margin) on the device: the Viterbi score (0-d float64) and the
     unit segment lattice of the beam -- every (unit, start, end) such that some path on which the
@@ -853,19 +848,10 @@ def _unit_segments(model, data, beam=10., max_dur=None, inference_graph=None, sc
     has margin 0.  Otherwise as `decode`.'''
     beam, max_dur = hk.check_segments(beam, max_dur, 'unit_segments')
     model._refuse_durations('the segment functions (unit_segments)')
-    graph = model.graph if inference_graph is None else inference_graph
-    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
-    n_units = len(model.start_pdf)
-    src, _ = graph.out_arcs()
-    cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_units)
-    stats = model.sufficient_statistics(data)
-    pc_all = model._emissions().expected_log_likelihood(stats)
-    if getattr(getattr(graph, '_set', None), 'is_bound', False):
-        model._bound_set(graph).refresh(pc_all.dtype)
-    batch = model._batch_of_one(graph, len(stats), pc_all.dtype)
+    cats, n_units = _checked_unit_categories(model, inference_graph)
+    batch, pc_llhs, n_frames = model._search_input(data, inference_graph, scale)
     best, _, frame, unit, seg = hk.segment_margins(
-        batch, hk.gather(batch, pc_all, scale), *cats, n_units, beam,
-        max(len(stats), 1) if max_dur is None else max_dur)
+        batch, pc_llhs, *cats, n_units, beam, max(n_frames, 1) if max_dur is None else max_dur)
     start, end, unit, margin = hk.segments_within(frame, unit, seg, beam)
     return best[0], start.to(torch.int32), end.to(torch.int32), unit, margin
 
@@ -874,18 +860,10 @@ def _segment_posteriors_of(model, data, min_post, max_dur, inference_graph, scal
     '`hk.segment_posteriors` of one utterance under the unit-start categories: its five outputs.'
     min_post, max_dur = hk.check_segment_posteriors(min_post, max_dur, what)
     model._refuse_durations(f'the segment functions ({what})')
-    graph = model.graph if inference_graph is None else inference_graph
-    arc_cat, init_cat = unit_start_categories(graph, model.start_pdf, model.end_pdf)
-    n_units = len(model.start_pdf)
-    src, _ = graph.out_arcs()
-    cats = hk.check_arc_categories([len(src)], [graph.n_states], [arc_cat], [init_cat], n_units)
-    stats = model.sufficient_statistics(data)
-    pc_all = model._emissions().expected_log_likelihood(stats)
-    if getattr(getattr(graph, '_set', None), 'is_bound', False):
-        model._bound_set(graph).refresh(pc_all.dtype)
-    batch = model._batch_of_one(graph, len(stats), pc_all.dtype)
-    return hk.segment_posteriors(batch, hk.gather(batch, pc_all, scale), *cats, n_units, min_post,
-                                 max(len(stats), 1) if max_dur is None else max_dur)
+    cats, n_units = _checked_unit_categories(model, inference_graph)
+    batch, pc_llhs, n_frames = model._search_input(data, inference_graph, scale)
+    return hk.segment_posteriors(batch, pc_llhs, *cats, n_units, min_post,
+                                 max(n_frames, 1) if max_dur is None else max_dur)
 
 
 def _unit_segment_posteriors(model, data, min_post=1e-3, max_dur=None, inference_graph=None,
