@@ -16,6 +16,7 @@ _torch.set_num_threads(int(_os.environ.get('BEER_HOST_THREADS',
 from .models import *
 from .inference import *
 from .adaptation import *
+from .scoring import *
 from . import dists
 from . import features
 from . import graph

@@ -219,6 +219,16 @@ def nbest_list(k):
     return 1 if k <= 1 else (2 if k <= 2 else (4 if k <= 4 else (8 if k <= 8 else 16)))
 
 
+# BEER_EDIT_* of include/beer_hip.h: the length limits and what `beer_edit_distance_route` returns
+EDIT_MAX_LEN, EDIT_MAX_LEN_OPS = 1 << 30, (1 << 21) - 1
+EDIT_OPS, EDIT_ROW_LDS, EDIT_ROW_WS = 0x100, 0x1000, 0x2000
+
+
+def edit_team(route):
+    'BEER_EDIT_TEAM: the lanes that share one pair of sequences.'
+    return route & 0xFF
+
+
 # BEER_ARCS_* of include/beer_hip.h: what `beer_hmm_arcs_route` returns
 ARCS_BLOCK, ARCS_ARCS_LDS, ARCS_FRAME_LDS, ARCS_UTT_LDS = 0x1000, 0x100, 0x200, 0x400
 
@@ -491,6 +501,10 @@ SIGNATURES = {
     'beer_features_deltas': [ctypes.c_int32, c_p, c_l, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, c_p, c_p, c_p],
     'beer_features_cmn': [ctypes.c_int32, c_p, ctypes.c_int32, ctypes.c_int32, c_p, c_p],
+    'beer_unit_sequences': [c_p, c_p, c_p, c_l, c_p, ctypes.c_int32, c_p, c_p, c_p, c_p],
+    'beer_edit_distance': [c_p, c_p, c_p, c_l, c_p, c_p, c_l, ctypes.c_int32, ctypes.c_int32, c_p,
+                           c_p, c_p, c_z, c_p],
+    'beer_edit_distance_route': [ctypes.c_int32, ctypes.c_int32, c_i],     # (host only: no stream)
     'beer_copy_pinned': [c_p, c_p, c_z, c_p],
     'beer_clock_probe': [c_p, c_i, c_p],
     'beer_suffstats_mean': [c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p],
@@ -533,6 +547,7 @@ SIZE_QUERIES = {
     'beer_hsmm_arcs_scratch_doubles': [c_i, c_p, c_i],
     'beer_frames_llh_backward_workspace_bytes': [c_i, c_i, c_l, c_i, c_i],
     'beer_cmllr_workspace_bytes': [c_i, c_i, c_l],
+    'beer_edit_distance_scratch_bytes': [c_l, ctypes.c_int32, ctypes.c_int32, c_i],
 }
 
 

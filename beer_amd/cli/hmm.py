@@ -577,7 +577,7 @@ class train:
 
 class decode:
     '''print the most likely path of all the utterances of a dataset, or (--nsamples) paths
-    drawn from the posterior'''
+    drawn from the posterior, or (--mbr) the minimum-Bayes-risk one of several'''
 
     @staticmethod
     def setup(parser):
@@ -598,6 +598,16 @@ class decode:
         parser.add_argument('--distinct', action='store_true',
                             help='with --nbest: among the N state paths keep the best-scoring '
                                  'one of each unit sequence and renumber (may print fewer than N)')
+        parser.add_argument('--mbr', action='store_true',
+                            help='with --nbest N or --nsamples N: print, as "<uttid> <units>", '
+                                 'the one of the N hypotheses with the smallest expected edit '
+                                 'distance to the others (minimum Bayes risk)')
+        parser.add_argument('--risks', default=None,
+                            help='with --mbr: write "<uttid> <chosen> <risk> <risk of '
+                                 'hypothesis 1>" lines to this file')
+        parser.add_argument('--mbr-scale', default=1., type=float,
+                            help='with --mbr --nbest: hypothesis r weighs '
+                                 'exp(MBR_SCALE * (score_r - score_1))')
         parser.add_argument('-s', '--acoustic-scale', default=1., type=float)
         parser.add_argument('--predictive', action='store_true',
                             help='decode with the posterior-predictive (Student-t) emission '
@@ -621,6 +631,17 @@ class decode:
                 (args.nbest is not None or args.nsamples is not None):
             raise SystemExit('--predictive decodes the most likely path: not with --nbest or '
                              '--nsamples')
+        if getattr(args, 'mbr', False):
+            if args.nbest is None and args.nsamples is None:
+                raise SystemExit('--mbr chooses among hypotheses: give --nbest N or --nsamples N')
+            if getattr(args, 'predictive', False):
+                raise SystemExit('--mbr: not with --predictive')
+            if args.scores is not None or args.distinct:
+                raise SystemExit('--mbr prints one hypothesis: not with --scores or --distinct')
+            if args.nsamples is not None and args.nsamples < 1:
+                raise SystemExit('--nsamples: at least 1')
+        elif getattr(args, 'risks', None) is not None:
+            raise SystemExit('--risks goes with --mbr')
 
     @staticmethod
     def nbest_lines(uttid, paths, scores, start_pdf, per_frame=False, distinct=False):
@@ -641,6 +662,36 @@ class decode:
         return out
 
     @staticmethod
+    def mbr(args, model, feats, use, kept, logger):
+        'decode --mbr: the hypothesis of smallest expected edit distance among the N of a search.'
+        if not kept:
+            paths, scores = [], None
+        elif args.nbest is not None:
+            paths, scores = beer.decode_nbest_batch(model, feats, args.nbest, inference_graphs=use,
+                                                    scale=args.acoustic_scale)
+        else:
+            generator = torch.Generator(device=_device())
+            generator.manual_seed(args.seed)
+            paths = beer.sample_paths_batch(model, feats, inference_graphs=use,
+                                            scale=args.acoustic_scale, nsamples=args.nsamples,
+                                            generator=generator)
+            scores = None
+        _, index, risk = beer.mbr_select(model, paths, scores, args.mbr_scale) if kept else \
+            ([], torch.zeros(0), torch.zeros(0, 1))
+        index, risk = index.cpu().tolist(), risk.cpu().numpy()
+        risk_lines = []
+        for n, (uttid, stack) in enumerate(zip(kept, paths)):
+            path = stack[index[n]].cpu().numpy()
+            phones = phones_of_path(path, model.start_pdf, args.per_frame) \
+                if path.size and path[0] >= 0 else []
+            print(uttid, ' '.join(phones))
+            risk_lines.append(f'{uttid} {index[n] + 1} {risk[n, index[n]]:.6f} {risk[n, 0]:.6f}\n')
+        if args.risks is not None:
+            with open(args.risks, 'w') as f:
+                f.writelines(risk_lines)
+        logger.info(f'successfully chose among the hypotheses of {len(kept)} utterances.')
+
+    @staticmethod
     def main(args, logger):
         decode.check(args)
         model = _load(args.model).to(_device())
@@ -648,6 +699,9 @@ class decode:
         alis = _load_alis(args.alis)
         feats, graphs, kept = _shard(model, dataset, _utt_ids(args.utts, dataset), alis, logger)
         use = None if alis is None else [g if g is not None else model.graph for g in graphs]
+        if args.mbr:
+            decode.mbr(args, model, feats, use, kept, logger)
+            return
         if args.nbest is not None:
             paths, scores = beer.decode_nbest_batch(
                 model, feats, args.nbest, inference_graphs=use, scale=args.acoustic_scale) \
@@ -1023,6 +1077,123 @@ class posteriors:
         logger.info(f'successfully computed the posteriors for {count} utterances.')
 
 
+def read_alignments(path):
+    'A file of per-frame alignments "<uttid> <label per frame ...>" as {uttid: [labels]}, in order.'
+    alis = {}
+    with open(path) as f:
+        for line in f:
+            tokens = line.split()
+            if tokens:
+                alis[tokens[0]] = tokens[1:]
+    return alis
+
+
+def _merge_repeats(labels):
+    labels = np.asarray(labels, dtype=np.int64)
+    return labels[np.concatenate([[True], labels[1:] != labels[:-1]])] if labels.size else labels
+
+
+class evaluate:
+    '''score per-frame unit alignments against reference alignments (the recipe's score_aud):
+    every unit is mapped to the reference label it shares most frames with, then the equivalent
+    phone error rate (repeats merged on both sides; edit distances on the GPU), the normalised
+    mutual information, the entropy rate of the units and the recall / precision / F-score of
+    the unit boundaries are printed as "key value" lines'''
+
+    KEYS = ('PER', 'sub', 'del', 'ins', 'NMI', 'entropy_rate', 'perplexity', 'recall',
+            'precision', 'fscore', 'n_units')
+
+    @staticmethod
+    def setup(parser):
+        parser.add_argument('--delta', default=2, type=int,
+                            help='frames a unit boundary may lie from a reference boundary and '
+                                 'still hit it')
+        parser.add_argument('--mapping', default=None,
+                            help='write the "<unit> <reference label>" mapping to this file')
+        parser.add_argument('--lists', action='store_true',
+                            help='the hypothesis file holds lists, "<uttid>-<r> <labels>" '
+                                 '(decode --nbest / --nsamples --per-frame): the scores are '
+                                 'those of every utterance\'s first hypothesis, and closest_PER '
+                                 'that of the closest one of its list')
+        parser.add_argument('ref_ali', help='reference per-frame alignments')
+        parser.add_argument('hyp_ali', help='per-frame alignments to score')
+
+    @staticmethod
+    def collect(ref, hyp, lists):
+        '''(uttids, reference labels, hypothesis lists) of the utterances both sides have, in the
+        reference's order, and the number skipped; SystemExit naming an utterance whose sides
+        differ in length.'''
+        if lists:
+            grouped = {}
+            for label, frames in hyp.items():
+                uttid, _, rank = label.rpartition('-')
+                if not uttid or not rank.isdigit():
+                    raise SystemExit(f'--lists: "{label}" is not "<uttid>-<r>"')
+                grouped.setdefault(uttid, []).append((int(rank), frames))
+            hyp = {u: [frames for _, frames in sorted(h, key=lambda e: e[0])]
+                   for u, h in grouped.items()}
+        else:
+            hyp = {u: [frames] for u, frames in hyp.items()}
+        uttids = [u for u in ref if u in hyp]
+        skipped = len(ref) - len(uttids) + sum(1 for u in hyp if u not in ref)
+        for u in uttids:
+            for frames in hyp[u]:
+                if len(frames) != len(ref[u]):
+                    raise SystemExit(f'{u}: {len(ref[u])} reference frames, {len(frames)} in '
+                                     'the hypothesis')
+        return uttids, [ref[u] for u in uttids], [hyp[u] for u in uttids], skipped
+
+    @staticmethod
+    def scores(ref, hyps, delta=2):
+        '''The scores as (key, text) lines, the unit -> reference label mapping and, for lists,
+        the line of the closest hypotheses: `ref` one list of labels per utterance, `hyps` one
+        list of such lists per utterance.'''
+        ref_names = sorted({l for utt in ref for l in utt})
+        hyp_names = sorted({l for lst in hyps for utt in lst for l in utt})
+        ref_id = {l: i for i, l in enumerate(ref_names)}
+        hyp_id = {l: i for i, l in enumerate(hyp_names)}
+        R = [np.asarray([ref_id[l] for l in utt], dtype=np.int64) for utt in ref]
+        H = [[np.asarray([hyp_id[l] for l in utt], dtype=np.int64) for utt in lst] for lst in hyps]
+        first = [lst[0] for lst in H]
+        counts = beer.contingency(R, first) if R else np.zeros((0, 0), dtype=np.int64)
+        if counts.shape[0] < len(hyp_names):          # (units only later ranks use: no overlap)
+            counts = np.concatenate([counts, np.zeros((len(hyp_names) - counts.shape[0],
+                                                       counts.shape[1]), dtype=np.int64)])
+        mapping = beer.maxoverlap_mapping(counts)
+        refs = [_merge_repeats(r) for r in R]
+        errors = beer.token_error_rate(refs, [_merge_repeats(mapping[h]) for h in first])
+        nmi = beer.normalized_mutual_information(counts)
+        entropy, perplexity = beer.entropy_rate(first)
+        bounds = beer.boundary_scores(R, first, delta=delta)
+
+        def percent(n):
+            return '%.2f' % (100. * n / errors.n_ref if errors.n_ref else 0.)
+        lines = [('PER', '%.2f' % errors.rate), ('sub', percent(errors.sub)),
+                 ('del', percent(errors.dele)), ('ins', percent(errors.ins)),
+                 ('NMI', '%.2f' % nmi), ('entropy_rate', '%.2f' % entropy),
+                 ('perplexity', '%.2f' % perplexity), ('recall', '%.2f' % bounds.recall),
+                 ('precision', '%.2f' % bounds.precision), ('fscore', '%.2f' % bounds.fscore),
+                 ('n_units', str(len(hyp_names)))]
+        closest = beer.closest_error_rate(refs, [[_merge_repeats(mapping[h]) for h in lst]
+                                               for lst in H])
+        named = [(u, ref_names[int(mapping[i])]) for i, u in enumerate(hyp_names)] \
+            if ref_names else []
+        return lines, named, ('closest_PER', '%.2f' % closest.rate)
+
+    @staticmethod
+    def main(args, logger):
+        ref, hyp = read_alignments(args.ref_ali), read_alignments(args.hyp_ali)
+        uttids, R, H, skipped = evaluate.collect(ref, hyp, args.lists)
+        lines, mapping, closest = evaluate.scores(R, H, args.delta)
+        for key, text in lines + ([closest] if args.lists else []):
+            print(key, text)
+        if args.mapping is not None:
+            with open(args.mapping, 'w') as f:
+                f.writelines(f'{unit} {label}\n' for unit, label in mapping)
+        logger.info(f'scored {len(uttids)} utterances; {skipped} without a counterpart were '
+                    'skipped.')
+
+
 def duration_lines(model):
     '''The lines of `beer hmm durations`: "<unit> <state> <mean frames> <mode> <p(1)> .. <p(D)>"
     per state of every unit (the states of a unit counted from 0), from the posterior means of
@@ -1055,4 +1226,4 @@ class durations:
 
 COMMANDS = [accumulate, decode, mkaligraph, mkdecodegraph, mkphoneloop, mkphoneloopbigram,
             mkphoneloopgraph, mkphones, posteriors, phonelist, train, update, score, lattice,
-            segments, adapt, durations, boundaries]
+            segments, adapt, durations, evaluate, boundaries]

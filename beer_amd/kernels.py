@@ -19,7 +19,8 @@ __all__ = ['normal_llh', 'mixtureset_estep', 'normal_accumulate', 'weights_from_
            'is_dense', 'dense_llh', 'dense_softmax', 'dense_accumulate', 'rowdot',
            'attach_stats_grad', 'differentiable_stats', 'sample_stats', 'attach_frame_grad',
            'frames_llh_backward', 'normal_llh_autograd', 'cmllr_frame_params', 'cmllr_table',
-           'cmllr_accumulate', 'cmllr_apply', 'CmllrTable']
+           'cmllr_accumulate', 'cmllr_apply', 'CmllrTable', 'unit_sequences', 'edit_distance',
+           'edit_distance_route', 'edit_distance_launch']
 
 LOG_2PI = 1.8378770664093453
 
@@ -969,3 +970,134 @@ def normal_llh_autograd(stats, exp_stats, cov_type):
     if has_source(stats):
         return _FrameLlh.apply(stats.source, exp_stats.detach(), stats.detach())
     return normal_llh(stats, exp_stats, cov_type)
+
+
+# ---------------------------------------------------------------------------
+# token sequences (csrc/editdist.hip)
+
+def _ragged(what, start, lens, n_sym):
+    """`start` / `lens` of a packed batch of sequences as (int64, int32) device tensors, checked
+    on the host against the `n_sym` packed symbols; and the lengths on the host."""
+    lens_h = torch.as_tensor(lens).detach().cpu().to(torch.int64).reshape(-1)
+    start_h = torch.as_tensor(start).detach().cpu().to(torch.int64).reshape(-1)
+    if lens_h.numel() != start_h.numel():
+        raise ValueError(f'{what}: {start_h.numel()} starts for {lens_h.numel()} lengths')
+    if lens_h.numel() and (int(lens_h.min()) < 0 or int(start_h.min()) < 0 or
+                           int((start_h + lens_h).max()) > n_sym):
+        raise ValueError(f'{what}: a sequence lies outside the {n_sym} packed symbols')
+    dev = _hip.require_device()
+    return start_h.to(dev), lens_h.to(torch.int32).to(dev), lens_h
+
+
+def unit_sequences(paths, start, lens, unit_of_pdf, per_frame=False):
+    """Packed pdf-id paths as unit sequences (`beer_unit_sequences`): (units int32 as long as
+    `paths` -- the units of sequence q compactly at units[start[q]:start[q] + n_units[q]] --,
+    n_units int32 [n_seq], frame_unit int32 as long as `paths` or None).  `paths`: int64, packed;
+    `unit_of_pdf`: int32 [n_pdf], a unit's index at its first pdf and -1 elsewhere.
+    n_units: 0 for an empty sequence, -1 for one that begins with a negative symbol (an n-best
+    rank without a path), -2 for one with a pdf outside the table or a first pdf inside a unit."""
+    paths = _hip.on_device(torch.as_tensor(paths), torch.int64).reshape(-1)
+    table = _hip.on_device(torch.as_tensor(unit_of_pdf), torch.int32).reshape(-1)
+    if table.numel() < 1:
+        raise ValueError('unit_sequences: an empty pdf table')
+    start, lens, _ = _ragged('unit_sequences', start, lens, paths.numel())
+    dev = paths.device
+    units = torch.empty(paths.numel(), dtype=torch.int32, device=dev)
+    n_units = torch.empty(lens.numel(), dtype=torch.int32, device=dev)
+    frames = torch.empty(paths.numel(), dtype=torch.int32, device=dev) if per_frame else None
+    _hip.call('beer_unit_sequences', _hip.ptr(paths), _hip.ptr(start), _hip.ptr(lens),
+              lens.numel(), _hip.ptr(table), table.numel(), _hip.ptr(units), _hip.ptr(n_units),
+              _hip.ptr(frames))
+    return units, n_units, frames
+
+
+def edit_distance_route(max_short, max_long, ops=False):
+    """beer_edit_distance_route: the form `beer_edit_distance` takes for pairs whose shorter side
+    has up to `max_short` symbols and whose longer side up to `max_long` (team size, cell type,
+    where a strip's boundary row waits).  HipInvalid where C refuses."""
+    route = _hip.lib().beer_edit_distance_route(int(max_short), int(max_long), int(bool(ops)))
+    if route == _hip.EINVAL:
+        raise _hip.HipInvalid(
+            f'edit_distance: sequences of {int(max_short)} x {int(max_long)} symbols: at most '
+            f'{_hip.EDIT_MAX_LEN_OPS if ops else _hip.EDIT_MAX_LEN}' + (' with ops' if ops else ''))
+    return route
+
+
+def edit_distance_launch(sym, start, lens, pair_a, pair_b, max_short, max_long, dist, ops=None,
+                         workspace=None):
+    """One `beer_edit_distance` call on tensors that are already int32 / int64 on the device
+    (`dist` [n_pair], `ops` [n_pair, 3] or None are written); `workspace`: a uint8 tensor of at
+    least `beer_edit_distance_scratch_bytes`, by default the call's kept scratch."""
+    n_pair = pair_a.numel()
+    edit_distance_route(max_short, max_long, ops is not None)
+    need = _hip.lib().beer_edit_distance_scratch_bytes(n_pair, int(max_short), int(max_long),
+                                                       int(ops is not None))
+    if workspace is None:
+        workspace, _ = _hip.scratch('beer_edit_distance', need, sym.device)
+    _hip.call('beer_edit_distance', _hip.ptr(sym), _hip.ptr(start), _hip.ptr(lens), lens.numel(),
+              _hip.ptr(pair_a), _hip.ptr(pair_b), n_pair, int(max_short), int(max_long),
+              _hip.ptr(dist), _hip.ptr(ops), _hip.ptr(workspace),
+              0 if workspace is None else workspace.numel())
+
+
+# the shorter side's length classes: a team of 8 / 16 / 32 / 64 lanes in one strip, then strips
+_EDIT_CLASSES = (8, 16, 32, 64)
+
+
+def edit_distance(sym, start, lens, pair_a, pair_b, ops=False):
+    """Levenshtein distances of pairs of packed int32 sequences (`beer_edit_distance`): int32
+    [n_pair] on the device, with `ops` also int32 [n_pair, 3], the (substitutions, deletions,
+    insertions) of the cheapest alignment with the smallest such triple; a deletion consumes a
+    symbol of sequence `pair_a[p]` alone.
+    The pairs are launched by the form their shorter side asks for (a team of 8 / 16 / 32 / 64
+    lanes; strips beyond 64 symbols), each class ordered by
+    len_a * len_b, largest first, so that the teams of a wave finish together; the results come
+    back in the caller's order.  ValueError: a pair index outside the sequences (checked on the
+    host, before any device work)."""
+    sym = _hip.on_device(torch.as_tensor(sym), torch.int32).reshape(-1)
+    start, lens, lens_h = _ragged('edit_distance', start, lens, sym.numel())
+    dev = sym.device
+    pairs = []
+    for what, idx in (('pair_a', pair_a), ('pair_b', pair_b)):
+        idx = torch.as_tensor(idx).reshape(-1)
+        if idx.numel() == 0:
+            idx = idx.to(torch.int32)
+        if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+            raise ValueError(f'edit_distance: {what} must be integers, not {idx.dtype}')
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= lens.numel()):
+            raise ValueError(f'edit_distance: {what} outside [0, {lens.numel()}): '
+                             f'{int(idx.min())} .. {int(idx.max())}')
+        pairs.append(_hip.on_device(idx, torch.int32))
+    pair_a, pair_b = pairs
+    if pair_a.numel() != pair_b.numel():
+        raise ValueError(f'edit_distance: {pair_a.numel()} and {pair_b.numel()} pair indices')
+    n_pair = pair_a.numel()
+    dist = torch.empty(n_pair, dtype=torch.int32, device=dev)
+    moves = torch.empty(n_pair, 3, dtype=torch.int32, device=dev) if ops else None
+    if n_pair == 0:
+        return (dist, moves) if ops else dist
+    wide = lens.to(torch.int64)
+    la, lb = wide[pair_a.long()], wide[pair_b.long()]
+    short, long_ = torch.minimum(la, lb), torch.maximum(la, lb)
+    team = torch.bucketize(short, torch.tensor(_EDIT_CLASSES, device=dev))
+    # by class, then by the size of the table, largest first (stable: equal pairs keep their order)
+    order = torch.argsort(short * long_, descending=True, stable=True)
+    order = order[torch.argsort(team[order], stable=True)]
+    counts = torch.bincount(team, minlength=len(_EDIT_CLASSES) + 1)
+    tops = torch.stack([torch.stack([torch.where(team == c, v, torch.zeros_like(v)).max()
+                                     for v in (short, long_)]) for c in range(len(_EDIT_CLASSES) + 1)])
+    counts, tops = counts.tolist(), tops.tolist()
+    a_sorted, b_sorted = pair_a[order].contiguous(), pair_b[order].contiguous()
+    d_sorted = torch.empty_like(dist)
+    m_sorted = torch.empty_like(moves) if ops else None
+    lo = 0
+    for c, n in enumerate(counts):
+        if n:
+            edit_distance_launch(sym, start, lens, a_sorted[lo:lo + n], b_sorted[lo:lo + n],
+                                 tops[c][0], tops[c][1], d_sorted[lo:lo + n],
+                                 m_sorted[lo:lo + n] if ops else None)
+        lo += n
+    dist[order] = d_sorted
+    if ops:
+        moves[order] = m_sorted
+    return (dist, moves) if ops else dist

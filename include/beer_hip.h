@@ -1948,6 +1948,83 @@ int beer_features_deltas(int32_t nutt, const int64_t* frame_off, int64_t total_f
 int beer_features_cmn(int32_t nutt, const int64_t* frame_off, int32_t D, int32_t ld,
                       double* x, void* stream);
 
+/* ---- token sequences: unit sequences of paths, edit distances (csrc/editdist.hip) ----
+ * Integer arithmetic only: every output is exact and the same bits in every run. */
+
+/* Pdf-id paths collapsed into unit sequences (`phones_of_path` of the command line, without the
+ * names), one wave per sequence.
+ *   sym          packed int64 symbols (pdf ids) of all the sequences (read only)
+ *   start, len   [n_seq] int64 / int32: sequence q is sym[start[q] .. start[q] + len[q])
+ *   unit_of_pdf  [n_pdf] int32: the index of the unit whose FIRST pdf this is, else -1
+ *   units        int32, as large as sym: the units of sequence q are written compactly at
+ *                units[start[q] ..]; a sequence never has more units than symbols
+ *   n_units      [n_seq] int32
+ *   frame_unit   NULL, or int32 as large as sym: for every symbol the unit (the value written to
+ *                `units`) that is running at that frame -- the per-frame form of the sequence
+ * Position 0 starts a unit; position t > 0 starts one iff sym[t] != sym[t-1] and
+ * unit_of_pdf[sym[t]] >= 0.  n_units[q] is the number of starts, except:
+ *   len[q] <= 0                          0, nothing written
+ *   sym[start[q]] < 0                   -1, nothing written (an n-best rank without a path)
+ *   a pdf outside [0, n_pdf), or a first pdf that is no unit's first
+ *                                       -2; what `units` / `frame_unit` hold for q is unspecified
+ *                                       (nothing is written outside q's own range)
+ * EINVAL, checked before anything is launched: n_seq < 0, n_pdf < 1, a NULL pointer (but
+ * frame_unit) with n_seq > 0. */
+int beer_unit_sequences(const int64_t* sym, const int64_t* start, const int32_t* len,
+                        int64_t n_seq, const int32_t* unit_of_pdf, int32_t n_pdf, int32_t* units,
+                        int32_t* n_units, int32_t* frame_unit, void* stream);
+
+/* Levenshtein distances of a ragged batch of sequence pairs.
+ *   sym          packed int32 symbols of all the sequences (read only)
+ *   start, len   [n_seq] int64 / int32, as above
+ *   pair_a/b     [n_pair] int32 sequence indices; repeats and a == b are allowed
+ *   max_short    >= min(len[a], len[b]) of every pair     } the caller's: the launcher reads no
+ *   max_long     >= max(len[a], len[b]) of every pair     } device memory
+ *   dist         [n_pair] int32: the smallest number of substitutions, deletions and insertions
+ *                that turn sequence a into sequence b
+ *   ops          NULL, or [n_pair, 3] int32: (substitutions, deletions, insertions) of the
+ *                alignment that is, among ALL alignments of that smallest cost, the one with the
+ *                lexicographically smallest (sub, del, ins).  A deletion consumes a symbol of a
+ *                alone, an insertion a symbol of b alone; ops(b, a) is ops(a, b) with the two
+ *                swapped.  Computed with no back-trace: the recursion runs on cells
+ *                cost << 42 | sub << 21 | del, whose integer order is that lexicographic order
+ *   workspace    device scratch of beer_edit_distance_scratch_bytes(n_pair, max_short, max_long,
+ *                ops != NULL) bytes (0: none needed, NULL will do); its content is opaque
+ * Length limits, from the field widths: BEER_EDIT_MAX_LEN_OPS = 2^21 - 1 symbols with `ops`
+ * (sub, del <= 2^21 - 1; cost <= 2^22 - 2 in 22 bits), BEER_EDIT_MAX_LEN = 2^30 without (the
+ * cost, at most twice that inside the table, in a uint32).
+ * EINVAL, checked before anything is launched: max_short < 0, max_long < max_short, max_long
+ * beyond the limit, n_seq or n_pair < 0, a NULL pointer (but ops / workspace) or n_seq = 0 with
+ * n_pair > 0, a workspace smaller than the query says.  The pair indices live on the device: the
+ * launcher cannot read them, so a pair that names a sequence outside [0, n_seq), a sequence of
+ * negative length, or one longer than max_short / max_long admit, reads nothing and gets dist
+ * (and ops) -1 -- the caller checks its indices on the host first. */
+#define BEER_EDIT_MAX_LEN (1 << 30)
+#define BEER_EDIT_MAX_LEN_OPS ((1 << 21) - 1)
+int beer_edit_distance(const int32_t* sym, const int64_t* start, const int32_t* len, int64_t n_seq,
+                       const int32_t* pair_a, const int32_t* pair_b, int64_t n_pair,
+                       int32_t max_short, int32_t max_long, int32_t* dist, int32_t* ops,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t beer_edit_distance_scratch_bytes(int64_t n_pair, int32_t max_short, int32_t max_long,
+                                        int want_ops);
+
+/* The form beer_edit_distance picks for these maxima (host only: it launches nothing), built
+ * from the launcher's own plan:
+ *   team | BEER_EDIT_OPS | BEER_EDIT_ROW_LDS or BEER_EDIT_ROW_WS
+ *   team   lanes that share a pair, the shorter sequence on them: 8 / 16 / 32 / 64, the smallest
+ *          that covers max_short (64 beyond); a wave holds 64 / team pairs, a workgroup 4 waves
+ *   BEER_EDIT_OPS      cells are uint64 (cost, sub, del) instead of uint32: `ops` is asked for
+ *   max_short <= 64    one strip of rows, nothing is kept between strips: neither ROW bit
+ *   BEER_EDIT_ROW_LDS  strips of 64 rows; the strip's last row, max_long + 1 cells of 4 (8 with
+ *                      ops) bytes, waits in a wave's 16 KiB of LDS: max_long <= 4095 (2047)
+ *   BEER_EDIT_ROW_WS   ... beyond that in the workspace, one row per wave of the grid
+ * BEER_EINVAL exactly where beer_edit_distance refuses these three arguments. */
+#define BEER_EDIT_OPS 0x100
+#define BEER_EDIT_ROW_LDS 0x1000
+#define BEER_EDIT_ROW_WS 0x2000
+#define BEER_EDIT_TEAM(route) ((route) & 0xFF)
+int beer_edit_distance_route(int32_t max_short, int32_t max_long, int want_ops);
+
 /* Copy `nbytes` (a multiple of 16, both pointers 16-byte aligned) from PINNED
  * host memory to device memory with a kernel on `stream`.  Used for the small
  * batch / graph descriptors: a copy-engine transfer queued behind running
